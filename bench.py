@@ -7,12 +7,15 @@ c -> rank c mod N (independent clips: no data-path collective), then one RCCL al
 `python bench.py --gpus N` with no RANK in the environment starts the N ranks itself (fresh child processes; the parent never
 touches the GPU); under torchrun it is one of the ranks.  Rank 0 prints ONE JSON line.
 
-The headline runs the f16-MFMA precision (f16 operands on the f16 matrix cores, f32 accumulate).  Outside the timed region every one of
-its greedy decisions on this batch is checked against the exact precision under teacher forcing (streamkit_amd/parity.py; the line carries
+The headline runs the f16-MFMA precision (f16 operands on the f16 matrix cores, f32 accumulate).  `value` is with the PCM resident in HBM
+(the bench contract).  A plain run does only what the headline needs: set-up, --warmup steps, --steps timed steps, the result line.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float64; the inputs are seeded, identical from run to run).
+
+--full adds everything else, outside the timed region: `value_pcie_inclusive` (PCM starting from pinned host memory); every greedy decision
+of f16_mfma on this batch checked against the exact precision under teacher forcing (streamkit_amd/parity.py; the line carries
 steps_checked / argmax_disagreements / max_margin_at_disagreement, and the process exits non-zero when a decision differs away from a
-near-tie); the exact mode (f32-chain contractions, bit-identical to the CPU oracle) is timed beside it and reported under "modes", and a
-sample of clips is compared with the oracle in the cpu_baseline leg.  `value` is with the PCM resident in HBM (the bench contract);
-`value_pcie_inclusive` starts from pinned host memory.
+near-tie); the exact mode (f32-chain contractions, bit-identical to the CPU oracle) timed beside it under "modes"; the roofline, plugin-path,
+quantised-file and TTS rows; and a sample of clips compared with the oracle in the cpu_baseline leg.  Each stays switchable off by its --no-* option.
 """
 import argparse
 import json
@@ -40,6 +43,9 @@ def parse_args():
     ap.add_argument("--clips", type=int, default=64, help="clips per GPU per step")
     ap.add_argument("--size", default="small")
     ap.add_argument("--precision", default="f16_mfma", choices=["f16_mfma", "exact"], help="precision of the headline number")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline (PCIe-inclusive timing, the other precision and the "
+                    "teacher-forced parity check, roofline, plugin-path, quantised-file and TTS rows, CPU baseline); the --no-* options switch single rows off")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (rank 0's clips) as DIR/<name>.npy")
     ap.add_argument("--no-other-mode", action="store_true", help="skip timing the other precision beside the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -176,6 +182,34 @@ def tts_leg(reps=5):
         tts.close()
 
 
+def dump_outputs(out_dir, res):
+    """What a caller of the timed path receives from its last step (Context.full_batch: one result per clip), as float64 arrays, one row per clip.
+    Per-token and per-segment fields are padded to the longest clip: ids and times with -1, the rest with 0; clips.npy holds the counts."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    B = len(res)
+    nt = max([len(r["tokens"]) for r in res] + [1])
+    ns = max([len(r["segments"]) for r in res] + [1])
+    texts = [b"".join(s["text"] for s in r["segments"]) for r in res]
+    nb = max([len(t) for t in texts] + [1])
+    tok = np.zeros((B, nt, 5)); tok[:, :, :2] = -1                      # (id, tid, p, plog, margin)
+    seg = np.full((B, ns, 3), -1.0)                                        # (t0, t1, n_tokens), times in 10 ms units
+    txt = np.full((B, nb), -1.0)                                           # the segments' UTF-8 bytes, concatenated
+    clips = np.zeros((B, 6))
+    for i, r in enumerate(res):
+        if r["tokens"]:
+            tok[i, :len(r["tokens"])] = r["tokens"]
+        for j, s in enumerate(r["segments"]):
+            seg[i, j] = (s["t0"], s["t1"], len(s["tokens"]))
+        txt[i, :len(texts[i])] = np.frombuffer(texts[i], np.uint8)
+        clips[i] = (len(r["tokens"]), len(r["segments"]), r["n_windows"], r["n_decode_steps"], r["fallback_requested"], r["lang_id"])
+    arrays = {"token_id": tok[:, :, 0], "token_tid": tok[:, :, 1], "token_p": tok[:, :, 2], "token_plog": tok[:, :, 3], "token_margin": tok[:, :, 4],
+              "segment_t0": seg[:, :, 0], "segment_t1": seg[:, :, 1], "segment_n_tokens": seg[:, :, 2], "text_bytes": txt,
+              "clips": clips}     # columns: n_tokens, n_segments, n_windows, n_decode_steps, fallback_requested, lang_id
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -250,7 +284,7 @@ def main():
     clip_ids = skd.shard_clip_ids(B * world, rank, world)
     host = np.stack([synth.clip(c, n_samples) for c in clip_ids])
     dev = torch.from_numpy(host).cuda()
-    pinned = torch.from_numpy(host).pin_memory()
+    pinned = torch.from_numpy(host).pin_memory() if args.full else None
     torch.cuda.synchronize()
     ptrs = [dev[i].data_ptr() for i in range(B)]
     ns = [n_samples] * B
@@ -299,12 +333,16 @@ def main():
     value = args.steps * audio_per_step / dt
     modes = {args.precision: {"value": round(value, 2), "ms_per_step": round(1000.0 * dt / args.steps, 3),
                               "encode_ms": round(timing["encode_ms"], 3), "decode_ms": round(timing["decode_ms"], 3), "mel_ms": round(timing["mel_ms"], 3)}}
-    dt_h, _ = timed(1, max(2, min(args.steps, 5)), from_host=True)
-    pcie_value = max(2, min(args.steps, 5)) * audio_per_step / dt_h
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
+    pcie_value = None
+    if args.full:
+        dt_h, _ = timed(1, max(2, min(args.steps, 5)), from_host=True)
+        pcie_value = max(2, min(args.steps, 5)) * audio_per_step / dt_h
 
     other = "exact" if args.precision == "f16_mfma" else "f16_mfma"
     identical = None
-    if not args.no_other_mode:
+    if args.full and not args.no_other_mode:
         n_o = max(2, min(args.steps, 5))
         ctx.set_precision(other)
         dt_o, res_o = timed(1, n_o)
@@ -328,7 +366,7 @@ def main():
 
     # every decision of the f16_mfma precision on THIS batch, checked against the exact precision under teacher forcing (streamkit_amd/parity.py)
     parity = None
-    if not args.no_other_mode:
+    if args.full and not args.no_other_mode:
         from streamkit_amd.parity import teacher_forced_compare
         try:
             tf = teacher_forced_compare(ctx, None, params, device_ptrs=ptrs, n_samples=ns)
@@ -363,11 +401,12 @@ def main():
         "transcripts_f16_vs_exact": identical,
         "parity_f16_vs_exact_teacher_forced": parity,
         "gather_ms": round(gather_ms, 3) if world > 1 else 0.0,
-        "value_pcie_inclusive": round(pcie_value, 2),
         "model_load_ms": round(model_load_ms, 1), "ctx_create_ms": round(ctx_create_ms, 1),
     }
+    if pcie_value is not None:
+        out["value_pcie_inclusive"] = round(pcie_value, 2)
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # (1) the dominant kernel's launches in the TIMED configuration — step graphs, the engine's row groups on their streams, eight steps enqueued ahead — stamped by the
         # kernel's own clock (include/skw_engine.h skw_ctx_kernel_clock: first wave in -> last wave out, live rows per launch); one graph-capturing step, then the measured one
         kclk = None
@@ -519,7 +558,7 @@ def main():
                                     "note": "the step the per-kernel event pairs were taken in (eager launches, an event pair per kernel): its wall time is not the benchmark's"}
         out["roofline"] = roof
 
-    if rank == 0 and world == 1 and not args.no_plugin_path:
+    if rank == 0 and world == 1 and args.full and not args.no_plugin_path:
         # the drop-in boundary, driver-run: (i) the headline precision, (ii) what a host gets that only swaps the .so (no `precision` parameter -> exact, the precision
         # that is bit-identical to the CPU oracle), (iii) the same on the reference's default file type (q5_1)
         out.update(plugin_path_leg(path, host, B, args.precision, "plugin_path"))
@@ -532,13 +571,13 @@ def main():
                                              "value_plugin_path_default on an f16 file, value_plugin_path_q5_1_default on the reference's default file type; "
                                              "value / value_plugin_path opt into precision=f16_mfma (teacher-forced tolerance mode)")
 
-    if rank == 0 and world == 1 and not args.no_tts:
+    if rank == 0 and world == 1 and args.full and not args.no_tts:
         try:
             out.update(tts_leg())
         except Exception as e:      # a side row must not cost the headline line
             out["tts"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # CPU baseline: the oracle (a port) on the host cores, bounded sample of the same workload
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from oracle_lib import OracleModel

@@ -13,5 +13,5 @@ for C in FETCH_SIZE WRITE_SIZE; do
 done
 cp $R/profiles/pmc_traffic.json $O/${TAG}_pmc_traffic.json 2>/dev/null
 python3 $R/tools/pmc_traffic.py /tmp/pmc_${TAG}_FETCH_SIZE/p_counter_collection.csv /tmp/pmc_${TAG}_WRITE_SIZE/p_counter_collection.csv $O/${TAG}_pmc_traffic.json $PREC > $O/${TAG}_pmc_hbm_traffic_per_kernel.txt
-cd $R && cp $O/${TAG}_pmc_traffic.json profiles/pmc_traffic.json && timeout -k 10 400 python3 bench.py --steps 5 --warmup 2 --precision $PREC > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err
+cd $R && cp $O/${TAG}_pmc_traffic.json profiles/pmc_traffic.json && timeout -k 10 400 python3 bench.py --full --steps 5 --warmup 2 --precision $PREC > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err
 tail -1 $O/${TAG}_bench_line.json
