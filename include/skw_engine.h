@@ -133,11 +133,19 @@ void skw_result_free(skw_result*);
  * it run on across calls of whisper_full_with_state; the reference node creates one state per instance (plugins/native/whisper/src/lib.rs:377-379), so an instance's n-th segment
  * that needs a sampled pass draws from where its earlier segments left the stream.  skw_full_batch_rng is skw_full_batch with that stream handed in and out per clip:
  * rng_state[i] = NULL (seed 0 for this call, what skw_full_batch does) or SKW_RNG_STATE_WORDS words — mt[624] and the index, initialised once by skw_rng_state_init — which the
- * call advances exactly as the reference's generator would advance on this clip.  Rows of a batch never share a stream, so the result does not depend on batch composition. */
+ * call advances exactly as the reference's generator would advance on this clip.  Rows of a batch never share a stream, so in the exact precision the result does not
+ * depend on batch composition (f16_mfma: under that precision's own contract for batch composition). */
 #define SKW_RNG_STATE_WORDS 625
 void skw_rng_state_init(uint32_t* state /* [SKW_RNG_STATE_WORDS] */);
 int  skw_full_batch_rng(skw_ctx*, const skw_full_params*, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                         uint32_t* const* rng_state /* [n_clips], entries may be NULL */, skw_result* results);
+/* Clips with different parameters in one batch: params[i] is clip i's own skw_full_params (every field may differ: language or auto-detection, task, no_timestamps,
+ * single_segment, max_tokens, max_initial_ts, the suppress_* rules, the thresholds, temperature and temperature_inc).  results[i] is what skw_full_batch_rng returns for
+ * clip i alone with params[i] and the same generator state: bit for bit in the exact precision, and in f16_mfma under that precision's contract for batch composition.
+ * An array whose entries are all equal gives exactly what skw_full_batch_rng gives.  rng_state as above (may be NULL).  The node's scheduler batches its instances'
+ * segments through this call whatever their parameters (the reference sets language and the suppress_* flags per instance, lib.rs:624-641). */
+int  skw_full_batch_mixed(skw_ctx*, const skw_full_params* params /* [n_clips] */, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                          uint32_t* const* rng_state /* NULL, or [n_clips] with entries that may be NULL */, skw_result* results);
 
 /* ---- decision trace / teacher forcing (parity instrumentation of the hot path; the reference has no counterpart) ----
  * skw_full_batch_traced is skw_full_batch that also returns, per clip, one record for EVERY sampling decision it made, in execution order

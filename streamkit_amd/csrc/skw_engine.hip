@@ -466,7 +466,7 @@ struct skw_ctx {
     hipStream_t stream = nullptr; hipEvent_t ev[6] = {};
     hipStream_t cur = nullptr;                       // stream the launch helpers enqueue on (== stream outside the decode groups)
     static const int MAX_GROUPS = 8; hipStream_t gstream[MAX_GROUPS] = {}; hipEvent_t gev[MAX_GROUPS] = {}; int n_groups = 1;
-    struct StepGraph { int g, r0, n, precision, ln_stats, kclk; unsigned sw_epoch; SkwLogitParams lp; hipGraphExec_t exec; }; std::vector<StepGraph> step_graphs; int use_graphs = 1;
+    struct StepGraph { int g, r0, n, precision, ln_stats, kclk; unsigned sw_epoch; SkwLogitParams lp; int rows; hipGraphExec_t exec; }; std::vector<StepGraph> step_graphs; int use_graphs = 1;
     char errbuf[512] = {0};
     std::vector<void*> allocs;
     // front end
@@ -488,6 +488,8 @@ struct skw_ctx {
     int* row_tok = nullptr;                          // per-row prompt token / detected language scratch
     float* probs = nullptr; uint32_t* rng = nullptr;   // sampled (t > 0) passes: probability workspace, std::mt19937 state per clip
     SkwSeqState* st = nullptr; SkwTokenOut* toks = nullptr; uint8_t* static_mask = nullptr; int static_mask_nst = -1;
+    // skw_full_batch_mixed: both static masks back to back ([0] without, [1] with the non-speech list; written at the first mixed call) and the rows' own rules, per window
+    uint8_t* static_mask_pair = nullptr; int static_mask_pair_built = 0; SkwRowRules* row_rules = nullptr;
     SkwSeqState* h_st = nullptr; SkwTokenOut* h_toks = nullptr; // pinned
     int* h_row_live = nullptr; int* d_row_live = nullptr;      // per-row live flags in pinned host memory and their device-side address: k_dec_sample clears a row's flag itself,
                                                                // so a step ends with no 4-byte copy kernel (4.2 us in the chain of every step) — the host reads the flags after the stream drains
@@ -603,6 +605,8 @@ extern "C" skw_ctx* skw_ctx_create(skw_model* m, int max_batch, int max_samples,
     want("probs", c->probs, (size_t)B * skw_probs_row_floats(hp.n_vocab), false);
     want("rng", c->rng, (size_t)B * SKW_RNG_WORDS, true);
     want("static_mask", c->static_mask, skw_static_mask_bytes(hp.n_vocab), true);
+    want("static_mask_pair", c->static_mask_pair, 2 * skw_static_mask_bytes(hp.n_vocab), true);
+    want("row_rules", c->row_rules, B, true);
     if (m->quant) {      // ggml q8 arithmetic (quantised files, exact precision): unrounded f32 activations and their q8 blocks
         want("y32", c->y32, enc_rows * d, false);
         want("h32", c->h32, enc_rows * 4 * d, false);
@@ -1031,11 +1035,12 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
 
 // One generation step of a row group as an executable graph: decoder step (positions and tokens read from the device state),
 // logit filters + sampling, and the read-back of the group's active count.  Captured once per (group, rows, filter params).
-static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogitParams& lp) {
+// rows: the per-row form of the sampler (skw_full_batch_mixed) — lp then holds model constants and any_sampled only, so one graph serves every parameter mix of its shape
+static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogitParams& lp, bool rows) {
     for (size_t i = 0; i < c->step_graphs.size(); ++i) {
         auto& sg = c->step_graphs[i];
         if (sg.g == g && sg.r0 == r0 && sg.n == n && sg.precision == c->precision && sg.ln_stats == c->ln_stats_on && sg.kclk == c->kclk_on && sg.sw_epoch == skw_sw_epoch() &&
-            memcmp(&sg.lp, &lp, sizeof lp) == 0) {
+            sg.rows == (int)rows && memcmp(&sg.lp, &lp, sizeof lp) == 0) {
             if (i + 1 != c->step_graphs.size()) { auto hit = sg; c->step_graphs.erase(c->step_graphs.begin() + i); c->step_graphs.push_back(hit); }   // most recently used last
             return c->step_graphs.back().exec;
         }
@@ -1045,7 +1050,9 @@ static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogi
     c->cur_group = g;
     run_decoder_step(c, r0, n, 0, true, s);
     c->cur_group = 0;
-    skw_dec_sample(c->logits + (size_t)r0 * NV, c->static_mask, lp, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->d_row_live + r0,
+    if (rows) skw_dec_sample_rows(c->logits + (size_t)r0 * NV, c->static_mask_pair, lp, c->row_rules + r0, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->d_row_live + r0,
+        c->probs + (size_t)r0 * skw_probs_row_floats(NV), c->rng, c->clip_idx + r0, c->prompt_buf + (size_t)r0 * SKW_PROMPT_CAP, s);
+    else skw_dec_sample(c->logits + (size_t)r0 * NV, c->static_mask, lp, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->d_row_live + r0,
         c->probs + (size_t)r0 * skw_probs_row_floats(NV), c->rng, c->clip_idx + r0, c->prompt_buf + (size_t)r0 * SKW_PROMPT_CAP, s);
     if (hipStreamEndCapture(s, &graph) != hipSuccess || !graph) return nullptr;
     if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
@@ -1054,20 +1061,34 @@ static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogi
         // bounded: a long-lived server with ragged batches would otherwise keep one executable graph per (group, rows, params) forever
         if (c->step_graphs.size() >= 24) { hipGraphExecDestroy(c->step_graphs.front().exec); c->step_graphs.erase(c->step_graphs.begin()); }
         skw_ctx::StepGraph sg; sg.g = g; sg.r0 = r0; sg.n = n; sg.precision = c->precision; sg.ln_stats = c->ln_stats_on; sg.kclk = c->kclk_on;
-         sg.sw_epoch = skw_sw_epoch(); sg.lp = lp; sg.exec = exec; c->step_graphs.push_back(sg);
+         sg.sw_epoch = skw_sw_epoch(); sg.lp = lp; sg.rows = (int)rows; sg.exec = exec; c->step_graphs.push_back(sg);
     }
     return exec;
 }
 
-static void build_static_mask(skw_ctx* c, const skw_full_params* p) {
-    if (c->static_mask_nst == (p->suppress_nst ? 1 : 0)) return;
-    skw_model* m = c->m; std::vector<uint8_t> mask(m->hp.n_vocab, 0);
+// the always-suppressed tokens (specials, languages, the non-speech list when asked for), packed for both sampler forms
+static std::vector<uint8_t> packed_static_mask(const skw_model* m, bool nst) {
+    std::vector<uint8_t> mask(m->hp.n_vocab, 0);
     mask[m->tok_not] = 1; mask[m->tok_sot] = 1; mask[m->tok_nosp] = 1; mask[m->tok_solm] = 1; mask[m->tok_translate] = 1; mask[m->tok_transcribe] = 1; mask[m->tok_prev] = 1;
     for (int i = 0; i < m->n_lang; ++i) mask[m->tok_sot + 1 + i] = 1;
-    if (p->suppress_nst) { for (int id : m->nst_ids) mask[id] = 1; if (m->tok_sp_dash >= 0) mask[m->tok_sp_dash] = 1; if (m->tok_sp_quote >= 0) mask[m->tok_sp_quote] = 1; }
+    if (nst) { for (int id : m->nst_ids) mask[id] = 1; if (m->tok_sp_dash >= 0) mask[m->tok_sp_dash] = 1; if (m->tok_sp_quote >= 0) mask[m->tok_sp_quote] = 1; }
     std::vector<uint8_t> packed(skw_static_mask_bytes(m->hp.n_vocab)); skw_static_mask_pack(mask.data(), m->hp.n_vocab, packed.data());
+    return packed;
+}
+static void build_static_mask(skw_ctx* c, const skw_full_params* p) {
+    if (c->static_mask_nst == (p->suppress_nst ? 1 : 0)) return;
+    const std::vector<uint8_t> packed = packed_static_mask(c->m, p->suppress_nst != 0);
     hipMemcpyAsync(c->static_mask, packed.data(), packed.size(), hipMemcpyHostToDevice, c->stream); hipStreamSynchronize(c->stream);
     c->static_mask_nst = p->suppress_nst ? 1 : 0;
+}
+// the per-row sampler's pair: [0] without, [1] with the non-speech list (a row picks by its own suppress_nst); written once per context
+static void build_static_mask_pair(skw_ctx* c) {
+    if (c->static_mask_pair_built) return;
+    for (int k = 0; k < 2; ++k) {
+        const std::vector<uint8_t> packed = packed_static_mask(c->m, k == 1);
+        hipMemcpyAsync(c->static_mask_pair + (size_t)k * packed.size(), packed.data(), packed.size(), hipMemcpyHostToDevice, c->stream); hipStreamSynchronize(c->stream);
+    }
+    c->static_mask_pair_built = 1;
 }
 
 // the sampler's view of the model's special tokens and of the whisper_full_params that shape whisper_process_logits
@@ -1083,6 +1104,17 @@ static SkwLogitParams make_logit_params(const skw_model* m, const skw_full_param
     if (p->max_initial_ts > 0.0f) { const float precision = (float)WHISPER_CHUNK_SIZE / hp.n_audio_ctx; lp.tid0_initial = (int)roundf(p->max_initial_ts / precision); }
     lp.n_max = hp.n_text_ctx / 2 - 4;
     return lp;
+}
+// the same six request fields as one row's record for the per-row sampler; mixed_logit_params: what is left in the launch's block (model constants)
+static SkwRowRules make_row_rules(const skw_model* m, const skw_full_params* p) {
+    const SkwLogitParams lp = make_logit_params(m, p);
+    SkwRowRules r{}; r.suppress_blank = lp.suppress_blank; r.suppress_nst = lp.suppress_nst; r.no_timestamps = lp.no_timestamps; r.single_segment = lp.single_segment;
+    r.max_tokens = lp.max_tokens; r.tid0_initial = lp.tid0_initial;
+    return r;
+}
+static SkwLogitParams mixed_logit_params(const skw_model* m) {
+    skw_full_params z{};      // (no request: the six fields stay 0 / -1 and the per-row form never reads them)
+    return make_logit_params(m, &z);
 }
 
 struct SeqAcc { std::vector<skw_segment> seg; std::vector<skw_token> tok; std::string text; };
@@ -1150,11 +1182,16 @@ static int move_retry_slots(skw_ctx* c, const std::vector<int>& old_slots) {
     return 0;
 }
 
+// pv: skw_full_batch_mixed — one skw_full_params per clip (p is then unused).  Everything a request decides is read through P(clip); the sampler takes the rows' rules from
+// device memory (skw_dec_sample_rows).  Without pv every P(clip) is *p and the launches are the uniform ones.
 static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device, skw_result* results,
-                           const int32_t* const* forced_ids, const int32_t* n_forced, std::vector<std::vector<SkwTraceStep>>* traces, uint32_t* const* rng_state = nullptr) {
+                           const int32_t* const* forced_ids, const int32_t* n_forced, std::vector<std::vector<SkwTraceStep>>* traces, uint32_t* const* rng_state = nullptr,
+                           const skw_full_params* pv = nullptr) {
     char* errbuf = c->errbuf; errbuf[0] = 0;
     WS_READY(c);
     if (n_clips < 1 || n_clips > c->max_batch) { snprintf(errbuf, 512, "n_clips %d outside [1, %d]", n_clips, c->max_batch); return -1; }
+    const bool mixed = pv != nullptr;
+    auto P = [&](int ci) -> const skw_full_params& { return mixed ? pv[ci] : *p; };
     HIPCHK(hipSetDevice(c->m->device));
     const bool tracing = traces != nullptr;
     std::vector<int> f_cursor(n_clips, 0);      // tracing: decisions of clip i made so far (= its position in forced_ids[i])
@@ -1170,15 +1207,18 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
     if (c->kclk_on && kclk_reset(c)) return -1;
     HIPCHK(hipEventRecord(c->ev[0], c->stream));
     if (load_clips(c, pcm, n_samples, n_clips, pcm_on_device, n_len, n_len_org)) return -1;
-    build_static_mask(c, p);
+    if (mixed) build_static_mask_pair(c); else build_static_mask(c, p);
     run_mel(c, n_clips);
     HIPCHK(hipEventRecord(c->ev[1], c->stream));
     float enc_ms = 0.f, dec_ms = 0.f; int tot_windows = 0, tot_steps = 0, tot_tokens = 0; long tot_row_steps = 0; int used_groups = 1, used_group_rows = 0;
 
     std::vector<int> seek(n_clips, 0); std::vector<SeqAcc> acc(n_clips);
     // temperature ladder (whisper_full_with_state): per clip, the index of the temperature its current window is decoded at
-    std::vector<float> temps; temps.push_back(p->temperature);
-    if (p->temperature_inc > 0.0f) for (float t = p->temperature + p->temperature_inc; t < 1.0f + 1e-6f && temps.size() < 16; t += p->temperature_inc) temps.push_back(t);
+    std::vector<std::vector<float>> temps(n_clips);      // (a clip's own ladder: temperature and temperature_inc are the request's)
+    for (int ci = 0; ci < n_clips; ++ci) {
+        std::vector<float>& tl = temps[ci]; const skw_full_params& q = P(ci); tl.push_back(q.temperature);
+        if (q.temperature_inc > 0.0f) for (float t = q.temperature + q.temperature_inc; t < 1.0f + 1e-6f && tl.size() < 16; t += q.temperature_inc) tl.push_back(t);
+    }
     std::vector<int> tidx(n_clips, 0), retry_slot(n_clips, -1);   // retry_slot: the window slot whose cross K/V a retrying clip left behind (-1: not retrying)
     // prompt_past (whisper_full_with_state): text already produced in this call conditions the next window of the same clip
     std::vector<std::vector<int>> prompt_past(n_clips); std::vector<int> last_take(n_clips, 0);
@@ -1191,10 +1231,13 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
         HIPCHK(hipMemcpyAsync(c->rng + (size_t)i * SKW_RNG_WORDS, rng_state[i], sizeof(uint32_t) * SKW_RNG_WORDS, hipMemcpyHostToDevice, c->stream));
     }
     // language: fixed by the caller, or (lang_id < 0, whisper.cpp's "auto") detected per clip from the [sot] step on the first window
-    std::vector<int> lang(n_clips, p->lang_id);
-    if (p->lang_id < 0) {
-        if (NV < 51865) { snprintf(errbuf, 512, "failed to auto-detect language: the model is not multilingual"); return -3; }
-        std::vector<int> act, zero(n_clips, 0); for (int i = 0; i < n_clips; ++i) if (n_len_org[i] > 0) act.push_back(i);
+    std::vector<int> lang(n_clips); bool any_auto = false;
+    for (int i = 0; i < n_clips; ++i) { lang[i] = P(i).lang_id; results[i].lang_id = lang[i]; if (lang[i] < 0 && !any_auto) { any_auto = true;
+        if (NV < 51865) { if (mixed) snprintf(errbuf, 512, "failed to auto-detect language: the model is not multilingual (clip %d)", i);
+                          else snprintf(errbuf, 512, "failed to auto-detect language: the model is not multilingual");
+                          return -3; } } }
+    if (any_auto) {      // the detection pass runs on the rows that asked for it
+        std::vector<int> act, zero(n_clips, 0); for (int i = 0; i < n_clips; ++i) if (lang[i] < 0 && n_len_org[i] > 0) act.push_back(i);
         const int Bd = (int)act.size();
         if (Bd > 0) {
             HIPCHK(hipMemcpyAsync(c->clip_idx, act.data(), sizeof(int) * Bd, hipMemcpyHostToDevice, c->stream));
@@ -1206,13 +1249,17 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
             std::vector<int> det(Bd); HIPCHK(hipMemcpyAsync(det.data(), c->row_tok, sizeof(int) * Bd, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
             for (int j = 0; j < Bd; ++j) { lang[act[j]] = det[j]; results[act[j]].lang_id = det[j]; }
         }
-        for (int i = 0; i < n_clips; ++i) if (lang[i] < 0) lang[i] = 0;
-    } else for (int i = 0; i < n_clips; ++i) results[i].lang_id = p->lang_id;
-    int32_t prompt[8]; int n_prompt = 0;
-    prompt[n_prompt++] = m->tok_sot;
-    if (NV >= 51865) { prompt[n_prompt++] = -1 /* per row: sot + 1 + lang[clip] */; prompt[n_prompt++] = p->translate ? m->tok_translate : m->tok_transcribe; }
-    if (p->no_timestamps) prompt[n_prompt++] = m->tok_not;
-    SkwLogitParams lp = make_logit_params(m, p);
+        for (int i = 0; i < n_clips; ++i) if (lang[i] < 0) { lang[i] = 0; results[i].lang_id = 0; }
+    }
+    // sot, language, task (, notimestamps): the tail of a row's prompt, from its clip's request
+    auto prompt_tail = [&](int ci, int32_t* out) {
+        const skw_full_params& q = P(ci); int n = 0;
+        out[n++] = m->tok_sot;
+        if (NV >= 51865) { out[n++] = m->tok_sot + 1 + lang[ci]; out[n++] = q.translate ? m->tok_translate : m->tok_transcribe; }
+        if (q.no_timestamps) out[n++] = m->tok_not;
+        return n;
+    };
+    SkwLogitParams lp = mixed ? mixed_logit_params(m) : make_logit_params(m, p);
 
     while (true) {
         // clips that still have audio to decode ("if only 100ms left, then stop"; "input is too short": delta_min = 10 frames, whisper.cpp #2065)
@@ -1233,17 +1280,23 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
         std::vector<int> pbuf((size_t)Bw * SKW_PROMPT_CAP, 0), np_row(Bw, 0);
         for (int j = 0; j < Bw; ++j) {
             const int ci = act[j]; int* pr = pbuf.data() + (size_t)j * SKW_PROMPT_CAP; int n = 0, take = 0;
-            if (!prompt_past[ci].empty() && temps[tidx[ci]] < 0.5f) {
+            int32_t prompt[8]; const int n_prompt = prompt_tail(ci, prompt);
+            if (!prompt_past[ci].empty() && temps[ci][tidx[ci]] < 0.5f) {
                 // the last bound only binds with no_timestamps: every position stays inside n_text_ctx
                 take = std::min(std::min(hp.n_text_ctx / 2, (int)prompt_past[ci].size()), hp.n_text_ctx - lp.n_max - n_prompt - 1);
                 pr[n++] = m->tok_prev; for (int i = 0; i < take; ++i) pr[n++] = prompt_past[ci][prompt_past[ci].size() - take + i];
             }
             last_take[ci] = take;
-            for (int t = 0; t < n_prompt; ++t) pr[n++] = prompt[t] >= 0 ? prompt[t] : m->tok_sot + 1 + lang[ci];
+            for (int t = 0; t < n_prompt; ++t) pr[n++] = prompt[t];
             np_row[j] = n;
         }
         HIPCHK(hipMemcpyAsync(c->prompt_buf, pbuf.data(), sizeof(int) * pbuf.size(), hipMemcpyHostToDevice, c->stream));
-        lp.any_sampled = 0; for (int j = 0; j < Bw; ++j) if (temps[tidx[act[j]]] > 0.0f) lp.any_sampled = 1;      // (part of the step graph's key: greedy passes run the lean sampler)
+        std::vector<SkwRowRules> rules;      // (alive until the stream is synchronised at the end of the window)
+        if (mixed) {
+            rules.resize(Bw); for (int j = 0; j < Bw; ++j) rules[j] = make_row_rules(m, &P(act[j]));
+            HIPCHK(hipMemcpyAsync(c->row_rules, rules.data(), sizeof(SkwRowRules) * Bw, hipMemcpyHostToDevice, c->stream));
+        }
+        lp.any_sampled = 0; for (int j = 0; j < Bw; ++j) if (temps[act[j]][tidx[act[j]]] > 0.0f) lp.any_sampled = 1;      // (part of the step graph's key: greedy passes run the lean sampler)
         std::vector<int> fbuf;
         if (tracing) {      // this pass's forced tokens per row: the clip's sequence from its cursor on (-1 = none: the row feeds its own choices)
             fbuf.assign((size_t)Bw * c->max_tok, -1);
@@ -1259,7 +1312,7 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
             SkwSeqState& s = c->h_st[j]; memset(&s, 0, sizeof s);
             s.active = 1; s.seek_delta = 100 * WHISPER_CHUNK_SIZE; s.seek = sk[j];
             s.seek_end = n_len_org[act[j]]; s.n_prompt = np_row[j]; s.min_margin = INFINITY; s.cur_token = pbuf[(size_t)j * SKW_PROMPT_CAP]; s.cur_pos = 0;
-            s.temperature = temps[tidx[act[j]]];
+            s.temperature = temps[act[j]][tidx[act[j]]];
         }
         // The prompt in one pass (whisper.cpp evaluates it in one whisper_decode call): every prompt token but a row's last becomes a row of ONE decoder pass —
         // the step's own kernels, a row per (sequence, position), the caches addressed through the row's sequence — which fills the self-attention K / V
@@ -1327,10 +1380,14 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
         // every step = decoder step (token and position from the device state) + k_dec_sample, which feeds the next prompt token
         // while a row is still inside its prompt and samples afterwards; rows have prompts of different lengths
         hipGraphExec_t gexec[skw_ctx::MAX_GROUPS] = {};
-        if (use_graphs && !profiling && !tracing) for (int g = 0; g < G; ++g) gexec[g] = step_graph(c, g, g_r0[g], g_n[g], lp);   // nullptr -> eager launches
+        if (use_graphs && !profiling && !tracing) for (int g = 0; g < G; ++g) gexec[g] = step_graph(c, g, g_r0[g], g_n[g], lp, mixed);   // nullptr -> eager launches
         auto sample = [&](int g) {
             c->cur = c->gstream[g];
-            { ProfScope p_(c, PC_DEC_SAMPLE, 0, 4.0 * g_n[g] * NV); skw_dec_sample(c->logits + (size_t)g_r0[g] * NV, c->static_mask, lp, c->st + g_r0[g],
+            { ProfScope p_(c, PC_DEC_SAMPLE, 0, 4.0 * g_n[g] * NV);
+              if (mixed) skw_dec_sample_rows(c->logits + (size_t)g_r0[g] * NV, c->static_mask_pair, lp, c->row_rules + g_r0[g], c->st + g_r0[g],
+                c->toks + (size_t)g_r0[g] * c->max_tok, c->max_tok, g_n[g], c->d_row_live + g_r0[g], c->probs + (size_t)g_r0[g] * skw_probs_row_floats(NV), c->rng,
+                c->clip_idx + g_r0[g], c->prompt_buf + (size_t)g_r0[g] * SKW_PROMPT_CAP, c->gstream[g]);
+              else skw_dec_sample(c->logits + (size_t)g_r0[g] * NV, c->static_mask, lp, c->st + g_r0[g],
                 c->toks + (size_t)g_r0[g] * c->max_tok, c->max_tok, g_n[g], c->d_row_live + g_r0[g], c->probs + (size_t)g_r0[g] * skw_probs_row_floats(NV), c->rng,
                 c->clip_idx + g_r0[g], c->prompt_buf + (size_t)g_r0[g] * SKW_PROMPT_CAP, c->gstream[g],
                                                                                      tracing ? c->forced_dev + (size_t)g_r0[g] * c->max_tok : nullptr,
@@ -1387,6 +1444,7 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
         // per-clip: ranking, segment assembly, seek update (whisper_full_with_state tail)
         for (int j = 0; j < Bw; ++j) {
             const int ci = act[j]; const SkwSeqState& s = c->h_st[j]; const SkwTokenOut* tk = c->h_toks + (size_t)j * c->max_tok; skw_result& R = results[ci]; SeqAcc& A = acc[ci];
+            const skw_full_params* p = &P(ci);      // the clip's own request from here on
             if (tidx[ci] == 0) R.n_windows++;
             R.n_decode_steps += 1 + std::max(0, s.n_tokens - 1);     // the prompt is one decode call in whisper.cpp, then one per sampled token but the last
             bool failed = s.failed != 0; int n_tok = s.n_tokens; const int result_len = s.result_len;
@@ -1395,7 +1453,7 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
             if (s.min_margin < R.min_margin) R.min_margin = s.min_margin;
             if (failed || (avg_logprobs < p->logprob_thold && s.no_speech_prob < p->no_speech_thold)) {
                 R.fallback_requested++;
-                if (tidx[ci] + 1 < (int)temps.size()) { tidx[ci]++; retry_slot[ci] = j; continue; }   // this window again, at the next temperature, on the cross K/V it already has (slot j)
+                if (tidx[ci] + 1 < (int)temps[ci].size()) { tidx[ci]++; retry_slot[ci] = j; continue; }   // this window again, at the next temperature, on the cross K/V it already has (slot j)
             }
             tidx[ci] = 0;
             int seek_delta = s.seek_delta;
@@ -1462,6 +1520,13 @@ extern "C" int skw_full_batch_rng(skw_ctx* c, const skw_full_params* p, const fl
     try { return full_batch_impl(c, p, pcm, n_samples, n_clips, pcm_on_device, results, nullptr, nullptr, nullptr, rng_state); }
     catch (const std::exception& e) { snprintf(c->errbuf, 512, "skw_full_batch_rng: %s", e.what()); return -5; }
 }
+extern "C" int skw_full_batch_mixed(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                                    uint32_t* const* rng_state, skw_result* results) {
+    try {
+        if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_mixed: params is NULL (one skw_full_params per clip)"); return -1; }
+        return full_batch_impl(c, params, pcm, n_samples, n_clips, pcm_on_device, results, nullptr, nullptr, nullptr, rng_state, params);
+    } catch (const std::exception& e) { snprintf(c->errbuf, 512, "skw_full_batch_mixed: %s", e.what()); return -5; }
+}
 extern "C" int skw_full_batch_traced(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                      const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, skw_result* results) {
     static_assert(sizeof(skw_trace_step) == sizeof(SkwTraceStep), "skw_trace_step is SkwTraceStep");
@@ -1482,8 +1547,9 @@ extern "C" int skw_full_batch_traced(skw_ctx* c, const skw_full_params* p, const
 // caller-supplied logits; ONE launch of the sampler (form 0: the one the decode step uses; form 1: the streaming kernel, which leaves the filtered row in
 // memory) makes each row's next decision.  has_ts / seek_delta / result_len are replayed from the history by the token loop's update rule, as
 // oracle/skwo_debug_process_logits does.  Outputs per row: the decision (skw_token), its trace record, and (form 1, optional) the filtered logits.
-extern "C" int skw_debug_sample_rows(skw_ctx* c, const skw_full_params* p, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist, const float* logits_host, int form,
-                                     float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out) {
+// pv (skw_debug_sample_rows_mixed): one skw_full_params per row — the launch is the per-row form of the sampler, each row under its own rules and its own static mask.
+static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const skw_full_params* pv, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
+                                  const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out) {
     char* errbuf = c->errbuf; errbuf[0] = 0;
     WS_READY(c);
     if (n_rows < 1 || n_rows > c->max_batch) { snprintf(errbuf, 512, "n_rows %d outside [1, %d]", n_rows, c->max_batch); return -1; }
@@ -1497,8 +1563,13 @@ extern "C" int skw_debug_sample_rows(skw_ctx* c, const skw_full_params* p, int n
             hipFree(f); snprintf(errbuf, 512, "trace buffers: device allocation failed"); return -1; }
         c->forced_dev = f; c->trace_dev = t;
     }
-    build_static_mask(c, p);
-    SkwLogitParams lp = make_logit_params(m, p); lp.any_sampled = 0;
+    SkwLogitParams lp; std::vector<SkwRowRules> rules;
+    if (pv) {
+        build_static_mask_pair(c); lp = mixed_logit_params(m);
+        rules.resize(n_rows); for (int r = 0; r < n_rows; ++r) rules[r] = make_row_rules(m, &pv[r]);
+        HIPCHK(hipMemcpyAsync(c->row_rules, rules.data(), sizeof(SkwRowRules) * n_rows, hipMemcpyHostToDevice, c->stream));
+    } else { build_static_mask(c, p); lp = make_logit_params(m, p); }
+    lp.any_sampled = 0;
     std::vector<SkwTokenOut> toks((size_t)n_rows * MT); memset(toks.data(), 0, toks.size() * sizeof(SkwTokenOut));
     std::vector<int> forced((size_t)n_rows * MT, -1), zero(n_rows, 0);
     for (int r = 0; r < n_rows; ++r) {
@@ -1522,7 +1593,9 @@ extern "C" int skw_debug_sample_rows(skw_ctx* c, const skw_full_params* p, int n
     HIPCHK(hipMemcpyAsync(c->clip_idx, zero.data(), sizeof(int) * n_rows, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->logits, logits_host, sizeof(float) * (size_t)n_rows * NV, hipMemcpyHostToDevice, c->stream));
     skw_debug_force_stream_sampler(form == 1);
-    skw_dec_sample(c->logits, c->static_mask, lp, c->st, c->toks, MT, n_rows, c->d_row_live, c->probs, c->rng, c->clip_idx, c->prompt_buf, c->stream, c->forced_dev, c->trace_dev);
+    if (pv) skw_dec_sample_rows(c->logits, c->static_mask_pair, lp, c->row_rules, c->st, c->toks, MT, n_rows, c->d_row_live, c->probs, c->rng, c->clip_idx, c->prompt_buf, c->stream,
+                                c->forced_dev, c->trace_dev);
+    else skw_dec_sample(c->logits, c->static_mask, lp, c->st, c->toks, MT, n_rows, c->d_row_live, c->probs, c->rng, c->clip_idx, c->prompt_buf, c->stream, c->forced_dev, c->trace_dev);
     skw_debug_force_stream_sampler(0);
     HIPCHK(hipGetLastError());
     std::vector<SkwTraceStep> tr((size_t)n_rows * MT);
@@ -1536,6 +1609,15 @@ extern "C" int skw_debug_sample_rows(skw_ctx* c, const skw_full_params* p, int n
         if (trace_out) memcpy(&trace_out[r], &tr[(size_t)r * MT + n_hist[r]], sizeof(skw_trace_step));
     }
     return 0;
+}
+extern "C" int skw_debug_sample_rows(skw_ctx* c, const skw_full_params* p, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist, const float* logits_host, int form,
+                                     float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out) {
+    return debug_sample_rows_impl(c, p, nullptr, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out);
+}
+extern "C" int skw_debug_sample_rows_mixed(skw_ctx* c, const skw_full_params* params /* [n_rows] */, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
+                                           const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out) {
+    if (!params) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_mixed: params is NULL (one skw_full_params per row)"); return -1; }
+    return debug_sample_rows_impl(c, params, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out);
 }
 extern "C" void skw_trace_free(skw_trace* t) { if (!t) return; free(t->steps); t->steps = nullptr; t->n = 0; }
 extern "C" void skw_result_free(skw_result* r) { if (!r) return; free(r->segments); free(r->tokens); free(r->text); memset(r, 0, sizeof *r); }

@@ -194,6 +194,12 @@ struct SkwLogitParams {
     int n_max;          // n_text_ctx/2 - 4
     int any_sampled;    // some row of this pass decodes at a temperature > 0 (host knowledge: the ladder's position per clip): the sampler's draw form (64 KB of LDS staging) is launched only then
 };
+// The request's rules of one row (skw_full_batch_mixed: the rows of a launch decode under different skw_full_params): the six fields of SkwLogitParams that come from
+// skw_full_params, in device memory, written by the host per window like prompt_buf.  suppress_nst also selects the row's static mask of the pair.
+struct SkwRowRules { int32_t suppress_blank, suppress_nst, no_timestamps, single_segment, max_tokens, tid0_initial, pad[2]; };
+// SkwLogitParams = 15 model constants + any_sampled (per pass) + the 6 request fields above.  A field added to it must be put on one side: a request field that is not also in
+// SkwRowRules (and copied by smp_row_rules, skw_kernels.hip) would be baked into the step graphs of mixed calls as a constant.  These two sizes make such an addition stop here.
+static_assert(sizeof(SkwLogitParams) == (15 + 1 + 6) * sizeof(int) && sizeof(SkwRowRules) == (6 + 2) * sizeof(int32_t), "classify the new field: model constant or per-row request rule");
 // whisper_process_logits + whisper_sample_token(best) + the per-token state update of whisper_full_with_state.
 // logits: [B][n_vocab] (modified in place), static_mask: [n_vocab] bytes (1 = always suppressed: specials, langs, nst list when enabled)
 // static_mask buffer = n_vocab bytes (1 = always suppressed), padded to 16, followed by the same bits transposed for the sampling
@@ -207,6 +213,10 @@ void skw_static_mask_pack(const uint8_t* mask, int n_vocab, uint8_t* out);
 void skw_dec_sample(float* logits, const uint8_t* static_mask, SkwLogitParams p, SkwSeqState* st, SkwTokenOut* toks /*[B][max_tokens]*/, int max_tok, int B, int* n_active,
                     float* probs, uint32_t* rng, const int* clip_idx, const int* prompt_buf /* [B][SKW_PROMPT_CAP]: row b feeds prompt_buf[b][0 .. n_prompt) before it samples */, hipStream_t s,
                     const int* forced = nullptr /* [B][max_tok]: token to feed after decision i instead of the chosen one (< 0: the chosen one) */, SkwTraceStep* trace = nullptr /* [B][max_tok] */);
+// the per-row form: static_mask_pair = two packed masks back to back, [0] without and [1] with the non-speech list; rules: [B]; the six request fields of p are ignored
+// (callers leave them zero, so a captured step graph holds no request's values and replays for any parameter mix)
+void skw_dec_sample_rows(float* logits, const uint8_t* static_mask_pair, SkwLogitParams p, const SkwRowRules* rules, SkwSeqState* st, SkwTokenOut* toks, int max_tok, int B, int* n_active,
+                         float* probs, uint32_t* rng, const int* clip_idx, const int* prompt_buf, hipStream_t s, const int* forced = nullptr, SkwTraceStep* trace = nullptr);
 void skw_debug_force_stream_sampler(int on);   // tests: the streaming sampler (filters the logits row in place) even where the register-resident form applies
 void skw_rng_seed(uint32_t* rng, int n_clips, uint32_t seed, hipStream_t s);   // std::mt19937(seed) for every clip
 

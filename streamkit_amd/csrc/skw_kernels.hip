@@ -1424,9 +1424,20 @@ __device__ int block_discrete_draw(const float* probs, double* q, int n, uint32_
     return h >= 0 ? h : n - 1;
 }
 
+// one packed static mask: n_vocab bytes padded to 16, then the transposed bits (two 64-bit words per thread of the register-resident sampler; SMP_NT below)
+__host__ __device__ inline size_t smp_mask_bytes(int n_vocab) { return (size_t)((n_vocab + 15) & ~15) + 2 * 512 * sizeof(unsigned long long); }
+// a row's own rules into the launch's parameter block; returns the row's mask of the pair [without | with the non-speech list]
+__device__ __forceinline__ const uint8_t* smp_row_rules(SkwLogitParams& p, const SkwRowRules& r, const uint8_t* mask_pair) {
+    p.suppress_blank = r.suppress_blank; p.suppress_nst = r.suppress_nst; p.no_timestamps = r.no_timestamps; p.single_segment = r.single_segment;
+    p.max_tokens = r.max_tokens; p.tid0_initial = r.tid0_initial;
+    return mask_pair + (r.suppress_nst ? smp_mask_bytes(p.n_vocab) : 0);
+}
+// ROWS (both sampler forms): the request's rules come from rules[row] in device memory instead of the by-value p, and the row picks its static mask out of the
+//  pair (skw_full_batch_mixed: rows of one launch decode under different skw_full_params); p then carries the model constants only
+template <bool ROWS>
 __global__ __launch_bounds__(1024) void k_dec_sample_stream(float* logits_all, const uint8_t* static_mask, SkwLogitParams p, SkwSeqState* st_all, SkwTokenOut* toks_all,
                                                      int max_tok, int* n_active, float* probs_all, uint32_t* rng_all, const int* clip_idx, const int* prompt_buf,
-                                                     const int* forced, SkwTraceStep* trace) {
+                                                     const int* forced, SkwTraceStep* trace, const SkwRowRules* rules) {
     __shared__ float sh_f[16]; __shared__ double sh_d[16]; __shared__ ArgBest sh_a[16];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     SkwSeqState* st = &st_all[b];
@@ -1437,6 +1448,7 @@ __global__ __launch_bounds__(1024) void k_dec_sample_stream(float* logits_all, c
     }
     float* lg = logits_all + (long)b * p.n_vocab;
     const int NV = p.n_vocab;
+    if constexpr (ROWS) static_mask = smp_row_rules(p, rules[b], static_mask);
     SkwTokenOut* toks = toks_all + (long)b * max_tok;
     const int n_tok = st->n_tokens;
     const bool is_initial = n_tok == 0;
@@ -1552,10 +1564,10 @@ struct SmpMain { ArgBest best; float best_logit; ArgBest bts; double sum_ts; flo
 #define SMP_IDX(c) (tq + SMP_NT * (c))
 // TRACE: the trace / teacher-forced form (one more pass for the runner-up's index); DRAW: rows at a temperature > 0 may be present (the workgroup-wide draw and its LDS
 //  staging are compiled in); the greedy step's graph holds <false, false>
-template <bool TRACE, bool DRAW>
+template <bool TRACE, bool DRAW, bool ROWS>
 __global__ __launch_bounds__(SMP_NT) void k_dec_sample(float* logits_all, const uint8_t* static_mask, SkwLogitParams p, SkwSeqState* st_all, SkwTokenOut* toks_all,
                                                        int max_tok, int* n_active, float* probs_all, uint32_t* rng_all, const int* clip_idx, const int* prompt_buf,
-                                                       const int* forced, SkwTraceStep* trace) {
+                                                       const int* forced, SkwTraceStep* trace, const SkwRowRules* rules) {
     __shared__ float sh_f[2][SMP_NT / 64]; __shared__ double sh_d[SMP_NT / 64]; __shared__ SmpMain sh_m[SMP_NT / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     SkwSeqState* st = &st_all[b];
@@ -1566,6 +1578,7 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_sample(float* logits_all, const 
     }
     float* lg = logits_all + (long)b * p.n_vocab;
     const int NV = p.n_vocab;
+    if constexpr (ROWS) static_mask = smp_row_rules(p, rules[b], static_mask);
     SkwTokenOut* toks = toks_all + (long)b * max_tok;
     const int n_tok = st->n_tokens;
     const bool is_initial = n_tok == 0;
@@ -1798,7 +1811,8 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_sample(float* logits_all, const 
     st->cur_token = tk.id; st->cur_pos = st->n_prompt + i;
     if (failed || completed) { st->active = 0; n_active[b] = 0; }     // the row's live flag, in host-mapped memory: the host reads it after the stream drains (no copy kernel in the step)
 }
-size_t skw_static_mask_bytes(int n_vocab) { return (size_t)((n_vocab + 15) & ~15) + 2 * SMP_NT * sizeof(unsigned long long); }
+static_assert(SMP_NT == 512, "smp_mask_bytes restates SMP_NT");
+size_t skw_static_mask_bytes(int n_vocab) { return smp_mask_bytes(n_vocab); }
 void skw_static_mask_pack(const uint8_t* mask, int n_vocab, uint8_t* out) {
     memset(out, 0, skw_static_mask_bytes(n_vocab)); memcpy(out, mask, n_vocab);
     unsigned long long* kw = (unsigned long long*)(out + ((n_vocab + 15) & ~15));
@@ -1806,14 +1820,25 @@ void skw_static_mask_pack(const uint8_t* mask, int n_vocab, uint8_t* out) {
 }
 static int g_force_stream_sampler = 0;      // tests: run the streaming form where the register-resident one would (it leaves the filtered row in memory)
 void skw_debug_force_stream_sampler(int on) { g_force_stream_sampler = on; }
+template <bool ROWS>
+static void dec_sample_launch(float* logits, const uint8_t* static_mask, const SkwLogitParams& p, SkwSeqState* st, SkwTokenOut* toks, int max_tok, int B, int* n_active,
+                              float* probs, uint32_t* rng, const int* clip_idx, const int* prompt_buf, hipStream_t s, const int* forced, SkwTraceStep* trace, const SkwRowRules* rules) {
+    if (!g_force_stream_sampler && p.n_vocab <= SMP_PT * SMP_NT && std::min(p.tok_eot, p.tok_beg) >= SMP_TX * SMP_NT) {
+        if (trace) hipLaunchKernelGGL((k_dec_sample<true, true, ROWS>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng, clip_idx, prompt_buf,
+            forced, trace, rules);
+        else if (p.any_sampled) hipLaunchKernelGGL((k_dec_sample<false, true, ROWS>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs,
+            rng, clip_idx, prompt_buf, nullptr, nullptr, rules);
+        else hipLaunchKernelGGL((k_dec_sample<false, false, ROWS>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng, clip_idx, prompt_buf,
+            nullptr, nullptr, rules);
+    } else hipLaunchKernelGGL(k_dec_sample_stream<ROWS>, dim3(B), dim3(1024), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng, clip_idx, prompt_buf, forced, trace, rules);
+}
 void skw_dec_sample(float* logits, const uint8_t* static_mask, SkwLogitParams p, SkwSeqState* st, SkwTokenOut* toks, int max_tok, int B, int* n_active,
                     float* probs, uint32_t* rng, const int* clip_idx, const int* prompt_buf, hipStream_t s, const int* forced, SkwTraceStep* trace) {
-    if (!g_force_stream_sampler && p.n_vocab <= SMP_PT * SMP_NT && std::min(p.tok_eot, p.tok_beg) >= SMP_TX * SMP_NT) {
-        if (trace) hipLaunchKernelGGL((k_dec_sample<true, true>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng, clip_idx, prompt_buf, forced, trace);
-        else if (p.any_sampled) hipLaunchKernelGGL((k_dec_sample<false, true>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs,
-            rng, clip_idx, prompt_buf, nullptr, nullptr);
-        else hipLaunchKernelGGL((k_dec_sample<false, false>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng, clip_idx, prompt_buf, nullptr, nullptr);
-    } else hipLaunchKernelGGL(k_dec_sample_stream, dim3(B), dim3(1024), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng, clip_idx, prompt_buf, forced, trace);
+    dec_sample_launch<false>(logits, static_mask, p, st, toks, max_tok, B, n_active, probs, rng, clip_idx, prompt_buf, s, forced, trace, nullptr);
+}
+void skw_dec_sample_rows(float* logits, const uint8_t* static_mask_pair, SkwLogitParams p, const SkwRowRules* rules, SkwSeqState* st, SkwTokenOut* toks, int max_tok, int B, int* n_active,
+                         float* probs, uint32_t* rng, const int* clip_idx, const int* prompt_buf, hipStream_t s, const int* forced, SkwTraceStep* trace) {
+    dec_sample_launch<true>(logits, static_mask_pair, p, st, toks, max_tok, B, n_active, probs, rng, clip_idx, prompt_buf, s, forced, trace, rules);
 }
 
 // ------------------------------------------------------------------ R1: audio::resampler arithmetic (rubato FastFixedIn, Linear)

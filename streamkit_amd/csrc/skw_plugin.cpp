@@ -5,7 +5,7 @@
 // ABI: include/streamkit_native_abi.h.
 //
 // Params beyond the reference's are ADDITIVE (unknown keys are ignored by the reference's serde config, lib.rs:66-104):
-// vad_mode, batch_window_ms, max_batch, flush_tail, precision, gpu_device: "auto", and input_sample_rate / input_resample_mode (the
+// vad_mode, batch_window_ms, max_batch, mixed_batch, flush_tail, precision, gpu_device: "auto", and input_sample_rate / input_resample_mode (the
 // audio::resampler node's arithmetic run inside this plugin, skw_resampler_core.h: a 48 kHz Opus source then needs no node in between).
 // One BEHAVIOURAL difference remains and is not additive: with the default vad_mode "auto" the Silero model at `vad_model_path`
 // gates what Whisper sees exactly as in the reference (skw_silero.h) only when that file exists; when it does not, the
@@ -70,6 +70,7 @@ struct WhisperConfig {
     // additive
     std::string vad_mode = "auto";   // auto | silero | energy | always
     int batch_window_ms = 2; int max_batch = 64; bool flush_tail = false;
+    bool mixed_batch = true;         // segments of differently configured instances share a GPU batch (skw_full_batch_mixed); false: a batch is cut at the first job whose parameters differ
     std::string precision = "exact"; // exact | f16_mfma  (include/skw_engine.h, SKW_PRECISION_*)
     uint32_t input_sample_rate = 16000; std::string input_resample_mode = "linear";   // linear (the audio::resampler node's rubato arithmetic, bit for bit) | polyphase
 };
@@ -114,7 +115,7 @@ bool parse_config(const char* json, WhisperConfig* cfg, std::string* err) {
     d = cfg->batch_window_ms; if (!num("batch_window_ms", &d)) return false; cfg->batch_window_ms = (int)d;
     d = cfg->max_batch; if (!num("max_batch", &d)) return false; cfg->max_batch = std::max(1, (int)d);
     if (!boo("use_gpu", &cfg->use_gpu) || !boo("suppress_blank", &cfg->suppress_blank) || !boo("suppress_non_speech_tokens", &cfg->suppress_non_speech_tokens) ||
-        !boo("emit_vad_events", &cfg->emit_vad_events) || !boo("flush_tail", &cfg->flush_tail)) return false;
+        !boo("emit_vad_events", &cfg->emit_vad_events) || !boo("flush_tail", &cfg->flush_tail) || !boo("mixed_batch", &cfg->mixed_batch)) return false;
     return true;
 }
 
@@ -152,6 +153,7 @@ struct Job {
     const float* data() const { return pinned.p ? pinned.p : pcm_pageable.data(); }
     ~Job() { PinnedPool::get().release(pinned); }
 };
+std::atomic<long> g_engine_calls{0}, g_batch_jobs{0}, g_mixed_calls{0};      // skw_whisper_plugin_batch_stats
 struct SharedEngine {
     skw_model* model = nullptr;
     skw_ctx* ctx = nullptr;
@@ -159,6 +161,8 @@ struct SharedEngine {
     int max_samples = 0;        // samples per row the workspace was created for
     int batch_limit = 64;       // scheduler: largest batch formed (the max_batch param of the instance created most recently; under mu)
     int window_ms = 2;          // scheduler: how long a batch waits for more jobs (batch_window_ms of the instance created most recently; under mu)
+    bool multilingual = true;   // the model has language tokens (n_vocab >= 51865); set once at load
+    bool mixed = true;          // scheduler: jobs join a batch whatever their parameters (mixed_batch of the instance created most recently; under mu)
     int precision = SKW_PRECISION_EXACT;
     static const int kMaxSamples = 16000 * 121;   // schema maximum of max_segment_duration_secs (120 s) + one VAD frame of slack: no segment is longer
     static int samples_for(float max_segment_secs) { const double s = std::min(120.0, std::max(1.0, (double)max_segment_secs)); return std::min(kMaxSamples, (int)std::ceil(s * 16000.0) + 1024); }
@@ -215,8 +219,8 @@ struct SharedEngine {
                 auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(window_ms);
                 while ((int)queue.size() < batch_limit && !stop) { if (cv.wait_until(l, deadline) == std::cv_status::timeout) break; }
                 while (!queue.empty() && (int)batch.size() < batch_limit) {
-                    // one skw_full_batch call shares its params: group by the params of the first job
-                    if (!batch.empty() && memcmp(&batch[0]->params, &queue.front()->params, sizeof(skw_full_params)) != 0) break;
+                    // arrival order, whatever the jobs' params: every row of skw_full_batch_mixed decodes under its own.  mixed_batch: false cuts at the first job that differs
+                    if (!mixed && !batch.empty() && memcmp(&batch[0]->params, &queue.front()->params, sizeof(skw_full_params)) != 0) break;
                     batch.push_back(queue.front()); queue.pop_front();
                 }
             }
@@ -228,8 +232,27 @@ struct SharedEngine {
                 std::lock_guard<std::mutex> wl(ws_mu);
                 if (ensure_workspace(need, n, &why)) {
                     std::vector<uint32_t*> rngs(n); for (int i = 0; i < n; ++i) rngs[i] = batch[i]->rng;
-                    rc = skw_full_batch_rng(ctx, &batch[0]->params, ptrs.data(), ns.data(), n, 0, rngs.data(), res.data());
+                    std::vector<skw_full_params> pv(n); bool differ = false;
+                    for (int i = 0; i < n; ++i) { pv[i] = batch[i]->params; differ = differ || memcmp(&pv[0], &pv[i], sizeof(skw_full_params)) != 0; }
+                    // (jobs that all share one parameter block run the uniform call: the same launches as before mixed batches existed)
+                    rc = differ ? skw_full_batch_mixed(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), res.data())
+                                : skw_full_batch_rng(ctx, &pv[0], ptrs.data(), ns.data(), n, 0, rngs.data(), res.data());
+                    g_engine_calls.fetch_add(1); g_batch_jobs.fetch_add(n); if (differ) g_mixed_calls.fetch_add(1);
                     if (rc == 0) for (int i = 0; i < n; ++i) batch[i]->result = res[i]; else why = skw_ctx_last_error(ctx);
+                    if (rc != 0 && differ) {
+                        // A refusal must stay with the request that earned it: jobs of differently configured instances share this call, and one of them being refused
+                        // (the engine fails the whole call and hands no generator state back) is no reason for the others to fail.  Each job again, alone, under its own
+                        // parameters; every job gets its own outcome.  (Jobs with equal blocks share their configuration, and shared the call before mixed batches too.)
+                        for (int i = 0; i < n; ++i) {
+                            skw_result one{}; const float* pp = ptrs[i]; uint32_t* rg = rngs[i];
+                            int r1 = skw_full_batch_rng(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &one);
+                            g_engine_calls.fetch_add(1);
+                            if (r1 == 0) batch[i]->result = one;
+                            else { try { batch[i]->error = skw_ctx_last_error(ctx); } catch (const std::exception&) { r1 = -1; } }      // (a promise is satisfied once)
+                            batch[i]->done.set_value(r1);
+                        }
+                        continue;
+                    }
                 }
             } catch (const std::exception& e) { rc = -1; why = e.what(); }     // the worker thread must not die with waiters blocked on it
             for (int i = 0; i < n; ++i) { if (rc != 0) batch[i]->error = why; batch[i]->done.set_value(rc); }
@@ -283,19 +306,23 @@ std::shared_ptr<SharedEngine> get_engine(const WhisperConfig& cfg, WhisperPlugin
     snprintf(keybuf, sizeof keybuf, "|%d|%d|%s", cfg.use_gpu ? 1 : 0, cfg.gpu_device, cfg.precision.c_str());   // the reference's key (path, use_gpu, gpu_device) + the additive precision
     const std::string key = cfg.model_path + keybuf;
     EngineCache& cache = engine_cache();
-    std::lock_guard<std::mutex> l(cache.mu);
+    std::unique_lock<std::mutex> l(cache.mu);
     auto it = cache.map.find(key);
     if (it != cache.map.end()) {
         g_cache_hits.fetch_add(1);
+        // ws_mu is held for the whole of a running batch: the cache's mutex is let go first, so that creating an instance of ANOTHER engine (or reading the statistics)
+        // does not wait behind this engine's batch (entries are never removed from the map: the pointer stays good)
+        const std::shared_ptr<SharedEngine> e = it->second;
+        l.unlock();
         // additive scheduler params: the most recent instance's
-        { std::lock_guard<std::mutex> le(it->second->mu); it->second->batch_limit = cfg.max_batch; it->second->window_ms = cfg.batch_window_ms; }
-        { std::lock_guard<std::mutex> lw(it->second->ws_mu);      // the floor follows the largest configuration seen; the workspace itself grows (or comes back) with the next batch
-          it->second->floor_samples = std::max(it->second->floor_samples, SharedEngine::samples_for(cfg.max_segment_duration_secs));
-          it->second->floor_batch = std::max(it->second->floor_batch, cfg.max_batch);
+        { std::lock_guard<std::mutex> le(e->mu); e->batch_limit = cfg.max_batch; e->window_ms = cfg.batch_window_ms; e->mixed = cfg.mixed_batch; }
+        { std::lock_guard<std::mutex> lw(e->ws_mu);      // the floor follows the largest configuration seen; the workspace itself grows (or comes back) with the next batch
+          e->floor_samples = std::max(e->floor_samples, SharedEngine::samples_for(cfg.max_segment_duration_secs));
+          e->floor_batch = std::max(e->floor_batch, cfg.max_batch);
           // an engine whose last instance had gone gets its workspace back here, at instance creation — where the reference creates a WhisperState (lib.rs:377-379) — not inside the first batch
-          if (!it->second->ctx && !it->second->ensure_workspace(it->second->floor_samples, it->second->floor_batch, err)) return nullptr; }
+          if (!e->ctx && !e->ensure_workspace(e->floor_samples, e->floor_batch, err)) return nullptr; }
         if (who) who->log(SK_LOG_INFO, "CACHE HIT: Reusing cached Whisper context (model_path=%s, gpu_device=%d, precision=%s)", cfg.model_path.c_str(), cfg.gpu_device, cfg.precision.c_str());
-        return it->second;
+        return e;
     }
     if (who) who->log(SK_LOG_INFO, "CACHE MISS: Loading Whisper model (model_path=%s, gpu_device=%d, precision=%s)", cfg.model_path.c_str(), cfg.gpu_device, cfg.precision.c_str());
     char ebuf[512] = {0};
@@ -304,9 +331,10 @@ std::shared_ptr<SharedEngine> get_engine(const WhisperConfig& cfg, WhisperPlugin
     eng->model = skw_model_load(cfg.model_path.c_str(), cfg.gpu_device, ebuf, sizeof ebuf);
     if (!eng->model) { *err = ebuf[0] ? ebuf : ("Failed to load Whisper model from '" + cfg.model_path + "'"); return nullptr; }
     g_model_loads.fetch_add(1);
+    { skw_hparams hp{}; skw_model_get_hparams(eng->model, &hp); eng->multilingual = hp.n_vocab >= 51865; }
     const auto t1 = std::chrono::steady_clock::now();
     eng->batch_limit = cfg.max_batch;
-    eng->window_ms = cfg.batch_window_ms;
+    eng->window_ms = cfg.batch_window_ms; eng->mixed = cfg.mixed_batch;
     eng->precision = cfg.precision == "f16_mfma" ? SKW_PRECISION_F16_MFMA : SKW_PRECISION_EXACT;
     eng->floor_samples = SharedEngine::samples_for(cfg.max_segment_duration_secs); eng->floor_batch = cfg.max_batch;
     if (!eng->ensure_workspace(eng->floor_samples, eng->floor_batch, err)) return nullptr;
@@ -397,6 +425,8 @@ bool transcribe_and_emit(WhisperPlugin* self, const Emit& em, const skw::Segment
     skw_full_default_params(&job->params);
     int lang = self->config.language == "auto" ? -1 : skw_model_lang_id(self->config.language.c_str());     // "auto": whisper.cpp detects it from the first window
     if (lang < 0 && self->config.language != "auto") { *err = "Whisper inference failed: unknown language '" + self->config.language + "'"; return false; }
+    // an English-only model cannot detect a language (whisper.cpp: "failed to auto-detect language"): this request's own error, raised before its segment joins a batch
+    if (lang < 0 && !self->engine->multilingual) { *err = "Whisper inference failed: failed to auto-detect language: the model is not multilingual"; return false; }
     job->params.lang_id = lang; job->params.translate = 0;
     job->params.suppress_blank = self->config.suppress_blank ? 1 : 0; job->params.suppress_nst = self->config.suppress_non_speech_tokens ? 1 : 0;
     job->params.n_threads = (int32_t)self->config.n_threads;
@@ -466,6 +496,7 @@ const char* const kSchema =
     "\"precision\":{\"type\":\"string\",\"description\":\"(additive) exact (f32-chain contractions, bit-reproducible; block-quantised model files run ggml's q8 arithmetic) | f16_mfma (f16 matrix cores; quantised files as their f16 twin)\",\"default\":\"exact\"},"
     "\"batch_window_ms\":{\"type\":\"integer\",\"description\":\"(additive) how long the per-GPU scheduler waits for concurrent instances before launching a batch\",\"default\":2},"
     "\"max_batch\":{\"type\":\"integer\",\"description\":\"(additive) largest number of segments transcribed in one GPU batch\",\"default\":64},"
+    "\"mixed_batch\":{\"type\":\"boolean\",\"description\":\"(additive) segments of instances with different language / suppress_* settings share one GPU batch; false cuts a batch at the first differing job\",\"default\":true},"
     "\"flush_tail\":{\"type\":\"boolean\",\"description\":\"(additive) transcribe buffered speech when the input stream ends (the reference drops it)\",\"default\":false},"
     "\"input_sample_rate\":{\"type\":\"integer\",\"description\":\"(additive) sample rate of the mono f32 packets fed to this node; anything but 16000 is resampled to 16 kHz on the GPU with the audio::resampler node's arithmetic (chunk_frames 960) before VAD segmentation\",\"default\":16000,\"minimum\":1000,\"maximum\":768000},"
     "\"input_resample_mode\":{\"type\":\"string\",\"description\":\"(additive) linear (rubato FastFixedIn/Linear, bit for bit what audio::resampler gives) | polyphase (Kaiser-windowed sinc)\",\"default\":\"linear\"}"
@@ -599,6 +630,13 @@ extern "C" const CNativePluginAPI* streamkit_native_plugin_api(void) { return &k
 extern "C" void skw_whisper_plugin_cache_stats(int* model_loads, int* cache_hits) {
     if (model_loads) *model_loads = g_model_loads.load();
     if (cache_hits) *cache_hits = g_cache_hits.load();
+}
+// additive, for tests and tools/bench_plugin.py: engine calls made by the schedulers of this process, the jobs (segments) they carried, and how many of the calls carried jobs that
+// did not all share one parameter block (skw_full_batch_mixed) — what tells a joined batch from several sequential ones.  Plain counters: no GPU is touched.
+extern "C" void skw_whisper_plugin_batch_stats(long* engine_calls, long* jobs, long* mixed_calls) {
+    if (engine_calls) *engine_calls = g_engine_calls.load();
+    if (jobs) *jobs = g_batch_jobs.load();
+    if (mixed_calls) *mixed_calls = g_mixed_calls.load();
 }
 // additive, for tests: cached engines (models resident), how many of them hold a batch workspace right now, and live plugin instances over all of them
 extern "C" void skw_whisper_plugin_workspace_stats(int* engines, int* workspaces, int* instances) {

@@ -89,6 +89,7 @@ def lib():
         L.skw_full_default_params.argtypes = [C.POINTER(FullParams)]
         L.skw_full_batch.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Result)]
         L.skw_full_batch_rng.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(Result)]
+        L.skw_full_batch_mixed.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(Result)]
         L.skw_rng_state_init.argtypes = [C.c_void_p]
         L.skw_result_free.argtypes = [C.POINTER(Result)]
         L.skw_full_batch_traced.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int,
@@ -115,6 +116,7 @@ def lib():
         L.skw_ctx_profile_get.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_long), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.skw_debug_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
         L.skw_debug_sample_rows.argtypes = [C.c_void_p, C.POINTER(FullParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.skw_debug_sample_rows_mixed.argtypes = [C.c_void_p, C.POINTER(FullParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.skw_debug_enable.argtypes = [C.c_int]
         L.skw_debug_get.restype = C.c_long
         L.skw_debug_get.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
@@ -217,8 +219,16 @@ class Context:
         trace=True (or forced=[per-clip int32 id sequences]): skw_full_batch_traced — returns (results, traces), traces[i] a structured
         array (TRACE_DT) with one record per sampling decision of clip i; with `forced` the decoder is fed those ids (teacher forcing).
         rng_states=[uint32[625] or None per clip] (rng_state_new()): the temperature ladder's std::mt19937 stream of each clip's OWNER, continued and updated in place
-        (skw_full_batch_rng: whisper.cpp keeps one generator per state and lets it run on across calls)."""
-        p = params or self.default_params()
+        (skw_full_batch_rng: whisper.cpp keeps one generator per state and lets it run on across calls).
+        params=[FullParams per clip]: skw_full_batch_mixed — every clip decodes under its own parameters in the one batch (rng_states allowed with it).  Tracing / teacher
+        forcing takes one FullParams and no rng_states: either combination raises ValueError."""
+        per_clip = isinstance(params, (list, tuple))
+        if trace or forced is not None:      # (checked before anything touches the library or the device)
+            if per_clip:
+                raise ValueError("full_batch: trace / forced take one FullParams, not a list (tracing with per-clip parameters is not supported)")
+            if rng_states is not None:
+                raise ValueError("full_batch: rng_states cannot be combined with trace / forced (the traced call starts every generator at seed 0)")
+        p = (FullParams * len(params))(*params) if per_clip else (params or self.default_params())
         if device_ptrs is not None:
             n = len(device_ptrs)
             ptrs = (C.c_void_p * n)(*device_ptrs)
@@ -230,6 +240,8 @@ class Context:
             ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
             ns = (C.c_int32 * n)(*[c.size for c in clips])
             on_dev = 0
+        if per_clip and len(params) != n:
+            raise ValueError("full_batch: %d parameter blocks for %d clips" % (len(params), n))
         res = (Result * n)()
         if trace or forced is not None:
             tr = (Trace * n)()
@@ -244,10 +256,15 @@ class Context:
                 a = np.frombuffer((C.c_char * (tr[i].n * TRACE_DT.itemsize)).from_address(tr[i].steps), dtype=TRACE_DT).copy() if tr[i].n else np.zeros(0, TRACE_DT)
                 traces.append(a)
                 lib().skw_trace_free(C.byref(tr[i]))
-        elif rng_states is not None:
-            assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
-            sp = (C.c_void_p * n)(*[None if s is None else s.ctypes.data for s in rng_states])
-            self._check(lib().skw_full_batch_rng(self.h, C.byref(p), ptrs, ns, n, on_dev, sp, res))
+        elif rng_states is not None or per_clip:
+            sp = None
+            if rng_states is not None:
+                assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
+                sp = (C.c_void_p * n)(*[None if s is None else s.ctypes.data for s in rng_states])
+            if per_clip:
+                self._check(lib().skw_full_batch_mixed(self.h, p, ptrs, ns, n, on_dev, sp, res))
+            else:
+                self._check(lib().skw_full_batch_rng(self.h, C.byref(p), ptrs, ns, n, on_dev, sp, res))
         else:
             self._check(lib().skw_full_batch(self.h, C.byref(p), ptrs, ns, n, on_dev, res))
         out = [_result_to_dict(res[i]) for i in range(n)]
@@ -330,9 +347,13 @@ class Context:
     def sample_rows(self, hists, logits, params=None, form=0, want_filtered=False):
         """K11 on its own (skw_debug_sample_rows): one sampler launch decides the next token of len(hists) decoders whose sampled tokens so far are
         hists[r], on caller-supplied logits [rows][n_vocab].  form 0: the decode step's sampler; 1: the streaming kernel (leaves the filtered row
-        in memory: want_filtered).  -> (tokens structured array, trace records, filtered logits or None)"""
-        p = params or self.default_params()
+        in memory: want_filtered).  -> (tokens structured array, trace records, filtered logits or None)
+        params=[FullParams per row]: the per-row form of the sampler (skw_debug_sample_rows_mixed) — every row under its own rules and its own static mask."""
+        per_row = isinstance(params, (list, tuple))
         R = len(hists)
+        if per_row and len(params) != R:
+            raise ValueError("sample_rows: %d parameter blocks for %d rows" % (len(params), R))
+        p = (FullParams * R)(*params) if per_row else (params or self.default_params())
         stride = max(1, max(len(h) for h in hists))
         hb = np.zeros((R, stride), dtype=np.int32)
         for r, h in enumerate(hists):
@@ -342,8 +363,9 @@ class Context:
         filt = np.empty_like(lg) if want_filtered else None
         toks = np.zeros(R, dtype=_TOKEN_DT)
         tr = np.zeros(R, dtype=TRACE_DT)
-        self._check(lib().skw_debug_sample_rows(self.h, C.byref(p), R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
-                                                filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data))
+        fn = lib().skw_debug_sample_rows_mixed if per_row else lib().skw_debug_sample_rows
+        self._check(fn(self.h, p if per_row else C.byref(p), R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
+                       filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data))
         return toks, tr, filt
 
     def math(self, kind, x):

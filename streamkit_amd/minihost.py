@@ -65,6 +65,17 @@ def run_oneshot(nodes, pcms, packet=960):
     return ms.value
 
 
+def whisper_batch_stats():
+    """skw_whisper_plugin_batch_stats of libwhisper.so: (engine_calls, jobs, mixed_calls) of this process's Whisper schedulers — GPU calls made, segments they carried, and
+    the calls whose segments did not all share one parameter block (skw_full_batch_mixed).  Plain counters; no GPU needed."""
+    L = C.CDLL(os.path.join(ROOT, "streamkit_amd", "libwhisper.so"))      # (the handle the mini-host holds once the plugin is loaded)
+    L.skw_whisper_plugin_batch_stats.argtypes = [C.POINTER(C.c_long)] * 3
+    L.skw_whisper_plugin_batch_stats.restype = None
+    calls, jobs, mixed = C.c_long(), C.c_long(), C.c_long()
+    L.skw_whisper_plugin_batch_stats(C.byref(calls), C.byref(jobs), C.byref(mixed))
+    return calls.value, jobs.value, mixed.value
+
+
 class Plugin:
     def __init__(self, path=None):
         path = path or os.path.join(ROOT, "streamkit_amd", "libwhisper.so")
