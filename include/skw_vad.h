@@ -13,8 +13,17 @@
  *   drop                                                  skw_vad_free(vad)
  *
  * The threshold comparison (`probability >= threshold`, vad.rs:131-134, lib.rs:421) stays with the caller, as in the reference's
- * `process` loop.  CPU code by design (a 128-unit LSTM stepped 31 times per audio-second; strictly sequential per stream); the
- * same header-only implementation (streamkit_amd/csrc/skw_silero.h) is compiled into libwhisper.so.
+ * `process` loop.  libskw_vad.so is CPU code with no GPU dependency; the same header-only implementation
+ * (streamkit_amd/csrc/skw_silero.h) is compiled into libwhisper.so.
+ *
+ * Two arithmetics evaluate the same network.  SKW_VAD_ARITH_LIBM is the gate as it always was (libm expf / tanhf, the host
+ * compiler's mul-add) and what skw_vad_create gives.  SKW_VAD_ARITH_CONTRACT is the arithmetic stated in
+ * include/skw_silero_net.h (explicit k-ascending fma chains, skw_expf); the HIP kernels behind skw_vad_gpu_process
+ * (libskw_engine.so) reproduce it bit for bit, batched over frames and streams: only W_hh.h and
+ * the gate non-linearities of the LSTM are sequential per stream.  Both evaluators and the GPU share one state block of
+ * 320 floats per stream (context[64], h[128], c[128]), so a stream may move between them at any frame.
+ * This header keeps the five calls that mirror the reference; everything additive — the choice of arithmetic, many frames per
+ * call, the state block, the GPU gate — is declared in include/skw_vad_batch.h.
  */
 #ifndef SKW_VAD_H
 #define SKW_VAD_H
@@ -31,6 +40,7 @@ int  skw_vad_process_chunk(skw_vad*, const float* frame512, float* probability);
 void skw_vad_reset(skw_vad*);
 void skw_vad_state(const skw_vad*, float* out256);   /* [2][1][128]: h then c */
 void skw_vad_free(skw_vad*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 #include "../../include/streamkit_native_abi.h"
 #include "skw_segmenter.h"
 #include "skw_kokoro_text.h"
+#include "skw_silero.h"
 #include <dlfcn.h>
 #include <cmath>
 #include <cstdio>
@@ -18,6 +19,8 @@
 #include <cstring>
 #include <ctime>
 #include <algorithm>
+#include <memory>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
@@ -332,6 +335,72 @@ int mh_segment_sim(const float* prob, int n_frames, float threshold, uint64_t mi
             n_cuts++; return true; }, &err);
     }
     return n_cuts;
+}
+// Second segmenter hook: the whole of skw::Segmenter as the Whisper node drives it — arbitrary packet sizes, vad_batch_frames, a scripted gate or the Silero
+// gate in the contract arithmetic, one update in mid-stream (what plugin_update_params does: pending frames judged by the old gate and threshold, then the
+// swap), one aborted cut, and the drain / tail of plugin_flush.  events[i] = {kind (0 start, 1 cut, 2 tail, 3 cut whose hand-over was refused), start_ms, end_ms,
+// samples, reason (0 max_duration, 1 silence, 2 flush), silence_ms or -1, segment counter, bits of the start probability | checksum of the samples, packet index}.
+struct mh_segrun_params {
+    int32_t batch_frames; float threshold; uint64_t min_silence_ms; float max_secs;
+    const float* script; const char* silero_path;          // script != NULL: probability of frame i is script[i]; else a SileroContractVad over silero_path
+    int64_t swap_at_sample;                                // -1: no update.  Else packets are split there and the update is applied between the two halves:
+    float swap_threshold; int32_t swap_batch_frames; int32_t swap_gate; const float* swap_script;      // swap_gate: a fresh gate (swap_script from its index 0, or a fresh Silero state)
+    int32_t abort_cut;                                     // the hand-over of cut number abort_cut is refused once (-1: never)
+    int32_t flush;                                         // 1: drain at the end; 2: drain and take the tail
+};
+struct ContractGate : skw::Vad {
+    skw::SileroContractVad v; explicit ContractGate(std::shared_ptr<const skw::SileroWeights> w) : v(std::move(w)) {}
+    float process_chunk(const float* f) override { return v.process_chunk(f); }
+    void process_chunks(const float* f, size_t n, float* p) override { v.process_chunks(f, n, p); }
+};
+int mh_segment_run(const mh_segrun_params* P, const float* samples, size_t n_samples, const int64_t* packets, int n_packets, long long* events, int max_events, char* err, size_t errlen) {
+    try {
+        skw::Segmenter seg; seg.configure(P->threshold, P->min_silence_ms, P->max_secs); seg.set_batch_frames((size_t)P->batch_frames);
+        std::shared_ptr<skw::SileroWeights> w;
+        auto make_gate = [&](const float* script) -> std::unique_ptr<skw::Vad> {
+            if (script) { auto* g = new ScriptVad(); g->p = script; return std::unique_ptr<skw::Vad>(g); }
+            if (!w) { w = std::make_shared<skw::SileroWeights>(); std::string e; if (!skw::SileroVad::load_weights(P->silero_path ? P->silero_path : "", w.get(), &e)) throw std::runtime_error(e); }
+            return std::unique_ptr<skw::Vad>(new ContractGate(w));
+        };
+        std::unique_ptr<skw::Vad> vad = make_gate(P->script);
+        int n_ev = 0, n_cuts = 0, packet = 0; bool abort_done = false;
+        auto checksum = [](const std::vector<float>& x) { uint64_t h = 1469598103934665603ull;
+            for (float f : x) { uint32_t u; memcpy(&u, &f, 4); h = (h ^ u) * 1099511628211ull; } return (long long)(h >> 1); };
+        auto counter = [](const std::string& id) { const size_t k = id.rfind('-'); return k == std::string::npos ? -1ll : atoll(id.c_str() + k + 1); };
+        auto put = [&](long long kind, long long a, long long b, long long n, long long reason, long long sil, long long ctr, long long extra) {
+            if (n_ev < max_events) { long long* o = events + 9 * n_ev; o[0] = kind; o[1] = a; o[2] = b; o[3] = n; o[4] = reason; o[5] = sil; o[6] = ctr; o[7] = extra; o[8] = packet; }
+            n_ev++;
+        };
+        auto on_start = [&](const skw::SpeechStart& s) { uint32_t u; memcpy(&u, &s.probability, 4); put(0, (long long)s.start_time_ms, -1, 0, -1, -1, counter(s.segment_id), u); };
+        auto on_cut = [&](const skw::SegmentCut& c) {
+            const bool refuse = !abort_done && n_cuts == P->abort_cut; if (refuse) abort_done = true;
+            put(refuse ? 3 : 1, (long long)c.start_time_ms, (long long)c.end_time_ms, (long long)c.samples.size(), strcmp(c.reason, "silence") == 0 ? 1 : 0,
+                c.has_silence_duration ? (long long)c.silence_duration_ms : -1, counter(c.segment_id), checksum(c.samples));
+            n_cuts++; return !refuse;
+        };
+        std::string e; size_t pos = 0;
+        auto feed = [&](size_t n) { seg.push(samples + pos, n, *vad, on_start, on_cut, &e); pos += n; };
+        bool swapped = P->swap_at_sample < 0;
+        for (packet = 0; packet < n_packets && pos < n_samples; ++packet) {
+            size_t n = std::min((size_t)packets[packet], n_samples - pos);
+            if (!swapped && pos + n >= (size_t)P->swap_at_sample) {
+                const size_t head = (size_t)P->swap_at_sample - pos; feed(head); n -= head;
+                if (P->swap_gate || P->swap_threshold != P->threshold) { seg.judge_pending(*vad); if (P->swap_gate) vad = make_gate(P->swap_script); }
+                seg.set_threshold(P->swap_threshold); if (P->swap_batch_frames > 0) seg.set_batch_frames((size_t)P->swap_batch_frames);
+                swapped = true;
+            }
+            feed(n);
+        }
+        if (P->flush >= 1) {
+            while (!seg.drain(*vad, on_start, on_cut)) {}                    // a refused hand-over ends one drain; the next takes up the judged frames where it stopped
+            skw::SegmentCut tail;
+            if (P->flush >= 2 && seg.take_tail(&tail))
+                put(2, (long long)tail.start_time_ms, (long long)tail.end_time_ms, (long long)tail.samples.size(), 2, -1, counter(tail.segment_id), checksum(tail.samples));
+        }
+        // closing row: the segmenter's own counters
+        put(4, (long long)seg.absolute_time_ms(), (long long)seg.pending_frames(), (long long)seg.judged_frames(), -1, -1, -1, (long long)seg.buffered_speech_samples());
+        return n_ev;
+    } catch (const std::exception& ex) { if (err && errlen) snprintf(err, errlen, "%s", ex.what()); return -1; }
 }
 // ------------------------------------------------------------------ core::json_serialize (json_serialize.rs:85-107)
 // serde_json::to_vec / to_vec_pretty of the externally tagged `Packet` enum (crates/core/src/types.rs:92-113), one per output packet,

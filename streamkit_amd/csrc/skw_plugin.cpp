@@ -15,6 +15,7 @@
 #include "../../include/streamkit_native_abi.h"
 #include "../../include/skw_engine.h"
 #include "skw_segmenter.h"
+#include "../../include/skw_vad_batch.h"
 #include "skw_silero.h"
 #include "skw_resampler_core.h"
 #include <sys/stat.h>
@@ -72,6 +73,8 @@ struct WhisperConfig {
     int batch_window_ms = 2; int max_batch = 64; bool flush_tail = false;
     bool mixed_batch = true;         // segments of differently configured instances share a GPU batch (skw_full_batch_mixed); false: a batch is cut at the first job whose parameters differ
     std::string precision = "exact"; // exact | f16_mfma  (include/skw_engine.h, SKW_PRECISION_*)
+    std::string vad_device = "cpu";  // cpu (the libm Silero gate, frame by frame) | gpu (Silero in the contract arithmetic of include/skw_silero_net.h on gpu_device's GPU)
+    int vad_batch_frames = 1;        // complete 512-sample frames held back before the gate is asked for their probabilities in one call
     uint32_t input_sample_rate = 16000; std::string input_resample_mode = "linear";   // linear (the audio::resampler node's rubato arithmetic, bit for bit) | polyphase
 };
 
@@ -94,6 +97,11 @@ bool parse_config(const char* json, WhisperConfig* cfg, std::string* err) {
     if (!str("model_path", &cfg->model_path) || !str("language", &cfg->language) || !str("vad_model_path", &cfg->vad_model_path) || !str("vad_mode", &cfg->vad_mode)
         || !str("precision", &cfg->precision)) return false;
     if (cfg->precision != "exact" && cfg->precision != "f16_mfma") { *err = "Invalid config: precision must be \"exact\" or \"f16_mfma\""; return false; }
+    if (!str("vad_device", &cfg->vad_device)) return false;
+    if (cfg->vad_device != "cpu" && cfg->vad_device != "gpu") { *err = "Invalid config: vad_device must be \"cpu\" or \"gpu\""; return false; }
+    d = cfg->vad_batch_frames; if (!num("vad_batch_frames", &d)) return false;
+    if (d < 1 || d > 65536 || d != std::floor(d)) { *err = "Invalid config: vad_batch_frames must be an integer between 1 and 65536"; return false; }
+    cfg->vad_batch_frames = (int)d;
     if (!str("input_resample_mode", &cfg->input_resample_mode)) return false;
     if (cfg->input_resample_mode != "linear" && cfg->input_resample_mode != "polyphase") { *err = "Invalid config: input_resample_mode must be \"linear\" or \"polyphase\""; return false; }
     d = cfg->input_sample_rate; if (!num("input_sample_rate", &d)) return false;
@@ -354,8 +362,38 @@ struct SileroGate : skw::Vad {
     float process_chunk(const float* f) override { return v.process_chunk(f); }
     void reset() override { v.reset(); }
 };
+// vad_device "gpu": the same network in the contract arithmetic.  Calls of at least kGpuMinFrames frames go to the device context of (file, device) — one per
+// process, shared by every instance, serialised inside skw_vad_gpu_process — smaller ones to the CPU contract evaluator, which gives the same bits: where a
+// call is evaluated is invisible in the result.  The stream's state lives in the CPU evaluator and travels with each GPU call.
+constexpr size_t kGpuMinFrames = 8;
+struct SileroGpuGate : skw::Vad {
+    skw::SileroContractVad v; skw_vad_gpu* gpu;
+    SileroGpuGate(std::shared_ptr<const skw::SileroWeights> w, skw_vad_gpu* g) : v(std::move(w)), gpu(g) {}
+    float process_chunk(const float* f) override { return v.process_chunk(f); }
+    void process_chunks(const float* frames, size_t n, float* probs) override {
+        if (n < kGpuMinFrames) { v.process_chunks(frames, n, probs); return; }
+        float st[320]; v.get_state(st);
+        const float* fp[1] = {frames}; const int32_t nf[1] = {(int32_t)n}; float* sp[1] = {st}; float* pp[1] = {probs};
+        if (skw_vad_gpu_process(gpu, 1, fp, nf, sp, pp) != 0)
+            throw std::runtime_error(std::string("Silero VAD on the GPU failed: ") + skw_vad_gpu_last_error(gpu));   // no fall-back; guarded() reports it
+        v.set_state(st);
+    }
+    void reset() override { v.reset(); }
+};
 std::mutex g_vad_mu;
 std::map<std::string, std::shared_ptr<const skw::SileroWeights>> g_vad_cache;
+std::map<std::string, skw_vad_gpu*> g_vad_gpu_cache;      // (file, device) -> device context, kept for the life of the process like the Whisper contexts
+skw_vad_gpu* get_silero_gpu(const std::string& path, int device, std::string* err) {
+    std::lock_guard<std::mutex> l(g_vad_mu);
+    const std::string key = path + "|" + std::to_string(device);
+    auto it = g_vad_gpu_cache.find(key);
+    if (it != g_vad_gpu_cache.end()) return it->second;
+    char ebuf[512] = {0};
+    skw_vad_gpu* g = skw_vad_gpu_create(path.c_str(), device, ebuf, sizeof ebuf);
+    if (!g) { *err = ebuf; return nullptr; }
+    g_vad_gpu_cache[key] = g;
+    return g;
+}
 std::shared_ptr<const skw::SileroWeights> get_silero(const std::string& path, std::string* err) {
     std::lock_guard<std::mutex> l(g_vad_mu);
     auto it = g_vad_cache.find(path);
@@ -368,6 +406,12 @@ std::shared_ptr<const skw::SileroWeights> get_silero(const std::string& path, st
 }
 
 // SileroVAD::new at lib.rs:382-383 ("Failed to initialize VAD: {e}") / :557-560 ("Failed to reload VAD: {e}", added by the caller)
+std::unique_ptr<skw::Vad> make_silero_gate(const WhisperConfig& cfg, std::shared_ptr<const skw::SileroWeights> w, std::string* err) {
+    if (cfg.vad_device != "gpu") return std::unique_ptr<skw::Vad>(new SileroGate(w));
+    skw_vad_gpu* g = get_silero_gpu(cfg.vad_model_path, cfg.gpu_device, err);
+    if (!g) return nullptr;                                                        // a gate that was asked to run on the GPU and cannot is an error, never a quiet CPU gate
+    return std::unique_ptr<skw::Vad>(new SileroGpuGate(w, g));
+}
 std::unique_ptr<skw::Vad> make_vad(const WhisperConfig& cfg, WhisperPlugin* p, std::string* err) {
     std::string mode = cfg.vad_mode;
     if (mode == "auto") {
@@ -377,7 +421,12 @@ std::unique_ptr<skw::Vad> make_vad(const WhisperConfig& cfg, WhisperPlugin* p, s
             // seen files of tools/make_synth_silero.py's making; the reference names v6, vad.rs:5).  In auto mode that is a warning and the energy
             // gate, not a node that fails to start; `vad_mode: "silero"` keeps the reference's hard failure.
             std::string e; auto w = get_silero(cfg.vad_model_path, &e);
-            if (w) { if (p) p->log(SK_LOG_INFO, "Silero VAD: %s", w->bound.c_str()); return std::unique_ptr<skw::Vad>(new SileroGate(w)); }
+            if (w) {
+                if (p) p->log(SK_LOG_INFO, "Silero VAD: %s", w->bound.c_str());
+                auto gate = make_silero_gate(cfg, w, &e);
+                if (!gate) *err = "Failed to initialize VAD: " + e;
+                return gate;
+            }
             if (p) p->log(SK_LOG_WARN, "%s; using vad_mode=energy (set vad_mode to \"silero\" to make this an error)", e.c_str());
             mode = "energy";
         } else {
@@ -386,13 +435,17 @@ std::unique_ptr<skw::Vad> make_vad(const WhisperConfig& cfg, WhisperPlugin* p, s
             mode = "energy";
         }
     }
+    if ((mode == "always" || mode == "energy") && cfg.vad_device == "gpu" && p)
+        p->log(SK_LOG_INFO, "vad_device \"gpu\" is unused with vad_mode=%s (only the Silero gate runs on the GPU)", mode.c_str());
     if (mode == "always") return std::unique_ptr<skw::Vad>(new skw::AlwaysSpeechVad());
     if (mode == "energy") return std::unique_ptr<skw::Vad>(new skw::EnergyVad());
     if (mode == "silero") {
         std::string e; auto w = get_silero(cfg.vad_model_path, &e);
         if (!w) { *err = "Failed to initialize VAD: " + e; return nullptr; }
         if (p) p->log(SK_LOG_INFO, "Silero VAD: %s", w->bound.c_str());
-        return std::unique_ptr<skw::Vad>(new SileroGate(w));
+        auto gate = make_silero_gate(cfg, w, &e);
+        if (!gate) *err = "Failed to initialize VAD: " + e;
+        return gate;
     }
     *err = "Failed to initialize VAD: unknown vad_mode '" + mode + "'"; return nullptr;
 }
@@ -470,7 +523,7 @@ bool transcribe_and_emit(WhisperPlugin* self, const Emit& em, const skw::Segment
 void emit_speech_start(WhisperPlugin* self, const Emit& em, const skw::SpeechStart& s) {
     if (!self->config.emit_vad_events) return;
     std::string j = "{\"segment_id\":" + skw::json_quote(s.segment_id) + ",\"speech_probability\":" + skw::json_f32(s.probability) +
-                    ",\"start_time_ms\":" + std::to_string(s.start_time_ms) + ",\"threshold\":" + skw::json_f32(self->config.vad_threshold) + "}";
+                    ",\"start_time_ms\":" + std::to_string(s.start_time_ms) + ",\"threshold\":" + skw::json_f32(s.threshold) + "}";
     em.telemetry("vad.speech_start", j);
 }
 
@@ -493,6 +546,8 @@ const char* const kSchema =
     "\"suppress_non_speech_tokens\":{\"type\":\"boolean\",\"description\":\"Suppress non-speech tokens like [BLANK_AUDIO], [MUSIC], [APPLAUSE], etc.\",\"default\":true},"
     "\"emit_vad_events\":{\"type\":\"boolean\",\"description\":\"Emit VAD speech start/end out-of-band to the telemetry bus (does not flow through graph pins).\",\"default\":false},"
     "\"vad_mode\":{\"type\":\"string\",\"description\":\"(additive) auto (Silero when vad_model_path exists, else an energy gate) | silero | energy | always\",\"default\":\"auto\"},"
+    "\"vad_device\":{\"type\":\"string\",\"description\":\"(additive) cpu (the Silero gate frame by frame on the host) | gpu (the Silero gate in the bit-exact contract arithmetic on the GPU of gpu_device; unused with the energy / always gates)\",\"default\":\"cpu\"},"
+    "\"vad_batch_frames\":{\"type\":\"integer\",\"description\":\"(additive) complete 512-sample frames held back before the VAD gate evaluates them in one call; cuts, ids and timestamps do not depend on it, a cut is handed over up to N-1 frames (32 ms each) later; file transcription sets 64 or more\",\"default\":1,\"minimum\":1,\"maximum\":65536},"
     "\"precision\":{\"type\":\"string\",\"description\":\"(additive) exact (f32-chain contractions, bit-reproducible; block-quantised model files run ggml's q8 arithmetic) | f16_mfma (f16 matrix cores; quantised files as their f16 twin)\",\"default\":\"exact\"},"
     "\"batch_window_ms\":{\"type\":\"integer\",\"description\":\"(additive) how long the per-GPU scheduler waits for concurrent instances before launching a batch\",\"default\":2},"
     "\"max_batch\":{\"type\":\"integer\",\"description\":\"(additive) largest number of segments transcribed in one GPU batch\",\"default\":64},"
@@ -525,6 +580,7 @@ CPluginHandle create_instance_impl(const char* params, CLogCallback log_cb, void
     p->vad = make_vad(p->config, p.get(), &err);
     if (!p->vad) { p->log(SK_LOG_ERROR, "%s", err.c_str()); return nullptr; }
     p->seg.configure(p->config.vad_threshold, p->config.min_silence_duration_ms, p->config.max_segment_duration_secs);
+    p->seg.set_batch_frames((size_t)p->config.vad_batch_frames);
     if (p->config.input_sample_rate != 16000) {
         p->front.reset(new skw::ResamplerCore());
         p->front->target = 16000; p->front->chunk_frames = 960; p->front->out_frame = 0;
@@ -592,11 +648,15 @@ CResult plugin_update_params(CPluginHandle handle, const char* params) {
             if (!eng) return err_result("Failed to reload Whisper model: " + err);
             self->hold(eng);
         }
-        if (nc.vad_model_path != self->config.vad_model_path || nc.vad_threshold != self->config.vad_threshold || nc.vad_mode != self->config.vad_mode) {
+        if (nc.vad_model_path != self->config.vad_model_path || nc.vad_threshold != self->config.vad_threshold || nc.vad_mode != self->config.vad_mode || nc.vad_device != self->config.vad_device ||
+            (nc.vad_device == "gpu" && nc.gpu_device != self->config.gpu_device)) {
             auto v = make_vad(nc, self, &err);
             if (!v) { const std::string pre = "Failed to initialize VAD: "; return err_result("Failed to reload VAD: " + (err.compare(0, pre.size(), pre) == 0 ? err.substr(pre.size()) : err)); }
+            // frames held back (vad_batch_frames > 1) belong to the gate and the threshold they arrived under: judged now, consumed by the next packet or flush
+            self->seg.judge_pending(*self->vad);
             self->vad = std::move(v);
         }
+        self->seg.set_batch_frames((size_t)nc.vad_batch_frames);
         if (nc.min_silence_duration_ms != self->config.min_silence_duration_ms) self->seg.set_min_silence_ms(nc.min_silence_duration_ms);
         self->seg.set_threshold(nc.vad_threshold); self->seg.set_max_duration_secs(nc.max_segment_duration_secs);
         nc.input_sample_rate = self->config.input_sample_rate; nc.input_resample_mode = self->config.input_resample_mode;   // the front end's rate is fixed at creation (a stream does not change rate)
@@ -612,6 +672,11 @@ CResult plugin_flush(CPluginHandle handle, COutputCallback out_cb, void* out_ud,
         Emit em{out_cb, out_ud, tel_cb, tel_ud}; std::string err;
         // the resampler front end's remainder belongs to the stream whether or not the tail is then transcribed (resampler.rs:543-730 runs on input close)
         if (self->front && !self->front->finish([&](const float* d, size_t n, std::string* e) { return feed_segmenter(self, em, d, n, e); }, &err)) return err_result(err);
+        // frames held back by vad_batch_frames > 1 are part of the stream: evaluated and consumed here (with the default of 1 there are none)
+        bool failed = false;
+        self->seg.drain(*self->vad, [&](const skw::SpeechStart& s) { emit_speech_start(self, em, s); },
+                        [&](const skw::SegmentCut& cut) { if (!transcribe_and_emit(self, em, cut, &err)) { failed = true; return false; } return true; });
+        if (failed || !err.empty()) return err_result(err);
         if (!self->config.flush_tail) return ok_result();   // trait default (sdk lib.rs:324-326): buffered tail is dropped
         skw::SegmentCut cut;
         if (self->seg.take_tail(&cut) && !transcribe_and_emit(self, em, cut, &err)) return err_result(err);

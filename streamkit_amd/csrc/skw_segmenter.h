@@ -134,64 +134,61 @@ inline std::string utf8_trim(const std::string& s) {
 }
 
 // ------------------------------------------------------------------ VAD gate (vad.rs:67-120 interface: 512 samples -> probability)
-struct Vad { virtual ~Vad() {} virtual float process_chunk(const float* frame512) = 0; virtual void reset() {} };
+// process_chunks: n consecutive frames of the stream in one call (a gate that batches, such as the GPU one, overrides it); by definition n calls of process_chunk
+struct Vad { virtual ~Vad() {} virtual float process_chunk(const float* frame512) = 0; virtual void reset() {}
+             virtual void process_chunks(const float* frames, size_t n, float* probs) { for (size_t i = 0; i < n; ++i) probs[i] = process_chunk(frames + i * 512); } };
 struct AlwaysSpeechVad : Vad { float process_chunk(const float*) override { return 1.0f; } };
 // energy gate: p = rms / (rms + 0.01)  (p >= 0.5  <=>  rms >= 0.01, about -40 dBFS)
 struct EnergyVad : Vad { float process_chunk(const float* f) override { float s = 0.0f; for (int i = 0; i < 512; ++i) s += f[i] * f[i]; float rms = sqrtf(s / 512.0f); return rms / (rms + 0.01f); } };
 
 // ------------------------------------------------------------------ segmentation state machine (lib.rs:404-494)
-struct SpeechStart { std::string segment_id; uint64_t start_time_ms; float probability; };
+// Three steps, kept apart: FRAMING (samples -> complete 512-sample frames), GATE EVALUATION (frames -> probability and decision, `batch_frames` frames per
+// call of the gate) and the STATE MACHINE (decisions -> speech starts and cuts).  The gate's state never depends on what the state machine decides, so the
+// probabilities — and with them every cut, segment_id, timestamp and event — do not depend on batch_frames; only WHEN a cut is handed over does (up to
+// batch_frames - 1 frames, 32 ms each, later).  A frame is judged once: its probability and its decision (against the threshold in force when it was
+// evaluated) stay attached to it until the state machine consumes it, also across an aborted cut and across a change of gate or threshold (judge_pending).
+struct SpeechStart { std::string segment_id; uint64_t start_time_ms; float probability; float threshold; };   // threshold: the one the frame was judged against
 struct SegmentCut {
     std::vector<float> samples; uint64_t start_time_ms = 0, end_time_ms = 0; const char* reason = ""; bool has_silence_duration = false; uint64_t silence_duration_ms = 0;
     std::string segment_id;
 };
 class Segmenter {
 public:
+    typedef std::function<void(const SpeechStart&)> OnStart;
+    typedef std::function<bool(const SegmentCut&)> OnCut;
     void configure(float threshold, uint64_t min_silence_ms, float max_secs) { threshold_ = threshold; set_min_silence_ms(min_silence_ms); max_secs_ = max_secs; }
     void set_threshold(float t) { threshold_ = t; }
     void set_min_silence_ms(uint64_t ms) { silence_threshold_frames_ = (size_t)(ms / 32); }   // lib.rs:386, 571
     void set_max_duration_secs(float s) { max_secs_ = s; }
+    // how many complete frames are held back before the gate is asked for their probabilities in one call (1: every frame at once, as the reference does)
+    void set_batch_frames(size_t n) { batch_frames_ = n < 1 ? 1 : n; }
+    size_t batch_frames() const { return batch_frames_; }
     // feeds samples; on_cut returns false to abort (the error propagates like `?` in lib.rs:464, 478)
-    void push(const float* samples, size_t n, Vad& vad, const std::function<void(const SpeechStart&)>& on_start,
-              const std::function<bool(const SegmentCut&)>& on_cut, std::string* err) {
+    void push(const float* samples, size_t n, Vad& vad, const OnStart& on_start, const OnCut& on_cut, std::string* err) {
+        (void)err;
         frame_buffer_.insert(frame_buffer_.end(), samples, samples + n);
-        float frame[512];
-        while (frame_buffer_.size() >= 512) {
-            for (int i = 0; i < 512; ++i) frame[i] = frame_buffer_[i];
-            frame_buffer_.erase(frame_buffer_.begin(), frame_buffer_.begin() + 512);
-            const float probability = vad.process_chunk(frame);
-            const bool is_speech = probability >= threshold_;
-            if (is_speech) {
-                silence_frame_count_ = 0;
-                if (speech_buffer_.empty()) {
-                    segment_start_time_ms_ = absolute_time_ms_;
-                    if (segment_counter_ != UINT64_MAX) segment_counter_++;
-                    current_segment_id_ = "seg-" + std::to_string(segment_start_time_ms_) + "-" + std::to_string(segment_counter_);
-                    on_start(SpeechStart{current_segment_id_, segment_start_time_ms_, probability});
-                }
-                speech_buffer_.insert(speech_buffer_.end(), frame, frame + 512);
-                const uint64_t segment_duration_ms = absolute_time_ms_ - segment_start_time_ms_;
-                const uint64_t max_duration_ms = (uint64_t)(max_secs_ * 1000.0f);
-                if (segment_duration_ms >= max_duration_ms) {
-                    const uint64_t end_time_ms = absolute_time_ms_ + 32;
-                    if (!cut(on_cut, end_time_ms, "max_duration", false, 0)) { (void)err; return; }
-                }
-            } else {
-                silence_frame_count_ += 1;
-                if (!speech_buffer_.empty() && silence_frame_count_ >= silence_threshold_frames_) {
-                    const uint64_t silence_frames = silence_frame_count_ > 0 ? (uint64_t)silence_frame_count_ - 1 : 0;
-                    const uint64_t back = silence_frames * 32;
-                    const uint64_t end_time_ms = absolute_time_ms_ >= back ? absolute_time_ms_ - back : 0;
-                    if (!cut(on_cut, end_time_ms, "silence", true, (uint64_t)silence_frame_count_ * 32)) return;
-                }
-            }
-            absolute_time_ms_ += 32;   // 512 samples @ 16 kHz
+        if (!consume(on_start, on_cut)) return;                    // frames judged earlier: left by an aborted cut or by judge_pending
+        while (frame_buffer_.size() >= 512 * batch_frames_) {
+            evaluate(vad, batch_frames_);
+            if (!consume(on_start, on_cut)) return;
         }
     }
+    // end of stream: the held-back complete frames are evaluated and consumed; false when on_cut aborted
+    bool drain(Vad& vad, const OnStart& on_start, const OnCut& on_cut) {
+        if (!consume(on_start, on_cut)) return false;
+        evaluate(vad, frame_buffer_.size() / 512);
+        return consume(on_start, on_cut);
+    }
+    // before the gate is replaced or the threshold changes: the held-back complete frames are judged by the gate and the threshold that were in force when they
+    // arrived; nothing is emitted (update_params has no output callback), the state machine consumes them on the next push or drain
+    void judge_pending(Vad& vad) { evaluate(vad, frame_buffer_.size() / 512); }
+    size_t pending_frames() const { return frame_buffer_.size() / 512; }
+    size_t judged_frames() const { return judged_.size(); }
     // additive (flush_tail): hand over whatever speech is buffered when the stream ends
     // (while a segment is open, the < 512 samples that have not filled a VAD frame yet belong to it too)
     bool take_tail(SegmentCut* out) {
         if (speech_buffer_.empty()) return false;
+        speech_buffer_.insert(speech_buffer_.end(), judged_samples_.begin(), judged_samples_.end()); judged_samples_.clear(); judged_.clear();   // (only after an aborted cut)
         speech_buffer_.insert(speech_buffer_.end(), frame_buffer_.begin(), frame_buffer_.end()); frame_buffer_.clear();
         out->samples.swap(speech_buffer_); speech_buffer_.clear(); out->start_time_ms = segment_start_time_ms_;
         out->end_time_ms = absolute_time_ms_; out->reason = "flush"; out->segment_id = current_segment_id_;
@@ -200,6 +197,51 @@ public:
     uint64_t absolute_time_ms() const { return absolute_time_ms_; }
     size_t buffered_speech_samples() const { return speech_buffer_.size(); }
 private:
+    struct Judged { float probability; bool is_speech; float threshold; };
+    void evaluate(Vad& vad, size_t k) {
+        if (k == 0) return;
+        eval_.assign(frame_buffer_.begin(), frame_buffer_.begin() + 512 * k);
+        frame_buffer_.erase(frame_buffer_.begin(), frame_buffer_.begin() + 512 * k);
+        probs_.resize(k);
+        if (k == 1) probs_[0] = vad.process_chunk(eval_.data()); else vad.process_chunks(eval_.data(), k, probs_.data());
+        judged_samples_.insert(judged_samples_.end(), eval_.begin(), eval_.end());
+        for (size_t i = 0; i < k; ++i) judged_.push_back(Judged{probs_[i], probs_[i] >= threshold_, threshold_});
+    }
+    bool consume(const OnStart& on_start, const OnCut& on_cut) {
+        float frame[512];
+        while (!judged_.empty()) {
+            for (int i = 0; i < 512; ++i) frame[i] = judged_samples_[i];
+            judged_samples_.erase(judged_samples_.begin(), judged_samples_.begin() + 512);
+            const float probability = judged_.front().probability, judged_against = judged_.front().threshold; const bool is_speech = judged_.front().is_speech;
+            judged_.pop_front();
+            if (is_speech) {
+                silence_frame_count_ = 0;
+                if (speech_buffer_.empty()) {
+                    segment_start_time_ms_ = absolute_time_ms_;
+                    if (segment_counter_ != UINT64_MAX) segment_counter_++;
+                    current_segment_id_ = "seg-" + std::to_string(segment_start_time_ms_) + "-" + std::to_string(segment_counter_);
+                    on_start(SpeechStart{current_segment_id_, segment_start_time_ms_, probability, judged_against});
+                }
+                speech_buffer_.insert(speech_buffer_.end(), frame, frame + 512);
+                const uint64_t segment_duration_ms = absolute_time_ms_ - segment_start_time_ms_;
+                const uint64_t max_duration_ms = (uint64_t)(max_secs_ * 1000.0f);
+                if (segment_duration_ms >= max_duration_ms) {
+                    const uint64_t end_time_ms = absolute_time_ms_ + 32;
+                    if (!cut(on_cut, end_time_ms, "max_duration", false, 0)) return false;
+                }
+            } else {
+                silence_frame_count_ += 1;
+                if (!speech_buffer_.empty() && silence_frame_count_ >= silence_threshold_frames_) {
+                    const uint64_t silence_frames = silence_frame_count_ > 0 ? (uint64_t)silence_frame_count_ - 1 : 0;
+                    const uint64_t back = silence_frames * 32;
+                    const uint64_t end_time_ms = absolute_time_ms_ >= back ? absolute_time_ms_ - back : 0;
+                    if (!cut(on_cut, end_time_ms, "silence", true, (uint64_t)silence_frame_count_ * 32)) return false;
+                }
+            }
+            absolute_time_ms_ += 32;   // 512 samples @ 16 kHz
+        }
+        return true;
+    }
     bool cut(const std::function<bool(const SegmentCut&)>& on_cut, uint64_t end_time_ms, const char* reason, bool has_sil, uint64_t sil_ms) {
         if (speech_buffer_.empty()) return true;   // lib.rs:589-591
         SegmentCut c; c.samples.swap(speech_buffer_); speech_buffer_.clear(); c.start_time_ms = segment_start_time_ms_; c.end_time_ms = end_time_ms; c.reason = reason;
@@ -210,6 +252,7 @@ private:
     }
     float threshold_ = 0.5f, max_secs_ = 30.0f; size_t silence_threshold_frames_ = 21;
     std::deque<float> frame_buffer_; std::vector<float> speech_buffer_;
+    size_t batch_frames_ = 1; std::deque<float> judged_samples_; std::deque<Judged> judged_; std::vector<float> eval_, probs_;
     uint64_t segment_start_time_ms_ = 0, segment_counter_ = 0, absolute_time_ms_ = 0; std::string current_segment_id_; size_t silence_frame_count_ = 0;
 };
 

@@ -6,7 +6,9 @@
 //                                   state [2, 1, 128] (h, c) carried between calls, sr = 16000; returns the speech probability;
 //                                   context <- last 64 samples of the frame
 //   :139-142 reset               -> SileroVad::reset
-// It is sequential per stream (an LSTM, ~31 calls per audio-second, ~0.4 MFLOP each) and is therefore CPU code by design.
+// SileroVad is the gate as the plugin runs it by default: libm arithmetic, one frame at a time on the CPU.  SileroContractVad
+// (below) evaluates the same network in the arithmetic of include/skw_silero_net.h, which the HIP kernels of skw_vad_gpu.hip
+// reproduce bit for bit: only W_hh.h and the gate non-linearities are sequential per stream, the rest is parallel over frames.
 //
 // The ONNX runtime and the model file are third-party and absent offline (parity unpinned).  What is restated here
 // is the published Silero v5 graph as recalled: reflect-pad 64 on the right -> STFT as a strided Conv1d with the stored basis
@@ -26,6 +28,7 @@
 #include <memory>
 #include <string>
 #include <vector>
+#include "../../include/skw_silero_net.h"
 
 namespace skw {
 namespace onnx {
@@ -222,6 +225,9 @@ public:
     void reset() { memset(h_, 0, sizeof h_); memset(c_, 0, sizeof c_); memset(ctx_, 0, sizeof ctx_); }
     const float* state_h() const { return h_; }
     const float* state_c() const { return c_; }
+    // the 320-float state block of include/skw_vad_batch.h: context[64], h[128], c[128]
+    void get_state(float* out320) const { memcpy(out320, ctx_, sizeof ctx_); memcpy(out320 + 64, h_, sizeof h_); memcpy(out320 + 192, c_, sizeof c_); }
+    void set_state(const float* in320) { memcpy(ctx_, in320, sizeof ctx_); memcpy(h_, in320 + 64, sizeof h_); memcpy(c_, in320 + 192, sizeof c_); }
     float process_chunk(const float* audio512) {
         const SileroWeights& w = *w_;
         float x[640];
@@ -269,6 +275,52 @@ private:
     static float sigm(float v) { return 1.0f / (1.0f + expf(-v)); }
     std::shared_ptr<const SileroWeights> w_;
     float h_[128], c_[128], hn_[128], ctx_[64];
+};
+
+// The same network in the contract arithmetic (include/skw_silero_net.h is the specification; this class only sequences its
+// functions).  Same call contract and state block as SileroVad, so a stream can move between the two evaluators, and between
+// this one and the GPU (skw_vad_gpu_process), at any frame.
+#if defined(__x86_64__) && defined(__GNUC__) && !defined(__clang__)
+#define SKW_SILERO_FMA_CLONES __attribute__((target_clones("fma", "default"), flatten))   // __builtin_fmaf as one instruction where the CPU has it; same bits either way
+#else
+#define SKW_SILERO_FMA_CLONES
+#endif
+struct SileroTaps { float mag[129 * 4], c1[128 * 4], c2[64 * 2], c3[64], c4[128], gin[512]; };   // the feed-forward half of one frame
+class SileroContractVad {
+public:
+    explicit SileroContractVad(std::shared_ptr<const SileroWeights> w) : w_(std::move(w)) { reset(); }
+    void reset() { memset(st_, 0, sizeof st_); }
+    void get_state(float* out320) const { memcpy(out320, st_, sizeof st_); }
+    void set_state(const float* in320) { memcpy(st_, in320, sizeof st_); }
+    // everything that depends on the audio alone: window -> STFT magnitudes -> four conv blocks -> b_ih + W_ih.x
+    SKW_SILERO_FMA_CLONES void feed_forward(const float* ctx64, const float* audio512, SileroTaps* t) const {
+        const SileroWeights& w = *w_;
+        float x[640]; skw_silero_window(ctx64, audio512, x);
+        for (int fr = 0; fr < 4; ++fr) for (int bin = 0; bin < 129; ++bin) t->mag[bin * 4 + fr] = skw_silero_stft_mag(w.basis.data(), x, bin, fr);
+        const float* in[4] = {t->mag, t->c1, t->c2, t->c3}; float* out[4] = {t->c1, t->c2, t->c3, t->c4};
+        int T = 4;
+        for (int l = 0; l < 4; ++l) {
+            const int ci = SILERO_CI[l], co = SILERO_CO[l], st = SILERO_STRIDE[l], To = (T + 2 - 3) / st + 1;
+            for (int o = 0; o < co; ++o) for (int tt = 0; tt < To; ++tt) out[l][o * To + tt] = skw_silero_conv_relu(w.cw[l].data(), w.cb[l].data(), in[l], ci, T, st, o, tt);
+            T = To;
+        }
+        for (int r = 0; r < 512; ++r) t->gin[r] = skw_silero_dot128(w.b_ih[r], &w.w_ih[(size_t)r * 128], t->c4);
+    }
+    SKW_SILERO_FMA_CLONES float process_chunk(const float* audio512) {
+        const SileroWeights& w = *w_;
+        SileroTaps t; feed_forward(st_, audio512, &t);
+        float* h = st_ + 64; float* c = st_ + 192; float gates[512], hn[128];
+        for (int r = 0; r < 512; ++r) gates[r] = t.gin[r] + skw_silero_dot128(w.b_hh[r], &w.w_hh[(size_t)r * 128], h);
+        for (int j = 0; j < 128; ++j) hn[j] = skw_silero_cell(gates[j], gates[128 + j], gates[256 + j], gates[384 + j], &c[j]);
+        memcpy(h, hn, sizeof hn);
+        memcpy(st_, audio512 + 512 - 64, sizeof(float) * 64);
+        return skw_silero_output(w.ob, w.ow.data(), h);
+    }
+    void process_chunks(const float* frames, size_t n, float* probs) { for (size_t i = 0; i < n; ++i) probs[i] = process_chunk(frames + i * 512); }
+    const SileroWeights& weights() const { return *w_; }
+private:
+    std::shared_ptr<const SileroWeights> w_;
+    float st_[320];                                   // context[64], h[128], c[128]
 };
 
 }  // namespace skw

@@ -177,3 +177,43 @@ def segment_sim(prob, threshold=0.5, min_silence_ms=700, max_secs=30.0, max_cuts
     cuts = np.zeros((max_cuts, 6), dtype=np.int64)
     n = lib().mh_segment_sim(prob.ctypes.data, prob.size, threshold, min_silence_ms, max_secs, cuts.ctypes.data, max_cuts)
     return cuts[:min(n, max_cuts)].tolist()
+
+
+class _SegRunParams(C.Structure):
+    _fields_ = [("batch_frames", C.c_int32), ("threshold", C.c_float), ("min_silence_ms", C.c_uint64), ("max_secs", C.c_float),
+                ("script", C.c_void_p), ("silero_path", C.c_char_p), ("swap_at_sample", C.c_int64),
+                ("swap_threshold", C.c_float), ("swap_batch_frames", C.c_int32), ("swap_gate", C.c_int32), ("swap_script", C.c_void_p),
+                ("abort_cut", C.c_int32), ("flush", C.c_int32)]
+
+
+SEG_EVENT_KINDS = ("start", "cut", "tail", "refused_cut", "end")
+
+
+def segment_run(samples, packets, batch_frames=1, threshold=0.5, min_silence_ms=700, max_secs=30.0, script=None, silero_path=None,
+                swap_at_sample=-1, swap_threshold=None, swap_batch_frames=0, swap_gate=False, swap_script=None, abort_cut=-1, flush=1, max_events=4096):
+    """Drives skw::Segmenter the way the Whisper node does (mh_segment_run): `samples` cut into `packets`, the gate asked for `batch_frames` frames per call;
+    gate = script (probability per frame) or the Silero contract gate over silero_path.  Returns a list of dicts (kind, start_ms, end_ms, samples, reason,
+    silence_ms, counter, extra, packet); the last one (kind "end") carries the segmenter's closing counters."""
+    samples = np.ascontiguousarray(samples, np.float32)
+    packets = np.ascontiguousarray(packets, np.int64)
+    keep = []
+    def arr(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.float32); keep.append(a)
+        return a.ctypes.data
+    p = _SegRunParams(batch_frames, threshold, min_silence_ms, max_secs, arr(script), os.fsencode(silero_path) if silero_path else None, swap_at_sample,
+                      threshold if swap_threshold is None else swap_threshold, swap_batch_frames, 1 if swap_gate else 0, arr(swap_script), abort_cut, flush)
+    ev = np.zeros((max_events, 9), np.int64)
+    err = C.create_string_buffer(512)
+    f = lib().mh_segment_run
+    f.argtypes = [C.POINTER(_SegRunParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
+    n = f(C.byref(p), samples.ctypes.data, samples.size, packets.ctypes.data, packets.size, ev.ctypes.data, max_events, err, 512)
+    if n < 0:
+        raise RuntimeError(err.value.decode(errors="replace"))
+    assert n <= max_events
+    keys = ("kind", "start_ms", "end_ms", "samples", "reason", "silence_ms", "counter", "extra", "packet")
+    out = [dict(zip(keys, row)) for row in ev[:n].tolist()]
+    for e in out:
+        e["kind"] = SEG_EVENT_KINDS[e["kind"]]
+    return out

@@ -9,7 +9,12 @@ the STFT basis is a real Hann-windowed DFT, the convolutions average non-negativ
 gates open on loud frames and its forget gate stays shut — probability ~0.02 on silence, ~0.99 on tones above ~-30 dBFS —
 with a seeded perturbation on every tensor so that all of them matter to the result.
 
-usage: make_synth_silero.py OUT.onnx [--seed N] [--lstm-op]     (--lstm-op stores W/R/B of an ONNX LSTM operator, gate order iofc)
+--random-lstm replaces the engineered LSTM and output layer by seeded random ones whose forget gate stays OPEN (bias +1) and
+whose recurrent weights are large enough to matter: on that file the carried h and c shape every later probability, and the
+probabilities wander through the middle of the range, so an evaluator that mishandles the carry cannot agree with one that does
+not.  (On the default file the cell state barely matters, by design.)
+
+usage: make_synth_silero.py OUT.onnx [--seed N] [--lstm-op] [--random-lstm]     (--lstm-op stores W/R/B of an ONNX LSTM operator, gate order iofc)
 """
 import struct
 import sys
@@ -73,7 +78,7 @@ def graph(name, nodes, initializers, inputs=(), outputs=()):
             b"".join(ld(11, value_info(i)) for i in inputs) + b"".join(ld(12, value_info(o)) for o in outputs))
 
 
-def weights_16k(seed):
+def weights_16k(seed, random_lstm=False):
     rng = np.random.default_rng(seed)
     k = np.arange(256)
     hann = 0.5 - 0.5 * np.cos(2 * np.pi * k / 256)
@@ -98,6 +103,19 @@ def weights_16k(seed):
     w["decoder.rnn.bias_hh"] = b_hh.astype(np.float32)
     w["decoder.decoder.2.weight"] = (0.1 + rng.normal(0, 0.01, (1, 128, 1))).astype(np.float32)
     w["decoder.decoder.2.bias"] = np.array([-4.0], np.float32)
+    if random_lstm:
+        r2 = np.random.default_rng(seed + 77)
+        # conv3 features are ~0.3 x the tone amplitude and all positive: sigma 3 puts the input half of the gates at a few units on loud frames
+        w_ih = r2.normal(0, 3.0, (512, 128))
+        w_ih[128:256] *= 0.1                                                 # ... and the forget gate near its bias, so that c stays within a few units
+        w["decoder.rnn.weight_ih"] = w_ih.astype(np.float32)
+        w["decoder.rnn.weight_hh"] = r2.normal(0, 0.15, (512, 128)).astype(np.float32)
+        b = r2.normal(0, 0.3, 512)
+        b[128:256] += 1.0                                                    # forget gate open (~0.7): c carries over
+        w["decoder.rnn.bias_ih"] = b.astype(np.float32)
+        w["decoder.rnn.bias_hh"] = r2.normal(0, 0.3, 512).astype(np.float32)
+        w["decoder.decoder.2.weight"] = r2.normal(0, 0.3, (1, 128, 1)).astype(np.float32)
+        w["decoder.decoder.2.bias"] = np.array([0.4], np.float32)
     return w
 
 
@@ -139,8 +157,8 @@ def branch(prefix, w):
     return graph(prefix + "graph", nodes, inits, outputs=[prefix + "out"])
 
 
-def build(seed=1234, lstm_op=False):
-    w16, w8 = weights_16k(seed), weights_8k(seed)
+def build(seed=1234, lstm_op=False, random_lstm=False):
+    w16, w8 = weights_16k(seed, random_lstm), weights_8k(seed)
     if lstm_op:
         w16, w8 = to_lstm_op(w16), to_lstm_op(w8)
     g8 = branch("If_0_else_branch__Inline_0__", w8)
@@ -156,7 +174,7 @@ def build(seed=1234, lstm_op=False):
 if __name__ == "__main__":
     out = sys.argv[1]
     seed = int(sys.argv[sys.argv.index("--seed") + 1]) if "--seed" in sys.argv else 1234
-    data, _ = build(seed, "--lstm-op" in sys.argv)
+    data, _ = build(seed, "--lstm-op" in sys.argv, "--random-lstm" in sys.argv)
     with open(out, "wb") as f:
         f.write(data)
     print("wrote %s (%d bytes)" % (out, len(data)))
