@@ -54,6 +54,11 @@ typedef struct {
     float   temperature;      /* whisper_full_params.temperature, default 0.0: the first pass of a window is greedy argmax */
     float   temperature_inc;  /* default 0.2: a window that fails (entropy / logprob / repetition rules) is decoded again at +0.2 .. 1.0,
                                  sampling with std::discrete_distribution semantics from a per-clip std::mt19937(0); <= 0 disables the ladder */
+    int32_t audio_ctx;        /* whisper_full_params.audio_ctx (last field; the struct grew by four bytes with it): 0 = the model's n_audio_ctx (the default: today's behaviour, bit for bit);
+                                 K in 1 .. n_audio_ctx: every window of the clip is encoded and attended over K positions — the conv stem sees mel frames [seek, seek + 2 K) and zeros
+                                 beyond, the positional embedding is its first K rows, encoder, cross K / V and the decoder's cross attention have K positions.  What the host decides
+                                 (seek advance, the 30 s window, segment assembly, the 0.02 s timestamp precision behind max_initial_ts) stays on the model's constants.  Per clip in
+                                 skw_full_batch_mixed.  Outside [0, n_audio_ctx]: the call fails, naming the clip.  With lang_id < 0 the detection pass uses the same K. */
 } skw_full_params;
 
 typedef struct {
@@ -122,6 +127,9 @@ int skw_ctx_set_precision(skw_ctx*, int precision);   /* 0 on success; takes eff
 int skw_ctx_get_precision(const skw_ctx*);
 
 void skw_full_default_params(skw_full_params*);
+/* The "auto" rule for skw_full_params.audio_ctx, stated once: clips of at least 480 000 samples (30 s) get n_audio_ctx; shorter ones
+ * min(n_audio_ctx, 32 * ceil((ceil(n_samples / 320) + 25) / 32)) — the 20 ms positions the audio covers, half a second of margin, whole 32-key blocks.  Needs no device. */
+int  skw_audio_ctx_for_samples(int n_samples, int n_audio_ctx);
 
 /* ---- the hot path ---- */
 /* pcm[i]: 16 kHz mono f32, n_samples[i] samples; host pointers (pcm_on_device = 0) or device pointers (= 1).
@@ -184,6 +192,8 @@ int  skw_ctx_profile_get(skw_ctx*, int cls, char* name, size_t name_len, long* c
  * summed live rows (a launch's algorithmic bytes = 4 B x live rows x n_audio_ctx x n_text_state), shortest / longest launch, the clock's rate in kHz.  Diagnostic; off by default. */
 int  skw_ctx_kernel_clock(skw_ctx*, int on);
 int  skw_ctx_kernel_clock_get(skw_ctx*, long* launches, double* sum_us, double* sum_live_rows, double* min_us, double* max_us, int* clock_khz);
+/* the keys those launches walked, summed over their live rows: with per-clip audio contexts a launch's algorithmic bytes are 4 B x (its rows' walked keys) x n_text_state */
+int  skw_ctx_kernel_clock_keys(skw_ctx*, double* sum_keys);
 /* every recorded launch as (begin us, end us, live rows), relative to the earliest begin; returns the count written.  Row groups run on their own streams, so launches overlap:
  * the union of the intervals is the time the kernel was in flight at all. */
 long skw_ctx_kernel_clock_records(skw_ctx*, double* out /* [cap][3] */, long cap);
@@ -197,7 +207,10 @@ int skw_log_mel(skw_ctx*, const float* pcm_host, int n_samples, float* mel_out, 
 int skw_conv_stem(skw_ctx*, const float* pcm_host, int n_samples, int seek, float* x0);
 /* K2-K6: encoder output (after ln_post) [n_audio_ctx][n_state] f32 and, when non-null, cross K/V [n_text_layer][n_audio_ctx][n_state] f32 */
 int skw_encode(skw_ctx*, const float* pcm_host, int n_samples, int seek, float* enc_out, float* cross_k, float* cross_v);
-/* K7-K10: after skw_encode, run the decoder on tokens[0..n) from position 0 and return the last token's logits [n_vocab] */
+/* the same taps at an audio context of K = audio_ctx positions (0 = n_audio_ctx): x0 [K][n_state]; enc_out [K][n_state], cross K/V [n_text_layer][K][n_state] */
+int skw_conv_stem_actx(skw_ctx*, const float* pcm_host, int n_samples, int seek, int audio_ctx, float* x0);
+int skw_encode_actx(skw_ctx*, const float* pcm_host, int n_samples, int seek, int audio_ctx, float* enc_out, float* cross_k, float* cross_v);
+/* K7-K10: after skw_encode / skw_encode_actx (whose K it follows), run the decoder on tokens[0..n) from position 0 and return the last token's logits [n_vocab] */
 int skw_decode_logits(skw_ctx*, const int32_t* tokens, int n_tokens, float* logits);
 
 /* ---- resampler front end: the arithmetic of the reference's audio::resampler node on the GPU ----

@@ -405,6 +405,12 @@ extern "C" const char* skw_model_token_text(const skw_model* m, int id, int* len
     if (id < 0 || id >= m->hp.n_vocab) { if (len) *len = 0; return ""; }
     if (len) *len = (int)m->tok_str[id].size(); return m->tok_str[id].c_str();
 }
+// the "auto" audio context of a clip: the positions its audio covers (20 ms each), half a second of margin, whole 32-key blocks — never more than the model's context
+extern "C" int skw_audio_ctx_for_samples(int n_samples, int n_audio_ctx) {
+    if (n_samples >= WHISPER_SAMPLE_RATE * WHISPER_CHUNK_SIZE) return n_audio_ctx;
+    const int pos = ((n_samples > 0 ? n_samples : 0) + 319) / 320;
+    return std::min(n_audio_ctx, 32 * ((pos + 25 + 31) / 32));
+}
 extern "C" void skw_full_default_params(skw_full_params* p) {
     memset(p, 0, sizeof *p); p->lang_id = 0; p->suppress_blank = 1; p->suppress_nst = 0; p->max_initial_ts = 1.0f; p->entropy_thold = 2.4f; p->logprob_thold = -1.0f; p->no_speech_thold = 0.6f;
     p->temperature = 0.0f; p->temperature_inc = 0.2f;
@@ -466,12 +472,17 @@ struct skw_ctx {
     hipStream_t stream = nullptr; hipEvent_t ev[6] = {};
     hipStream_t cur = nullptr;                       // stream the launch helpers enqueue on (== stream outside the decode groups)
     static const int MAX_GROUPS = 8; hipStream_t gstream[MAX_GROUPS] = {}; hipEvent_t gev[MAX_GROUPS] = {}; int n_groups = 1;
-    struct StepGraph { int g, r0, n, precision, ln_stats, kclk; unsigned sw_epoch; SkwLogitParams lp; int rows; hipGraphExec_t exec; }; std::vector<StepGraph> step_graphs; int use_graphs = 1;
+    struct StepGraph { int g, r0, n, precision, ln_stats, kclk, var_k; unsigned sw_epoch; SkwLogitParams lp; int rows; hipGraphExec_t exec; }; std::vector<StepGraph> step_graphs; int use_graphs = 1;
     char errbuf[512] = {0};
     std::vector<void*> allocs;
     // front end
     float* pcm = nullptr; long* pcm_off = nullptr; int* n_samples = nullptr; int* n_len = nullptr; float* mel = nullptr; float* clip_max = nullptr;
     int *clip_idx = nullptr, *seek = nullptr;
+    // per-clip audio context (skw_full_params.audio_ctx): slot_k[slot] = the positions of the window in that slot, travelling with clip_idx / seek.  var_k: some slot of the
+    // current pass is shorter than n_audio_ctx — the attention kernels then take their extents from slot_k / SkwSeqState.n_keys (device memory); otherwise the launches are today's.
+    // enc_rows: rows per slot of the encoder's activations in the last pass (dense: the largest K of the pass, rounded — enc_rows_for); h1_T: the conv1 rows per slot whose pad
+    // rows are currently zero in h1
+    int* slot_k = nullptr; bool var_k = false; int enc_rows = 0, h1_T = 0;
     half_t* im2col = nullptr; half_t* h1 = nullptr;
     // encoder
     float* x = nullptr; half_t* y16 = nullptr; half_t *Qh = nullptr, *Kh = nullptr, *Vt = nullptr; half_t* hbuf = nullptr; float* enc_out32 = nullptr;
@@ -537,7 +548,7 @@ extern "C" skw_ctx* skw_ctx_create(skw_model* m, int max_batch, int max_samples,
     c->max_samples = max_samples;
     c->n_len_max = (max_samples + WHISPER_SAMPLE_RATE * 30 + 2 * (WHISPER_N_FFT / 2) - WHISPER_N_FFT) / WHISPER_HOP + 1;
     const skw_hparams& hp = m->hp; const int B = max_batch, nc = hp.n_audio_ctx, T = 2 * nc, d = hp.n_audio_state, dt = hp.n_text_state;
-    c->Tpad = (nc + 31) & ~31;
+    c->Tpad = (nc + 31) & ~31; c->enc_rows = nc; c->h1_T = T;
     c->kv_frag_on = skw_sw(SW_XATTN_FRAG) != 0;
     bool ok = true;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) ok = false;
@@ -573,6 +584,7 @@ extern "C" skw_ctx* skw_ctx_create(skw_model* m, int max_batch, int max_samples,
     want("clip_max", c->clip_max, B, false);
     want("clip_idx", c->clip_idx, B, false);
     want("seek", c->seek, B, false);
+    want("slot_k", c->slot_k, B, true);
     want("row_tok", c->row_tok, B, true);
     want("prompt_buf", c->prompt_buf, (size_t)B * SKW_PROMPT_CAP, true);
     want("im2col", c->im2col, (size_t)B * T * c->m->conv1.k_pad, false);
@@ -805,9 +817,29 @@ static void run_mel(skw_ctx* c, int n) {
 // conv stem for Bw window slots (clip_idx/seek on device) -> c->x [Bw*nc][d]
 // row0: the first window slot to compute (slots before it keep what they hold: temperature retries, see skw_full_batch); the stem's
 // buffers are scratch, so the Bw - row0 computed windows sit at their start
-static void run_conv(skw_ctx* c, int Bw_all, int row0 = 0) {
-    skw_model* m = c->m; const int nc = m->hp.n_audio_ctx, T = 2 * nc, d = m->hp.n_audio_state; const int Bw = Bw_all - row0;
-    skw_mel_im2col(c->mel, c->clip_idx + row0, c->seek + row0, c->n_len, Bw, c->n_len_max, m->hp.n_mels, T, m->conv1.k_pad, c->im2col, c->stream);
+// Per-clip audio context: the rows a slot's activations take in the encoder pass.  GEMMs are row-wise, so a pass whose longest window has kmax positions runs over Bw x enc_rows
+// rows instead of Bw x n_audio_ctx: kmax rounded to whole 32-key blocks and to at least 256 — the f16 GEMMs' per-clip epilogues step from one slot to the next at most once
+// per 256-row tile.  A slot's rows past its own K are don't-care: computed from zero mel frames, read by nothing.
+static int enc_rows_for(const skw_ctx* c, int kmax) {
+    const int nc = c->m->hp.n_audio_ctx;
+    return kmax >= nc ? nc : std::min(nc, std::max(256, (kmax + 31) & ~31));
+}
+// K of every slot of the pass about to run -> device; returns the rows per slot for run_conv / run_encoder (windows row0 .. are computed)
+static int set_slot_k(skw_ctx* c, const int* ks, int Bw, int row0, hipStream_t s) {
+    const int nc = c->m->hp.n_audio_ctx; int kmax = 1; bool var = false;
+    for (int j = 0; j < Bw; ++j) { var = var || ks[j] < nc; if (j >= row0) kmax = std::max(kmax, ks[j]); }
+    c->var_k = var;
+    (void)hipMemcpyAsync(c->slot_k, ks, sizeof(int) * Bw, hipMemcpyHostToDevice, s);      // (callers keep ks alive until the stream is synchronised)
+    return enc_rows_for(c, kmax);
+}
+static void run_conv(skw_ctx* c, int Bw_all, int row0 = 0, int rows = 0) {
+    skw_model* m = c->m; const int nc = rows > 0 ? rows : m->hp.n_audio_ctx, T = 2 * nc, d = m->hp.n_audio_state; const int Bw = Bw_all - row0;
+    if (T != c->h1_T) {      // h1 is [slot][T + 2 rows]: the zero row in front of every slot's block moves with T (conv2's first output reads it; the row behind the block is read by nothing)
+        (void)hipMemset2DAsync(c->h1, (size_t)(T + 2) * d * sizeof(half_t), 0, (size_t)d * sizeof(half_t), c->max_batch, c->stream);
+        c->h1_T = T;
+    }
+    c->enc_rows = nc;
+    skw_mel_im2col(c->mel, c->clip_idx + row0, c->seek + row0, c->n_len, Bw, c->n_len_max, m->hp.n_mels, T, m->conv1.k_pad, c->im2col, c->stream, c->var_k ? c->slot_k + row0 : nullptr);
     SkwGemmArgs a = gemm_args(c->im2col, m->conv1.k_pad, m->conv1, Bw * T, c->h1, d, EPI_GELU_F16_KPERM_ROWPAD); a.gelu_tab = m->gelu_tab; a.n_ctx = T;
     GEMM(c, a, m->conv1.n_in);
     SkwGemmArgs b = gemm_args(c->h1, 2L * d, m->conv2, Bw * nc, c->x, d, EPI_CONV2); b.a_rows_per_batch = nc; b.a_batch_stride = (long)(T + 2) * d;
@@ -815,8 +847,13 @@ static void run_conv(skw_ctx* c, int Bw_all, int row0 = 0) {
     GEMM(c, b, m->conv2.n_in);
 }
 // encoder blocks + ln_post (+ cross K/V) over Bw windows; input c->x
-static void run_encoder(skw_ctx* c, int Bw_all, bool want_f32_out, bool cross, int row0 = 0) {
-    skw_model* m = c->m; const skw_hparams& hp = m->hp; const int nc = hp.n_audio_ctx, d = hp.n_audio_state, H = hp.n_audio_head; const int Bw = Bw_all - row0, M = Bw * nc;
+// rows: rows per slot of the activations (enc_rows_for; 0: n_audio_ctx).  Strides of Qh / Kh / Vt and of cross K / V stay those of the full context
+static void run_encoder(skw_ctx* c, int Bw_all, bool want_f32_out, bool cross, int row0 = 0, int rows = 0) {
+    skw_model* m = c->m; const skw_hparams& hp = m->hp; const int nc = rows > 0 ? rows : hp.n_audio_ctx, d = hp.n_audio_state, H = hp.n_audio_head; const int Bw = Bw_all - row0, M = Bw * nc;
+    const int* sk_dev = c->var_k ? c->slot_k + row0 : nullptr;      // per-slot keys / queries of the attention (null: every slot is full length, today's launches)
+    c->enc_rows = nc;
+    // cross K as rows (exact precision, q8, SKW_XATTN_FRAG=0): a slot's rows are n_audio_ctx apart in the buffer whatever `rows` is, so a shortened pass writes slot by slot
+    const bool ck_per_slot = nc != hp.n_audio_ctx && Bw > 1 && !c->kv_frag();
     const size_t xk0 = (size_t)row0 * c->kclip(), xv0 = (size_t)row0 * hp.n_text_head * 64 * c->Tpad;      // cross K / V of the computed windows land in slots row0 ..
     if (use_q8(c)) {
         // Quantised file, exact precision: every weight product is ggml's (rows -> q8 blocks, integer block dots), so what feeds a
@@ -829,7 +866,7 @@ static void run_encoder(skw_ctx* c, int Bw_all, bool want_f32_out, bool cross, i
             { SkwGemmArgs a = q8_args(M, c->Kh, 0, EPI_HEADS_F16); a.n_ctx = nc; a.H = H; a.Tpad = c->Tpad; Q8_GEMM(c, a, L.k, 0); }
             { SkwGemmArgs a = q8_args(M, c->Vt, 0, EPI_VT_F16); a.n_ctx = nc; a.H = H; a.Tpad = c->Tpad; Q8_GEMM(c, a, L.v, 0); }
             { ProfScope p_(c, PC_ATTN_ENC, 4.0 * Bw * H * (double)nc * nc * 64, 2.0 * 4 * M * d);
-              skw_attn_encoder(c->Qh, c->Kh, c->Vt, (half_t*)c->y32, d, Bw, H, nc, c->Tpad, c->stream, nullptr, nullptr, 1); }
+              skw_attn_encoder(c->Qh, c->Kh, c->Vt, (half_t*)c->y32, d, Bw, H, nc, c->Tpad, c->stream, nullptr, nullptr, 1, sk_dev, nc); }
             Q8_ROWS(c, c->y32, d, M, d, 0);
             { SkwGemmArgs a = q8_args(M, c->x, d, EPI_F32); a.res = c->x; a.ldres = d; Q8_GEMM(c, a, L.o, 0); }
             Q8_LN(c, c->x, M, d, L.mlp_ln, 0, c->y32);
@@ -845,8 +882,17 @@ static void run_encoder(skw_ctx* c, int Bw_all, bool want_f32_out, bool cross, i
             for (int l = 0; l < hp.n_text_layer; ++l) {
                 const DecLayer& L = m->dec[l];
                 half_t* ck = c->crossK + (size_t)l * c->max_batch * c->kclip() + xk0; half_t* cv = c->crossV + (size_t)l * c->max_batch * hp.n_text_head * 64 * c->Tpad + xv0;
-                { SkwGemmArgs a = q8_args(M, ck, dt, EPI_F16_PLAIN); a.scale = Kscale; a.has_scale = 1; Q8_GEMM(c, a, L.ck, 0); }
+                if (!ck_per_slot) { SkwGemmArgs a = q8_args(M, ck, dt, EPI_F16_PLAIN); a.scale = Kscale; a.has_scale = 1; Q8_GEMM(c, a, L.ck, 0); }
                 { SkwGemmArgs a = q8_args(M, cv, 0, EPI_VT_F16); a.n_ctx = nc; a.H = hp.n_text_head; a.Tpad = c->Tpad; Q8_GEMM(c, a, L.cv, 0); }
+            }
+            // a shortened pass: cross K slot by slot.  The q8 blocks' scales are stored [block][row of the launch], so a slot's rows are quantised again as a launch of their own
+            // (row-wise: the same blocks)
+            for (int j = 0; ck_per_slot && j < Bw; ++j) {
+                Q8_ROWS(c, c->encq32 + (size_t)j * nc * d, d, nc, d, 0);
+                for (int l = 0; l < hp.n_text_layer; ++l) {
+                    half_t* ck = c->crossK + (size_t)l * c->max_batch * c->kclip() + xk0 + (size_t)j * c->kclip();
+                    SkwGemmArgs a = q8_args(nc, ck, dt, EPI_F16_PLAIN); a.scale = Kscale; a.has_scale = 1; Q8_GEMM(c, a, m->dec[l].ck, 0);
+                }
             }
         }
         c->last_enc_B = Bw_all;
@@ -871,8 +917,8 @@ static void run_encoder(skw_ctx* c, int Bw_all, bool want_f32_out, bool cross, i
         float* dbg2 = nullptr;
         if (dbg) { hipMalloc((void**)&dbg2, sizeof(float) * 64 * c->Tpad); hipMemset(dbg2, 0, sizeof(float) * 64 * c->Tpad); }
         { ProfScope p_(c, PC_ATTN_ENC, 4.0 * Bw * H * (double)nc * nc * 64, 2.0 * 4 * M * d);
-          if (c->precision == SKW_PRECISION_F16_MFMA && !dbg) skw_attn_encoder16(c->Qh, c->Kh, c->Vt, c->y16, d, Bw, H, nc, c->Tpad, c->stream);
-          else skw_attn_encoder(c->Qh, c->Kh, c->Vt, c->y16, d, Bw, H, nc, c->Tpad, c->stream, dbg, dbg2); }
+          if (c->precision == SKW_PRECISION_F16_MFMA && !dbg) skw_attn_encoder16(c->Qh, c->Kh, c->Vt, c->y16, d, Bw, H, nc, c->Tpad, c->stream, sk_dev, nc);
+          else skw_attn_encoder(c->Qh, c->Kh, c->Vt, c->y16, d, Bw, H, nc, c->Tpad, c->stream, dbg, dbg2, 0, sk_dev, nc); }
         if (dbg2) { tap(c, "l0.SP", dbg2, 64, c->Tpad, TAP_F32); hipFree(dbg2); }
         if (dbg) { tap(c, "l0.att32", dbg, nc, d, TAP_F32); tap(c, "l0.rmax", dbg + (size_t)nc * d, H, nc, TAP_F32);
         tap(c, "l0.rinv", dbg + (size_t)nc * d + (size_t)H * nc, H, nc, TAP_F32); hipFree(dbg); }
@@ -892,8 +938,11 @@ static void run_encoder(skw_ctx* c, int Bw_all, bool want_f32_out, bool cross, i
         for (int l = 0; l < hp.n_text_layer; ++l) {
             const DecLayer& L = m->dec[l];
             half_t* ck = c->crossK + (size_t)l * c->max_batch * c->kclip() + xk0; half_t* cv = c->crossV + (size_t)l * c->max_batch * hp.n_text_head * 64 * c->Tpad + xv0;
-            { SkwGemmArgs a = gemm_args(c->y16, d, L.ck, M, ck, dt, EPI_F16_PLAIN); a.scale = Kscale; a.has_scale = 1; if (c->kv_frag()) { a.frag = 1;
-            a.n_ctx = nc; a.H = hp.n_text_head; a.Tpad = c->Tpad; } GEMM(c, a, d); }
+            for (int j = 0; j < (ck_per_slot ? Bw : 1); ++j) {
+                SkwGemmArgs a = gemm_args(c->y16 + (size_t)j * nc * d, d, L.ck, ck_per_slot ? nc : M, ck + (size_t)j * c->kclip(), dt, EPI_F16_PLAIN); a.scale = Kscale; a.has_scale = 1;
+                if (c->kv_frag()) { a.frag = 1; a.n_ctx = nc; a.H = hp.n_text_head; a.Tpad = c->Tpad; }
+                GEMM(c, a, d);
+            }
             { // cross V^T through the operand-swapped product (rows = features, columns = tokens), as for the encoder's V
                 SkwGemmArgs a{}; a.A = L.cv.w; a.lda = L.cv.k_pad; a.W = c->y16; a.ldw = d; a.M = L.cv.n_out; a.N = M; a.K = L.cv.k_pad; a.C = cv;
                 a.bias = L.cv.b; a.epi = EPI_VT_F16; a.n_ctx = nc; a.H = hp.n_text_head; a.Tpad = c->Tpad; a.scale = 1.0f;
@@ -906,7 +955,10 @@ static void run_encoder(skw_ctx* c, int Bw_all, bool want_f32_out, bool cross, i
 }
 
 // one decoder step for Bw sequences: token/pos taken from the device state; logits computed when want_logits
-__global__ void k_set_tokens(SkwSeqState* st, int tok, int pos) { st[blockIdx.x].cur_token = tok; st[blockIdx.x].cur_pos = pos; st[blockIdx.x].active = 1; }
+// slot_k: the rows' cross-attention key counts (row i decodes window slot i)
+__global__ void k_set_tokens(SkwSeqState* st, int tok, int pos, const int* slot_k) {
+    st[blockIdx.x].cur_token = tok; st[blockIdx.x].cur_pos = pos; st[blockIdx.x].active = 1; st[blockIdx.x].n_keys = slot_k[blockIdx.x];
+}
 // whisper_lang_auto_detect_with_state: the language whose token has the largest logit after the [sot] step (lowest id on a tie)
 __global__ void k_lang_argmax(const float* logits, int n_vocab, int tok_sot, int n_lang, int* out) {
     const float* lg = logits + (long)blockIdx.x * n_vocab; float bv = -INFINITY; int bi = 0x7fffffff;
@@ -926,6 +978,8 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
     const int* seqp = prefill ? &st[0].pad : nullptr;                                  // row -> sequence for the attention kernels
     // where the QKV epilogue appends a row's K / V: absolute cache row (prefill) or position inside the row's own cache
     const int* kvpos = prefill ? &st[0].seek : &st[0].cur_pos;
+    // per-clip audio context: the rows' key counts sit next to `active` in device memory, so a captured step holds none; null while every slot is full length (today's launches)
+    const int* nkeys = c->var_k ? &st[0].n_keys : nullptr;
     const long kv_ld = prefill ? 0 : (long)ntc * dt;
     if (use_q8(c)) {   // quantised file, exact precision: ggml's arithmetic (see run_encoder); the row group's q8 scratch starts at its first row
         float* dy32 = c->dy32 + (size_t)r0 * dt; float* datt32 = c->datt32 + (size_t)r0 * dt; float* dh32 = c->dh32 + (size_t)r0 * 4 * dt;
@@ -944,7 +998,7 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
             Q8_LN(c, dx, Bw, dt, L.cross_ln, r0, dy32);
             { SkwGemmArgs a = q8_args(Bw, dq16, dt, EPI_F16_PLAIN); a.scale = KQscale; a.has_scale = 1; Q8_GEMM(c, a, L.cq, r0, true); }
             { ProfScope p_(c, PC_DEC_XATTN, 4.0 * live * (double)nc * dt, 4.0 * live * (double)nc * dt);
-            skw_dec_cross_attn_vt(dq16, ck, cv, Bw, H, dt, nc, c->Tpad, (half_t*)datt32, &st[0].active, s, 1, 0, seqp); }
+            skw_dec_cross_attn_vt(dq16, ck, cv, Bw, H, dt, nc, c->Tpad, (half_t*)datt32, &st[0].active, s, 1, 0, seqp, nullptr, nullptr, 0, nullptr, nkeys); }
             Q8_ROWS(c, datt32, dt, Bw, dt, r0);
             { SkwGemmArgs a = q8_args(Bw, dx, dt, EPI_F32); a.res = dx; a.ldres = dt; Q8_GEMM(c, a, L.co, r0, true); }
             Q8_LN(c, dx, Bw, dt, L.mlp_ln, r0, dy32);
@@ -1012,11 +1066,12 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
                 // the prompt pass in the tolerance precision: one read of a sequence's cross K / V^T for up to 128 of its prompt tokens (the encoder attention kernel with the
                 // prompt tokens as queries) instead of one per token — 4.6 MB per row per layer otherwise.  The exact precision keeps the single-query kernel: bit-identical to stepping.
                 ProfScope p_(c, PC_DEC_XATTN, 4.0 * Bw * (double)nc * 64.0 * H, 4.0 * c->pf_nseq * (double)nc * dt);
-                skw_xattn_prefill16(dq16, ck, cv, datt16, c->pf_nseq, c->pf_nq_max, c->pf_meta, c->pf_meta + c->max_batch, c->pf_meta + 2 * c->max_batch, H, dt, nc, c->Tpad, s, c->kv_frag(), xa_frag);
+                skw_xattn_prefill16(dq16, ck, cv, datt16, c->pf_nseq, c->pf_nq_max, c->pf_meta, c->pf_meta + c->max_batch, c->pf_meta + 2 * c->max_batch, H, dt, nc, c->Tpad, s, c->kv_frag(), xa_frag,
+                                    c->var_k ? c->slot_k : nullptr);
             } else
             { ProfScope p_(c, PC_DEC_XATTN, 4.0 * live * (double)nc * dt, 4.0 * live * (double)nc * dt, true);
             skw_dec_cross_attn_vt(dq16, ck, cv, Bw, H, dt, nc, c->Tpad, datt16, &st[0].active, s, 0, c->kv_frag() ? 2 : c->precision == SKW_PRECISION_F16_MFMA, seqp, p_.ev_a(), p_.ev_b(), xa_frag,
-                                  prefill ? nullptr : kclk_node(c, c->cur_group, l));
+                                  prefill ? nullptr : kclk_node(c, c->cur_group, l), nkeys);
             }
         }
         { SkwGemmArgs a = gemm_args(datt16, dt, L.co, Bw, dx, dt, EPI_F32); a.res = dx; a.ldres = dt; a.a_frag = xa_frag; gemm_s(a); }
@@ -1040,7 +1095,7 @@ static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogi
     for (size_t i = 0; i < c->step_graphs.size(); ++i) {
         auto& sg = c->step_graphs[i];
         if (sg.g == g && sg.r0 == r0 && sg.n == n && sg.precision == c->precision && sg.ln_stats == c->ln_stats_on && sg.kclk == c->kclk_on && sg.sw_epoch == skw_sw_epoch() &&
-            sg.rows == (int)rows && memcmp(&sg.lp, &lp, sizeof lp) == 0) {
+            sg.var_k == (int)c->var_k && sg.rows == (int)rows && memcmp(&sg.lp, &lp, sizeof lp) == 0) {
             if (i + 1 != c->step_graphs.size()) { auto hit = sg; c->step_graphs.erase(c->step_graphs.begin() + i); c->step_graphs.push_back(hit); }   // most recently used last
             return c->step_graphs.back().exec;
         }
@@ -1060,7 +1115,7 @@ static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogi
     if (exec) {
         // bounded: a long-lived server with ragged batches would otherwise keep one executable graph per (group, rows, params) forever
         if (c->step_graphs.size() >= 24) { hipGraphExecDestroy(c->step_graphs.front().exec); c->step_graphs.erase(c->step_graphs.begin()); }
-        skw_ctx::StepGraph sg; sg.g = g; sg.r0 = r0; sg.n = n; sg.precision = c->precision; sg.ln_stats = c->ln_stats_on; sg.kclk = c->kclk_on;
+        skw_ctx::StepGraph sg; sg.g = g; sg.r0 = r0; sg.n = n; sg.precision = c->precision; sg.ln_stats = c->ln_stats_on; sg.kclk = c->kclk_on; sg.var_k = (int)c->var_k;
          sg.sw_epoch = skw_sw_epoch(); sg.lp = lp; sg.rows = (int)rows; sg.exec = exec; c->step_graphs.push_back(sg);
     }
     return exec;
@@ -1192,6 +1247,9 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
     if (n_clips < 1 || n_clips > c->max_batch) { snprintf(errbuf, 512, "n_clips %d outside [1, %d]", n_clips, c->max_batch); return -1; }
     const bool mixed = pv != nullptr;
     auto P = [&](int ci) -> const skw_full_params& { return mixed ? pv[ci] : *p; };
+    for (int i = 0; i < n_clips; ++i) if (P(i).audio_ctx < 0 || P(i).audio_ctx > c->m->hp.n_audio_ctx) {
+        snprintf(errbuf, 512, "clip %d: audio_ctx %d outside [0, %d] (0 = the model's n_audio_ctx)", i, P(i).audio_ctx, c->m->hp.n_audio_ctx); return -3; }
+    auto K_of = [&](int ci) { return P(ci).audio_ctx > 0 ? P(ci).audio_ctx : c->m->hp.n_audio_ctx; };      // the clip's audio context, every window of it
     HIPCHK(hipSetDevice(c->m->device));
     const bool tracing = traces != nullptr;
     std::vector<int> f_cursor(n_clips, 0);      // tracing: decisions of clip i made so far (= its position in forced_ids[i])
@@ -1242,8 +1300,10 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
         if (Bd > 0) {
             HIPCHK(hipMemcpyAsync(c->clip_idx, act.data(), sizeof(int) * Bd, hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(c->seek, zero.data(), sizeof(int) * Bd, hipMemcpyHostToDevice, c->stream));
-            run_conv(c, Bd); run_encoder(c, Bd, false, true);
-            hipLaunchKernelGGL(k_set_tokens, dim3(Bd), dim3(1), 0, c->stream, c->st, m->tok_sot, 0);
+            std::vector<int> kd(Bd); for (int j = 0; j < Bd; ++j) kd[j] = K_of(act[j]);      // detection sees the first window as the clip's own audio_ctx shapes it
+            const int rows_d = set_slot_k(c, kd.data(), Bd, 0, c->stream);
+            run_conv(c, Bd, 0, rows_d); run_encoder(c, Bd, false, true, 0, rows_d);
+            hipLaunchKernelGGL(k_set_tokens, dim3(Bd), dim3(1), 0, c->stream, c->st, m->tok_sot, 0, c->slot_k);
             run_decoder_step(c, 0, Bd, 0, true, c->stream);
             hipLaunchKernelGGL(k_lang_argmax, dim3(Bd), dim3(64), 0, c->stream, c->logits, NV, m->tok_sot, m->n_lang, c->row_tok);
             std::vector<int> det(Bd); HIPCHK(hipMemcpyAsync(det.data(), c->row_tok, sizeof(int) * Bd, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
@@ -1276,6 +1336,9 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
         std::vector<int> sk(Bw); for (int j = 0; j < Bw; ++j) sk[j] = seek[act[j]];
         HIPCHK(hipMemcpyAsync(c->clip_idx, act.data(), sizeof(int) * Bw, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->seek, sk.data(), sizeof(int) * Bw, hipMemcpyHostToDevice, c->stream));
+        // the slots' audio contexts: a retried window (slots 0 .. R-1) keeps its clip's K with the cross K/V it moved
+        std::vector<int> ks(Bw); for (int j = 0; j < Bw; ++j) ks[j] = K_of(act[j]);
+        const int enc_rows = set_slot_k(c, ks.data(), Bw, R, c->stream);
         // per-row prompt: [prev] + the last n_text_ctx/2 tokens of the clip's prompt_past (passes at t < 0.5 only) + sot, language, task (, notimestamps)
         std::vector<int> pbuf((size_t)Bw * SKW_PROMPT_CAP, 0), np_row(Bw, 0);
         for (int j = 0; j < Bw; ++j) {
@@ -1305,14 +1368,14 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
             HIPCHK(hipMemcpyAsync(c->forced_dev, fbuf.data(), sizeof(int) * fbuf.size(), hipMemcpyHostToDevice, c->stream));
         }
         HIPCHK(hipEventRecord(c->ev[2], c->stream));
-        if (R < Bw) { run_conv(c, Bw, R); run_encoder(c, Bw, false, true, R); }
+        if (R < Bw) { run_conv(c, Bw, R, enc_rows); run_encoder(c, Bw, false, true, R, enc_rows); }
         HIPCHK(hipEventRecord(c->ev[3], c->stream));
         // decoder state
         for (int j = 0; j < Bw; ++j) {
             SkwSeqState& s = c->h_st[j]; memset(&s, 0, sizeof s);
             s.active = 1; s.seek_delta = 100 * WHISPER_CHUNK_SIZE; s.seek = sk[j];
             s.seek_end = n_len_org[act[j]]; s.n_prompt = np_row[j]; s.min_margin = INFINITY; s.cur_token = pbuf[(size_t)j * SKW_PROMPT_CAP]; s.cur_pos = 0;
-            s.temperature = temps[act[j]][tidx[act[j]]];
+            s.temperature = temps[act[j]][tidx[act[j]]]; s.n_keys = ks[j];
         }
         // The prompt in one pass (whisper.cpp evaluates it in one whisper_decode call): every prompt token but a row's last becomes a row of ONE decoder pass —
         // the step's own kernels, a row per (sequence, position), the caches addressed through the row's sequence — which fills the self-attention K / V
@@ -1325,7 +1388,7 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
             std::vector<SkwSeqState> pf; std::vector<int> row_end;      // row_end: cumulative rows after each sequence (chunks are whole sequences)
             for (int j = 0; j < Bw; ++j) {
                 for (int k = 0; k + 1 < np_row[j]; ++k) { SkwSeqState t; memset(&t, 0, sizeof t);
-                t.active = 1; t.cur_token = pbuf[(size_t)j * SKW_PROMPT_CAP + k]; t.cur_pos = k; t.pad = j; t.seek = j * ntc + k; pf.push_back(t); }
+                t.active = 1; t.cur_token = pbuf[(size_t)j * SKW_PROMPT_CAP + k]; t.cur_pos = k; t.pad = j; t.seek = j * ntc + k; t.n_keys = ks[j]; pf.push_back(t); }
                 row_end.push_back((int)pf.size());
                 c->h_st[j].cur_token = pbuf[(size_t)j * SKW_PROMPT_CAP + np_row[j] - 1]; c->h_st[j].cur_pos = np_row[j] - 1;
             }
@@ -1640,21 +1703,26 @@ extern "C" int skw_log_mel(skw_ctx* c, const float* pcm_host, int n_samples, flo
     HIPCHK(hipMemcpyAsync(mel_out, tmp, n * sizeof(float), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); hipFree(tmp);
     *n_len_o = n_len[0]; *n_len_org_o = n_len_org[0]; return 0;
 }
-static int tap_prepare(skw_ctx* c, const float* pcm_host, int n_samples, int seek) {
+// audio_ctx: 0 = the model's n_audio_ctx; the tap's one window slot gets that many positions (returned through *K)
+static int tap_prepare(skw_ctx* c, const float* pcm_host, int n_samples, int seek, int audio_ctx, int* K) {
     char* errbuf = c->errbuf;
     WS_READY(c);
+    if (audio_ctx < 0 || audio_ctx > c->m->hp.n_audio_ctx) { snprintf(errbuf, 512, "audio_ctx %d outside [0, %d] (0 = the model's n_audio_ctx)", audio_ctx, c->m->hp.n_audio_ctx); return -1; }
+    *K = audio_ctx > 0 ? audio_ctx : c->m->hp.n_audio_ctx;
     HIPCHK(hipSetDevice(c->m->device));
     std::vector<int> n_len, n_len_org; const float* pp[1] = {pcm_host}; int32_t ns[1] = {n_samples};
     if (load_clips(c, pp, ns, 1, 0, n_len, n_len_org)) return -1;
     run_mel(c, 1);
     int zero = 0; HIPCHK(hipMemcpyAsync(c->clip_idx, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream)); HIPCHK(hipMemcpyAsync(c->seek, &seek, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    const int rows = set_slot_k(c, K, 1, 0, c->stream);
     HIPCHK(hipStreamSynchronize(c->stream));
-    run_conv(c, 1); return 0;
+    run_conv(c, 1, 0, rows); return 0;
 }
-extern "C" int skw_conv_stem(skw_ctx* c, const float* pcm_host, int n_samples, int seek, float* x0) {
-    char* errbuf = c->errbuf; if (tap_prepare(c, pcm_host, n_samples, seek)) return -1;
-    HIPCHK(hipMemcpyAsync(x0, c->x, sizeof(float) * c->m->hp.n_audio_ctx * c->m->hp.n_audio_state, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return 0;
+extern "C" int skw_conv_stem_actx(skw_ctx* c, const float* pcm_host, int n_samples, int seek, int audio_ctx, float* x0) {
+    char* errbuf = c->errbuf; int K = 0; if (tap_prepare(c, pcm_host, n_samples, seek, audio_ctx, &K)) return -1;
+    HIPCHK(hipMemcpyAsync(x0, c->x, sizeof(float) * K * c->m->hp.n_audio_state, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return 0;
 }
+extern "C" int skw_conv_stem(skw_ctx* c, const float* pcm_host, int n_samples, int seek, float* x0) { return skw_conv_stem_actx(c, pcm_host, n_samples, seek, 0, x0); }
 // cross V^T [(h*64 + c)][Tpad kperm] of batch slot 0 -> natural [key][d] f32
 __global__ void k_vt2f_copy(const half_t* src, float* dst, int nc, int dt, int Tpad) { long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
 if (i >= (long)nc * dt) return; int key = (int)(i / dt), n = (int)(i % dt); dst[i] = (float)src[(long)n * Tpad + skw_kperm(key)]; }
@@ -1666,9 +1734,12 @@ if (i >= (long)nc * dt) return; int key = (int)(i / dt), n = (int)(i % dt);
 const int p = skw_kperm(key); dst[i] = (float)src[skw_vtfrag_off(0, H, Tpad, n, p & ~7) + (p & 7)]; }
 __global__ void k_h2f_copy(const half_t* src, float* dst, long n) { long i = (long)blockIdx.x * blockDim.x + threadIdx.x; if (i < n) dst[i] = (float)src[i]; }
 extern "C" int skw_encode(skw_ctx* c, const float* pcm_host, int n_samples, int seek, float* enc_out, float* cross_k, float* cross_v) {
-    char* errbuf = c->errbuf; if (tap_prepare(c, pcm_host, n_samples, seek)) return -1;
-    const skw_hparams& hp = c->m->hp; const int nc = hp.n_audio_ctx, d = hp.n_audio_state, dt = hp.n_text_state;
-    run_encoder(c, 1, true, true);
+    return skw_encode_actx(c, pcm_host, n_samples, seek, 0, enc_out, cross_k, cross_v);
+}
+extern "C" int skw_encode_actx(skw_ctx* c, const float* pcm_host, int n_samples, int seek, int audio_ctx, float* enc_out, float* cross_k, float* cross_v) {
+    char* errbuf = c->errbuf; int K = 0; if (tap_prepare(c, pcm_host, n_samples, seek, audio_ctx, &K)) return -1;
+    const skw_hparams& hp = c->m->hp; const int nc = K, d = hp.n_audio_state, dt = hp.n_text_state;      // (nc: the K positions exported)
+    run_encoder(c, 1, true, true, 0, c->enc_rows);
     HIPCHK(hipMemcpyAsync(enc_out, c->enc_out32, sizeof(float) * nc * d, hipMemcpyDeviceToHost, c->stream));
     if (cross_k && cross_v) {
         const long n = (long)nc * dt; float* tmp = nullptr; HIPCHK(hipMalloc((void**)&tmp, n * sizeof(float)));
@@ -1690,7 +1761,7 @@ extern "C" int skw_decode_logits(skw_ctx* c, const int32_t* tokens, int n_tokens
     HIPCHK(hipSetDevice(c->m->device));
     if (n_tokens < 1 || n_tokens > c->m->hp.n_text_ctx) { snprintf(errbuf, 512, "bad n_tokens"); return -1; }
     for (int t = 0; t < n_tokens; ++t) {
-        hipLaunchKernelGGL(k_set_tokens, dim3(1), dim3(1), 0, c->stream, c->st, tokens[t], t);
+        hipLaunchKernelGGL(k_set_tokens, dim3(1), dim3(1), 0, c->stream, c->st, tokens[t], t, c->slot_k);      // (slot 0's K: the last encode's)
         run_decoder_step(c, 0, 1, t, t == n_tokens - 1, c->stream);
     }
     HIPCHK(hipMemcpyAsync(logits, c->logits, sizeof(float) * c->m->hp.n_vocab, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return 0;
@@ -1930,6 +2001,20 @@ extern "C" int skw_ctx_kernel_clock_get(skw_ctx* c, long* launches, double* sum_
     return 0;
 }
 
+// the keys the recorded launches walked, summed over their live rows (per-clip audio context: a launch's algorithmic bytes = 4 B x its rows' walked keys x n_text_state)
+extern "C" int skw_ctx_kernel_clock_keys(skw_ctx* c, double* sum_keys) {
+    char* errbuf = c->errbuf;
+    if (!c->kclk) { snprintf(errbuf, 512, "the kernel clock was never armed"); return -1; }
+    HIPCHK(hipSetDevice(c->m->device));
+    const size_t nb = kclk_node_bytes(), n_nodes = (size_t)skw_ctx::MAX_GROUPS * c->m->hp.n_text_layer;
+    std::vector<char> h(nb * n_nodes);
+    HIPCHK(hipMemcpy(h.data(), c->kclk, h.size(), hipMemcpyDeviceToHost));
+    double sk = 0;
+    for (size_t i = 0; i < n_nodes; ++i) { const SkwKClk* k = (const SkwKClk*)(h.data() + nb * i);
+        for (int j = 0; j < KCLK_CAP; ++j) for (int sh = 0; sh < SKW_KCLK_SHARDS; ++sh) sk += k->rec[j][sh].keys; }
+    *sum_keys = sk;
+    return 0;
+}
 // every recorded launch of the last call as (begin us, end us, live rows), times relative to the earliest begin; returns the count written (<= cap), < 0 on error.  Launches of
 // different row groups overlap in time: the union of the intervals is the time the kernel was in flight at all.
 extern "C" long skw_ctx_kernel_clock_records(skw_ctx* c, double* out /* [cap][3] */, long cap) {

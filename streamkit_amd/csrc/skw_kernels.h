@@ -88,13 +88,17 @@ bool skw_gemm16_takes_w(const SkwGemmArgs& a);      // true: skw_gemm16 launches
 bool skw_gemm16_small(const SkwGemmArgs& a, hipStream_t s);
 // A = LayerNorm(ln_x [M][K] f32; ln_w, ln_b), statistics and normalisation inside the kernel from the rows it holds in registers; W in NATURAL k order
 bool skw_gemm16_small_lnA(const SkwGemmArgs& a, hipStream_t s);
-void skw_attn_encoder16(const half_t* Qh, const half_t* Kh, const half_t* Vt, half_t* out, long ld_out, int B, int H, int n_ctx, int Tpad, hipStream_t s);
+// slot_k (per-clip audio context; null: every slot has n_ctx positions): slot b attends over its first slot_k[b] keys with its first slot_k[b] queries; Tpad stays the stride
+// of Qh / Kh / Vt, out_rows the rows per slot of `out` (>= every slot_k[b]).  Keys past slot_k[b] hold whatever an earlier, longer call left: they reach no result.
+void skw_attn_encoder16(const half_t* Qh, const half_t* Kh, const half_t* Vt, half_t* out, long ld_out, int B, int H, int n_ctx, int Tpad, hipStream_t s,
+                        const int* slot_k = nullptr, int out_rows = 0);
 // cross attention of the prompt pass (f16_mfma): the encoder attention kernel with a sequence's prompt tokens as the queries — one read of the sequence's cross K / V^T per 128 of them.
 // q: [rows][d] f16 plain (scaled); sequence i: rows row0[i] .. + nq[i], cross K / V^T of window slot slot[i]; out: [rows][kperm(d)] f16
 // fragment-order image of a [N][ldw] f16 weight (N % 16 == 0, K % 32 == 0; perm: rows taken in the kperm'ed output order of the GELU epilogues); out: N * K halves
 void skw_make_wfrag(const half_t* W, long ldw, int N, int K, int perm, half_t* out, hipStream_t s);
 void skw_xattn_prefill16(const half_t* q, const half_t* ck, const half_t* cvt, half_t* out, int n_seq, int nq_max, const int* row0, const int* nq, const int* slot,
-                         int H, int d, int n_ctx, int Tpad, hipStream_t s, int frag = 0, int ofrag = 0);
+                         // slot_k: [window slots] keys of each slot's cross K / V^T (null: n_ctx)
+                         int H, int d, int n_ctx, int Tpad, hipStream_t s, int frag = 0, int ofrag = 0, const int* slot_k = nullptr);
 // small-M GEMM (M <= 64): fragments straight from global memory, one 16-column strip per wave
 void skw_gemm_smallm(const SkwGemmArgs& a, hipStream_t s);
 
@@ -105,7 +109,7 @@ void skw_layernorm(const float* x, int rows, int d, const float* w, const float*
 // out: f16 [b*n_ctx + i][kperm(h*64 + c)] with row stride ld_out
 // f32_out: `out` is a float [B*n_ctx][ld_out] buffer, natural order, unrounded
 void skw_attn_encoder(const half_t* Qh, const half_t* Kh, const half_t* Vt, half_t* out, long ld_out, int B, int H, int n_ctx, int Tpad, hipStream_t s,
-    float* dbg = nullptr, float* dbg2 = nullptr, int f32_out = 0);
+    float* dbg = nullptr, float* dbg2 = nullptr, int f32_out = 0, const int* slot_k = nullptr /* as skw_attn_encoder16 */, int out_rows = 0);
 
 // log-mel front end
 struct SkwMelTables { const float* hann; const float* sin_t; const float* cos_t; const float* filters; int n_mel; int n_fft_bins;
@@ -115,7 +119,9 @@ void skw_mel_frames(const float* pcm, const long* pcm_off, const int* n_samples,
 // per-clip max -> clamp (max-8) and (x+4)/4, in place; tmp: [B] doubles
 void skw_mel_normalize(float* mel, const int* n_len, int B, int n_len_max, int n_mel, float* clip_max, hipStream_t s);
 // build conv1's im2col rows for the window starting at seek[b]: out f16 [b*T + t][256 kperm] (k = tap*n_mel + c, zero padded to 256)
-void skw_mel_im2col(const float* mel, const int* clip_idx, const int* seek, const int* n_len, int Bw, int n_len_max, int n_mel, int T, int k_pad, half_t* out, hipStream_t s);
+// slot_k (may be null): window slot b sees mel frames [seek, seek + 2 slot_k[b]) and zeros beyond (per-clip audio context); T stays the rows per slot of `out`
+void skw_mel_im2col(const float* mel, const int* clip_idx, const int* seek, const int* n_len, int Bw, int n_len_max, int n_mel, int T, int k_pad, half_t* out, hipStream_t s,
+                    const int* slot_k = nullptr);
 
 // ---------------- decoder ----------------
 // x[b][d] = f32(te[tok[b]][kperm(i)]) + pe[pos[b]][i]
@@ -151,13 +157,16 @@ void skw_dec_self_attn(const half_t* q, const half_t* kc, const half_t* vc, cons
 // what rocprofv3 calls the duration minus the dispatch and completion-signal edges, which skw_debug_xattn measures (events and clock on the same isolated launches).
 #define SKW_KCLK_SHARDS 16
 #define SKW_KCLK_MAX_WG 4096
-struct SkwKClkRec { unsigned long long t0_inv, t1; unsigned live_rows, pad; };
+struct SkwKClkRec { unsigned long long t0_inv, t1; unsigned live_rows, keys; };      // keys: summed over the live rows, the keys each walked
 struct SkwKClk { unsigned cap, pad0, pad1, pad2; unsigned cnt[SKW_KCLK_MAX_WG]; SkwKClkRec rec[1][SKW_KCLK_SHARDS]; };      // rec[cap][SKW_KCLK_SHARDS] follows
 void skw_dec_cross_attn_vt(const half_t* q, const half_t* ck, const half_t* cvt, int B, int H, int d, int n_ctx, int Tpad, half_t* out, const int* active, hipStream_t s,
     int f32_out = 0, int pv16 = 0, const int* seq = nullptr,
                            // ofrag (one-pass kernel only): the output rows as the fragment-order A image of the projection that follows; events: stamped at the kernel's
                            //  own begin / end (the engine's per-kernel profile)
-                           hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, int ofrag = 0, SkwKClk* clk = nullptr);
+                           hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, int ofrag = 0, SkwKClk* clk = nullptr,
+                           // nkeys (stride of `active`; null: n_ctx): &state[0].n_keys — row b attends over the first nkeys[b] keys of its sequence (0: n_ctx).  Read from device
+                           //  memory, so a captured step holds no key count; n_ctx and Tpad stay the strides of the buffers
+                           const int* nkeys = nullptr);
 
 // per-sequence decoding state kept on the device (whisper_decoder + the bits of whisper_full_with_state's loop that depend on it)
 struct SkwSeqState {
@@ -173,6 +182,7 @@ struct SkwSeqState {
     int32_t cur_pos;       // its position
     float temperature;     // 0: argmax; > 0: logits / t, then a std::discrete_distribution draw from the clip's mt19937
     int32_t pad;
+    int32_t n_keys;        // cross-attention keys of this row (the clip's audio_ctx); 0: the model's n_audio_ctx
 };
 // The prompt pass (skw_engine.hip, prefill): one SkwSeqState per PROMPT TOKEN, so every kernel of the decode step takes it as a row —
 //   active = 1, cur_token / cur_pos = the token and its position, pad = the sequence (window slot) it belongs to, seek = slot * n_text_ctx + position (its K / V cache row).

@@ -282,7 +282,9 @@ void skw_layernorm(const float* x, int rows, int d, const float* w, const float*
 #define AT_KROW 72   // halves per K row in LDS (64 + 8 pad = 144 B)
 #define AT_VROW 40   // halves per V^T row in LDS (32 + 8 pad = 80 B)
 __global__ __launch_bounds__(256, 2) void k_attn_encoder(const half_t* Qh, const half_t* Kh, const half_t* Vt, half_t* out, long ld_out,
-                                                         int H, int n_ctx, int Tpad, float kq_scale, float* dbg, float* dbg2, int f32_out) {
+                                                         int H, int n_ctx, int Tpad, float kq_scale, float* dbg, float* dbg2, int f32_out, const int* slot_k, int out_rows) {
+    // per-clip audio context: this slot's keys and queries come from device memory; what is walked ends at its last 32-key block, the buffers keep their Tpad stride
+    if (slot_k) { n_ctx = slot_k[blockIdx.z]; if ((int)blockIdx.x * 128 >= n_ctx) return; }      // (uniform per workgroup)
     __shared__ __attribute__((aligned(16))) half_t ldsK[2][32 * AT_KROW];
     __shared__ __attribute__((aligned(16))) half_t ldsV[2][64 * AT_VROW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -301,7 +303,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_encoder(const half_t* Qh, const
 #pragma unroll
         for (int e = 0; e < 8; ++e) { qf[qt][e] = h2f(x0.h[e]); qf[qt][8 + e] = h2f(x1.h[e]); }
     }
-    const int nkb = Tpad >> 5;
+    const int nkb = slot_k ? (n_ctx + 31) >> 5 : Tpad >> 5;
     // staging maps
     const int krow = tid >> 3, kcc = tid & 7;   // K: 32 rows x 8 chunks
     const int vrow = tid >> 2, vcc = tid & 3;   // V^T: 64 rows x 4 chunks
@@ -385,6 +387,13 @@ __global__ __launch_bounds__(256, 2) void k_attn_encoder(const half_t* Qh, const
                     H8 vf[4];
 #pragma unroll
                     for (int ct = 0; ct < 4; ++ct) vf[ct].u = *(const uint4*)(&ldsV[buf][(ct * 16 + r16) * AT_VROW + g * 8]);
+                    // keys past a short slot's context hold an earlier call's values (or a don't-care row's): they are replaced, not multiplied by p = 0
+                    if (slot_k && kb * 32 + 32 > n_ctx) {
+#pragma unroll
+                        for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) if (kb * 32 + 4 * e + g >= n_ctx) vf[ct].h[e] = f2h(0.0f);
+                    }
 #pragma unroll
                     for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
@@ -421,7 +430,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_encoder(const half_t* Qh, const
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 int qi = q0 + qt * 16 + g * 4 + r; int c = ct * 16 + r16;
-                if (qi < n_ctx) att_store(out, ((long)b * n_ctx + qi) * ld_out, h * 64 + c, oacc[qt][ct][r], f32_out);
+                if (qi < n_ctx) att_store(out, ((long)b * out_rows + qi) * ld_out, h * 64 + c, oacc[qt][ct][r], f32_out);
                 if (dbg && qi < n_ctx && b == 0) { dbg[(long)qi * (H * 64) + h * 64 + c] = oacc[qt][ct][r];
                 if (ct == 0 && r == 0 && g == 0 && q0 + qt * 16 + r16 < n_ctx) { dbg[(long)n_ctx * H * 64 + (long)h * n_ctx + q0 + qt * 16 + r16] = rmax[qt];
                 dbg[(long)n_ctx * H * 64 + (long)(H + h) * n_ctx + q0 + qt * 16 + r16] = rinv[qt]; } }
@@ -610,17 +619,19 @@ __global__ __launch_bounds__(256, 1) void k_attn_encoder_v3(const half_t* Qh, co
         }
 }
 
-void skw_attn_encoder(const half_t* Qh, const half_t* Kh, const half_t* Vt, half_t* out, long ld_out, int B, int H, int n_ctx, int Tpad, hipStream_t s, float* dbg, float* dbg2, int f32_out) {
+void skw_attn_encoder(const half_t* Qh, const half_t* Kh, const half_t* Vt, half_t* out, long ld_out, int B, int H, int n_ctx, int Tpad, hipStream_t s, float* dbg, float* dbg2, int f32_out,
+                      const int* slot_k, int out_rows) {
     // Whisper's 1500-frame context; k_attn_encoder below is the form that carries the stage taps (layer 0 of a tapped run) and any other context length
-    if (Tpad == 1504 && Tpad - n_ctx < 16 && !dbg) {
+    if (!out_rows) out_rows = n_ctx;
+    if (Tpad == 1504 && Tpad - n_ctx < 16 && !dbg && !slot_k) {
         const int qtiles = (n_ctx + 63) / 64;
         constexpr int RT3 = 72;
         hipLaunchKernelGGL((k_attn_encoder_v3<94, RT3>), dim3(qtiles * H * B), dim3(256), (size_t)4 * (94 - RT3) * 64 * 16, s, Qh, Kh, Vt, out, ld_out, H, n_ctx, Tpad,
             1.0f / sqrtf(64.0f), qtiles, f32_out);
         return;
     }
-    dim3 grid((n_ctx + 127) / 128, H, B);
-    hipLaunchKernelGGL(k_attn_encoder, grid, dim3(256), 0, s, Qh, Kh, Vt, out, ld_out, H, n_ctx, Tpad, 1.0f / sqrtf(64.0f), dbg, dbg2, f32_out);
+    dim3 grid(((slot_k ? out_rows : n_ctx) + 127) / 128, H, B);
+    hipLaunchKernelGGL(k_attn_encoder, grid, dim3(256), 0, s, Qh, Kh, Vt, out, ld_out, H, n_ctx, Tpad, 1.0f / sqrtf(64.0f), dbg, dbg2, f32_out, slot_k, out_rows);
 }
 
 // ------------------------------------------------------------------ log-mel front end (K1)
@@ -735,20 +746,22 @@ void skw_mel_normalize(float* mel, const int* n_len, int B, int n_len_max, int n
     hipLaunchKernelGGL(k_mel_norm, dim3(64, B), dim3(256), 0, s, mel, n_len, n_len_max, n_mel, (const unsigned*)clip_max);
 }
 // conv1 im2col: out[(bw*T + t)][kperm(k)], k = tap*n_mel + c (k < 3*n_mel), zero padded to k_pad (256 for 80 bands, 384 for large-v3's 128: the width of the conv1 weight image)
-__global__ void k_mel_im2col(const float* mel, const int* clip_idx, const int* seek, const int* n_len, int n_len_max, int n_mel, int T, int k_pad, half_t* out) {
+__global__ void k_mel_im2col(const float* mel, const int* clip_idx, const int* seek, const int* n_len, int n_len_max, int n_mel, int T, int k_pad, half_t* out, const int* slot_k) {
     const int bw = blockIdx.y, t = blockIdx.x;   // 256 threads
     const int clip = clip_idx[bw], sk = seek[bw], nl = n_len[clip];
+    const int lim = slot_k ? min(T, 2 * slot_k[bw]) : T;      // the slot's own window: frames past 2 K read as zero (conv1 output 2 K - 1 reads frame 2 K)
     for (int k = threadIdx.x; k < k_pad; k += blockDim.x) {
         float v = 0.0f;
         if (k < 3 * n_mel) {
             int tap = k / n_mel, c = k % n_mel; int tt = t - 1 + tap; int fr = sk + tt;
-            if (tt >= 0 && tt < T && fr < nl) v = mel[((long)clip * n_len_max + fr) * n_mel + c];
+            if (tt >= 0 && tt < lim && fr < nl) v = mel[((long)clip * n_len_max + fr) * n_mel + c];
         }
         out[((long)bw * T + t) * k_pad + skw_kperm(k)] = f2h(v);
     }
 }
-void skw_mel_im2col(const float* mel, const int* clip_idx, const int* seek, const int* n_len, int Bw, int n_len_max, int n_mel, int T, int k_pad, half_t* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_mel_im2col, dim3(T, Bw), dim3(256), 0, s, mel, clip_idx, seek, n_len, n_len_max, n_mel, T, k_pad, out);
+void skw_mel_im2col(const float* mel, const int* clip_idx, const int* seek, const int* n_len, int Bw, int n_len_max, int n_mel, int T, int k_pad, half_t* out, hipStream_t s,
+                    const int* slot_k) {
+    hipLaunchKernelGGL(k_mel_im2col, dim3(T, Bw), dim3(256), 0, s, mel, clip_idx, seek, n_len, n_len_max, n_mel, T, k_pad, out, slot_k);
 }
 
 // ------------------------------------------------------------------ decoder pieces
@@ -974,9 +987,11 @@ __global__ __launch_bounds__(256) void k_dec_attn(const half_t* q, long ldq, con
 template <int MAXT, int WPH, int HPW, bool PV16 = false>
 __global__ __launch_bounds__(64 * HPW * WPH, (HPW * WPH >= 12) ? 1 : 12 / (HPW * WPH)) void k_dec_cross_attn(const half_t* q, long ldq, const half_t* kbase, long k_batch_stride, long ldk,
                                                            const half_t* vtbase, int n_ctx, int Tpad, int H, half_t* out, long ldo, const int* active, int active_stride,
-                                                               int f32_out, const int* seq) {
+                                                               int f32_out, const int* seq, const int* nkeys) {
     const int bx = blockIdx.x, by = blockIdx.y;
     if (active && !active[by * active_stride]) return;      // uniform per workgroup (one sequence): a finished sequence stops streaming its 55 MB of cross K/V
+    // per-clip audio context: the row's key count from device memory (0: the model's); the caller's n_ctx and Tpad stay the strides of cross K / V^T
+    if (nkeys) { const int nk = nkeys[by * active_stride]; if (nk > 0) n_ctx = min(nk, n_ctx); }
     __shared__ float plds[HPW][MAXT * 64];
     __shared__ __attribute__((aligned(16))) half_t klds[HPW * WPH][64 * 72];
     __shared__ float smax[HPW][WPH];
@@ -1046,7 +1061,7 @@ __global__ __launch_bounds__(64 * HPW * WPH, (HPW * WPH >= 12) ? 1 : 12 / (HPW *
     __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(vtbase + bh * 64 * Tpad), 0, (unsigned)(64 * Tpad * 2), 0x00020000);
     constexpr int CT = 4 / WPH;                                                   // channel tiles per wave
     const unsigned vo = (unsigned)(((half * CT * 16 + r16) * Tpad + g * 8) * 2);
-    const int nkb = Tpad >> 5;
+    const int nkb = (n_ctx + 31) >> 5;                                            // the 32-key blocks below the row's key count (a full row: Tpad >> 5)
     constexpr int RD = PV16 ? SKW_XATTN_RD16 : 8;
     H8v ring[RD][CT];
 #pragma unroll
@@ -1091,6 +1106,13 @@ __global__ __launch_bounds__(64 * HPW * WPH, (HPW * WPH >= 12) ? 1 : 12 / (HPW *
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) ring[j][ct].v = __builtin_amdgcn_raw_buffer_load_b128(rv, (nb < nkb) ? vo + ct * 16 * Tpad * 2 + nb * 64 : 0x7fffff00u, 0, 0);
             const int kbc = min(kb, nkb - 1);     // blocks past the end multiply p by zero-filled fragments
+            // keys past the row's count in its last block: V^T there is an earlier, longer call's (or a don't-care encoder row's) — replaced by zeros, never multiplied by p = 0
+            if (kbc * 32 + 32 > n_ctx) {
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) if (kbc * 32 + 4 * e + g >= n_ctx) vf[ct].h[e] = f2h(0.0f);
+            }
             if constexpr (PV16) {
                 // f16_mfma precision: p is f16-valued and V^T is f16, so a 32-key block is ONE v_mfma_f32_16x16x32_f16 (16 cycles) instead of eight dependent
                 // f32 MFMAs (256 cycles: tools/xattn_probe.py put them at 8.7 us of a 65 us launch that is otherwise at the memory system's pace).
@@ -1138,10 +1160,12 @@ __global__ __launch_bounds__(64 * HPW * WPH, (HPW * WPH >= 12) ? 1 : 12 / (HPW *
 // together they walk one sequential stream.  What lost against this form (profiles/r03g, r03h, r04i): the row layouts (16 x 64 B per load instruction), contiguous quarters per wave, 2 / 4
 // blocks in flight, one or two heads per workgroup, XCD-aware placement of a sequence's workgroups.
 // clk (bench.py's roofline line; null in every other run): the launch's own begin and end on the device's constant-rate clock — see SkwKClk in skw_kernels.h.
-template <int HPW, int RD>
+// VARK (per-clip audio context; the uniform full-length step keeps the VARK = false instantiation): the row's key count comes from device memory (nkeys, next to `active`), a wave
+// walks only the 32-key blocks below it — so no block is all pad, and exp2(-inf - -inf) never happens — and the V^T of the pad keys in the row's last block is replaced by zeros.
+template <int HPW, int RD, bool VARK = false>
 __global__ __launch_bounds__(256 * HPW, (HPW >= 3) ? 1 : 3 / HPW) void k_dec_cross_attn16(const half_t* q, long ldq, const half_t* kbase, long k_batch_stride, long ldk, const half_t* vtbase,
                                                                                          int n_ctx, int Tpad, int H, half_t* out, long ldo, const int* active,
-                                                                                             int active_stride, int f32_out, const int* seq, int ofrag_k, SkwKClk* clk) {
+                                                                                             int active_stride, int f32_out, const int* seq, int ofrag_k, SkwKClk* clk, const int* nkeys) {
     typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
     constexpr int AUX = 2;
     const int b = blockIdx.y;
@@ -1165,8 +1189,10 @@ __global__ __launch_bounds__(256 * HPW, (HPW >= 3) ? 1 : 3 / HPW) void k_dec_cro
     const int bs = seq ? seq[b * active_stride] : b;
     const int r16 = lane & 15, g = lane >> 4;
     // a wave's blocks: every fourth 32-key block (the four waves of a head walk one sequential stream together)
-    const int nkb = Tpad >> 5;
-    const int first = part, step = 4, cnt = (nkb - part + 3) >> 2;
+    const int nkb = Tpad >> 5;                                          // the images' stride
+    if constexpr (VARK) { const int nk = nkeys[b * active_stride]; if (nk > 0) n_ctx = min(nk, n_ctx); }      // (uniform per workgroup)
+    const int nkw = VARK ? (n_ctx + 31) >> 5 : nkb;                     // the blocks walked
+    const int first = part, step = 4, cnt = (nkw - part + 3) >> 2;
     f16x8_t qb[2];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) qb[kk] = *(const f16x8_t*)(q + (long)b * ldq + h * 64 + kk * 32 + g * 8);
@@ -1222,7 +1248,16 @@ __global__ __launch_bounds__(256 * HPW, (HPW >= 3) ? 1 : 3 / HPW) void k_dec_cro
                     // masked keys: exp2(-inf) = 0; the sum is of the rounded values the MFMA multiplies
                     for (int r = 0; r < 4; ++r) { const half_t ph = f2h(__builtin_amdgcn_exp2f(__builtin_fmaf(sc[t][r], LOG2E, -mc))); pb[4 * t + r] = ph; l = l + h2f(ph); }
 #pragma unroll
-                for (int ct = 0; ct < 4; ++ct) o[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, ring[j][4 + ct]), pb, o[ct], 0, 0, 0);
+                for (int ct = 0; ct < 4; ++ct) {
+                    f16x8_t vt = __builtin_bit_cast(f16x8_t, ring[j][4 + ct]);
+                    if constexpr (VARK) {
+                        if (kb * 32 + 32 > n_ctx) {                     // (wave-uniform) element e of lane group g is key 4 e + g of the block
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) if (kb * 32 + 4 * e + g >= n_ctx) vt[e] = (half_t)0.0f;
+                        }
+                    }
+                    o[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vt, pb, o[ct], 0, 0, 0);
+                }
                 if (n + RD < cnt) issue(ring[j], kb + RD * step);              // the slot's next block (RD - 1 blocks stay in flight while one is consumed)
             }
         }
@@ -1250,28 +1285,33 @@ __global__ __launch_bounds__(256 * HPW, (HPW >= 3) ? 1 : 3 / HPW) void k_dec_cro
     }
     if (rec) {      // earliest begin and latest end over the workgroups, off the critical path (thread 0 sits in a wave that does the final combine and store)
         atomicMax(&rec->t0_inv, ~t_in); atomicMax(&rec->t1, wall_clock64());
-        if (blockIdx.x == 0) atomicAdd(&rec->live_rows, 1u);
+        if (blockIdx.x == 0) { atomicAdd(&rec->live_rows, 1u); atomicAdd(&rec->keys, (unsigned)n_ctx); }
     }
 }
 void skw_dec_cross_attn_vt(const half_t* q, const half_t* ck, const half_t* cvt, int B, int H, int d, int n_ctx, int Tpad, half_t* out, const int* active, hipStream_t s,
-    int f32_out, int pv16, const int* seq, hipEvent_t ev_start, hipEvent_t ev_stop, int ofrag, SkwKClk* clk) {
+    int f32_out, int pv16, const int* seq, hipEvent_t ev_start, hipEvent_t ev_stop, int ofrag, SkwKClk* clk, const int* nkeys) {
     const int as = (int)(sizeof(SkwSeqState) / 4);
     const dim3 grid((H + 2) / 3, B), blk(768);        // three heads per workgroup: 256 workgroups of 12 waves at 64 rows x 12 heads, one per CU
     // (with events: hipExtLaunchKernelGGL stamps them at the kernel's own begin and end — the duration rocprofv3 reports — instead of an event pair around the launch, which adds the dispatch gap)
     if (pv16 == 2) {          // f16_mfma precision, fragment-order cross K / V^T: the one-pass streaming kernel
-        if (ev_start) hipExtLaunchKernelGGL((k_dec_cross_attn16<3, 3>), grid, blk, 0, s, ev_start, ev_stop, 0, q, (long)d, ck, (long)Tpad * d, (long)d, cvt, n_ctx, Tpad, H, out, (long)d,
-            active, as, f32_out & 1, seq, ofrag ? d : 0, clk);
+        if (nkeys && ev_start) hipExtLaunchKernelGGL((k_dec_cross_attn16<3, 3, true>), grid, blk, 0, s, ev_start, ev_stop, 0, q, (long)d, ck, (long)Tpad * d, (long)d, cvt, n_ctx, Tpad, H,
+            out, (long)d, active, as, f32_out & 1, seq, ofrag ? d : 0, clk, nkeys);
+        else if (nkeys) hipLaunchKernelGGL((k_dec_cross_attn16<3, 3, true>), grid, blk, 0, s, q, (long)d, ck, (long)Tpad * d, (long)d, cvt, n_ctx, Tpad, H, out, (long)d, active, as,
+            f32_out & 1, seq, ofrag ? d : 0, clk, nkeys);
+        else if (ev_start) hipExtLaunchKernelGGL((k_dec_cross_attn16<3, 3>), grid, blk, 0, s, ev_start, ev_stop, 0, q, (long)d, ck, (long)Tpad * d, (long)d, cvt, n_ctx, Tpad, H, out, (long)d,
+            active, as, f32_out & 1, seq, ofrag ? d : 0, clk, nkeys);
         else hipLaunchKernelGGL((k_dec_cross_attn16<3, 3>), grid, blk, 0, s, q, (long)d, ck, (long)Tpad * d, (long)d, cvt, n_ctx, Tpad, H, out, (long)d, active, as, f32_out & 1, seq,
-            ofrag ? d : 0, clk);
+            ofrag ? d : 0, clk, nkeys);
         return;
     }
     // row layouts: the two-phase kernel; pv16 == 1 (f16_mfma with SKW_XATTN_FRAG=0) takes a 32-key block of P.V in one f16 MFMA, the exact precision chains f32 MFMAs key by key
     if (pv16 && ev_start) hipExtLaunchKernelGGL((k_dec_cross_attn<24, 4, 3, true>), grid, blk, 0, s, ev_start, ev_stop, 0, q, (long)d, ck, (long)n_ctx * d, (long)d, cvt, n_ctx, Tpad, H, out,
-        (long)d, active, as, f32_out & 1, seq);
+        (long)d, active, as, f32_out & 1, seq, nkeys);
     else if (ev_start) hipExtLaunchKernelGGL((k_dec_cross_attn<24, 4, 3>), grid, blk, 0, s, ev_start, ev_stop, 0, q, (long)d, ck, (long)n_ctx * d, (long)d, cvt, n_ctx, Tpad, H, out,
-        (long)d, active, as, f32_out & 1, seq);
-    else if (pv16) hipLaunchKernelGGL((k_dec_cross_attn<24, 4, 3, true>), grid, blk, 0, s, q, (long)d, ck, (long)n_ctx * d, (long)d, cvt, n_ctx, Tpad, H, out, (long)d, active, as, f32_out & 1, seq);
-    else hipLaunchKernelGGL((k_dec_cross_attn<24, 4, 3>), grid, blk, 0, s, q, (long)d, ck, (long)n_ctx * d, (long)d, cvt, n_ctx, Tpad, H, out, (long)d, active, as, f32_out & 1, seq);
+        (long)d, active, as, f32_out & 1, seq, nkeys);
+    else if (pv16) hipLaunchKernelGGL((k_dec_cross_attn<24, 4, 3, true>), grid, blk, 0, s, q, (long)d, ck, (long)n_ctx * d, (long)d, cvt, n_ctx, Tpad, H, out, (long)d, active, as, f32_out & 1,
+        seq, nkeys);
+    else hipLaunchKernelGGL((k_dec_cross_attn<24, 4, 3>), grid, blk, 0, s, q, (long)d, ck, (long)n_ctx * d, (long)d, cvt, n_ctx, Tpad, H, out, (long)d, active, as, f32_out & 1, seq, nkeys);
 }
 
 void skw_dec_self_attn(const half_t* q, const half_t* kc, const half_t* vc, const int* pos, int B, int H, int d, int n_text_ctx, half_t* out, const int* active,

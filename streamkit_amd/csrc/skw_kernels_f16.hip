@@ -699,8 +699,11 @@ void skw_gemm16(const SkwGemmArgs& a, hipStream_t s) {
 // [row][d] f16 in natural k order, as the cross-query GEMM leaves them) against that sequence's cross K (plain rows [key][d], natural order: both operands of the score MFMA
 // then agree on which k sits in which slot) and V^T (already this kernel's layout).  One read of a sequence's K / V^T serves up to 128 of its prompt tokens instead of one.
 // frag: K / V^T are the fragment-order images (skw_kfrag_off / skw_vtfrag_off)      // per sequence of the pass: first row, rows, window slot
-struct SkwXPrefill { const int* row0; const int* nq; const int* slot; long ldq; long k_seq_stride; long ldk; int frag; int ofrag_k; };
-template <bool XP, int OCC = 2>
+// VARK — per-clip audio context (the uniform full-length call keeps the VARK = false instantiation): slot_k[slot] is the slot's key count (and, for the encoder's own attention,
+// its query count), read from device memory; the key loop ends at the slot's last 64-key block, whose pad keys are masked in the scores AND replaced by zeros in V^T (they hold an
+// earlier, longer call's values, or what a don't-care row of this call produced: not even 0 x stale may reach a sum).  out_rows: rows per slot of `out` (the encoder's dense packing).
+struct SkwXPrefill { const int* row0; const int* nq; const int* slot; long ldq; long k_seq_stride; long ldk; int frag; int ofrag_k; const int* slot_k; int out_rows; };
+template <bool XP, int OCC = 2, bool VARK = false>
 __global__ __launch_bounds__(256, OCC) void k_attn_encoder16(const half_t* Qh, const half_t* Kh, const half_t* Vt, half_t* out, long ld_out,
                                                            int H, int n_ctx, int Tpad, float kq_scale, int qblocks, SkwXPrefill xp) {
     __shared__ __attribute__((aligned(1024))) char lds[2][2][64 * 128];   // [buffer][K | V^T][64 rows x 128 B]
@@ -711,6 +714,8 @@ __global__ __launch_bounds__(256, OCC) void k_attn_encoder16(const half_t* Qh, c
     const int b = (int)(bh / H), h = (int)(bh % H);
     int n_q = n_ctx; long qrow0 = 0;
     if (XP) { n_q = xp.nq[b]; qrow0 = xp.row0[b]; if (qb * A16_QB >= n_q) return; bh = (long)xp.slot[b] * H + h; }      // (uniform per workgroup)
+    int n_k = n_ctx;                                                     // keys walked (n_ctx stays the stride of the row layouts)
+    if constexpr (VARK) { n_k = min(n_ctx, max(1, xp.slot_k[XP ? xp.slot[b] : b])); if (!XP) { n_q = n_k; if (qb * A16_QB >= n_q) return; } }
     const int q0 = qb * A16_QB + wave * 32;
     const int r16 = lane & 15, g = lane >> 4;
     f16x8 qf[2][2];
@@ -751,7 +756,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_encoder16(const half_t* Qh, c
         }
         st_vkey[i] = pos * 8;
     }
-    const int nkb = (Tpad + 63) >> 6;
+    const int nkb = VARK ? (n_k + 63) >> 6 : (Tpad + 63) >> 6;
     const int kappa = 4 * (r16 & 3) + (r16 >> 2);
     const int k_off = kappa * 128, k_sw = (r16 & 3) << 1, v_off = r16 * 128, v_sw = r16 & 7;      // k_sw = (kappa >> 1) & 6: the stored swizzle of the row this lane reads
     u32x4 sk[2], sv[2];
@@ -807,7 +812,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_encoder16(const half_t* Qh, c
             scores(kbase, kt, s0[kt], s1[kt]);
             if (kb == nkb - 1) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) if (kb * 64 + kt * 16 + 4 * r + g >= n_ctx) { s0[kt][r] = -INFINITY; s1[kt][r] = -INFINITY; }
+                for (int r = 0; r < 4; ++r) if (kb * 64 + kt * 16 + 4 * r + g >= n_k) { s0[kt][r] = -INFINITY; s1[kt][r] = -INFINITY; }
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) { bm0 = fmaxf(bm0, s0[kt][r]); bm1 = fmaxf(bm1, s1[kt][r]); }
@@ -838,7 +843,13 @@ __global__ __launch_bounds__(256, OCC) void k_attn_encoder16(const half_t* Qh, c
         for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) {
-                const f16x8 fv = *(const f16x8*)(vbase + ct * 2048 + v_off + (((kh * 4 + g) ^ v_sw) << 4));
+                f16x8 fv = *(const f16x8*)(vbase + ct * 2048 + v_off + (((kh * 4 + g) ^ v_sw) << 4));
+                if constexpr (VARK) {
+                    if (kb == nkb - 1) {                                 // element e of lane group g is key 32 kh + 4 e + g of the block
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) if (kb * 64 + kh * 32 + 4 * e + g >= n_k) fv[e] = (half_t)0.0f;
+                    }
+                }
                 oacc[0][ct] = MFMA16X32(fv, p0[kh], oacc[0][ct]);
                 oacc[1][ct] = MFMA16X32(fv, p1[kh], oacc[1][ct]);
             }
@@ -851,7 +862,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_encoder16(const half_t* Qh, c
     for (int qt = 0; qt < 2; ++qt) {
         const int qi = q0 + qt * 16 + r16;
         if (qi < n_q) {
-            half_t* op = XP ? out + (qrow0 + qi) * ld_out : out + ((long)b * n_ctx + qi) * ld_out;
+            half_t* op = XP ? out + (qrow0 + qi) * ld_out : out + ((long)b * (VARK ? xp.out_rows : n_ctx) + qi) * ld_out;
             const float inv = qt ? inv1 : inv0;
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct)
@@ -862,7 +873,15 @@ __global__ __launch_bounds__(256, OCC) void k_attn_encoder16(const half_t* Qh, c
         }
     }
 }
-void skw_attn_encoder16(const half_t* Qh, const half_t* Kh, const half_t* Vt, half_t* out, long ld_out, int B, int H, int n_ctx, int Tpad, hipStream_t s) {
+void skw_attn_encoder16(const half_t* Qh, const half_t* Kh, const half_t* Vt, half_t* out, long ld_out, int B, int H, int n_ctx, int Tpad, hipStream_t s,
+                        const int* slot_k, int out_rows) {
+    if (slot_k) {      // per-clip audio context: keys and queries per slot from device memory (workgroups past a slot's queries return at once)
+        if (!out_rows) out_rows = n_ctx;
+        SkwXPrefill xp{}; xp.slot_k = slot_k; xp.out_rows = out_rows;
+        const int qb = (out_rows + A16_QB - 1) / A16_QB;
+        hipLaunchKernelGGL((k_attn_encoder16<false, 4, true>), dim3(qb * H * B), dim3(256), 0, s, Qh, Kh, Vt, out, ld_out, H, n_ctx, Tpad, 1.0f / sqrtf(64.0f), qb, xp);
+        return;
+    }
     const int qblocks = (n_ctx + A16_QB - 1) / A16_QB;
     // registers capped at 128 (13 dwords of scratch per lane) so that four workgroups share a CU instead of three: 9.44-9.50 against 9.64-9.77 ms per batch in a same-box A/B
     // (profiles/r04i/r04t); the waves of different workgroups are what overlaps one's exponentials with another's MFMAs (uncapped: 143 registers, three per CU)
@@ -870,10 +889,11 @@ void skw_attn_encoder16(const half_t* Qh, const half_t* Kh, const half_t* Vt, ha
 }
 // the prompt pass's cross attention: n_seq sequences, sequence i's queries are rows row0[i] .. row0[i] + nq[i] of q [rows][d] (already scaled, like K), its K / V^T those of window slot slot[i]
 void skw_xattn_prefill16(const half_t* q, const half_t* ck, const half_t* cvt, half_t* out, int n_seq, int nq_max, const int* row0, const int* nq, const int* slot,
-                         int H, int d, int n_ctx, int Tpad, hipStream_t s, int frag, int ofrag) {
+                         int H, int d, int n_ctx, int Tpad, hipStream_t s, int frag, int ofrag, const int* slot_k) {
     const int qblocks = (nq_max + A16_QB - 1) / A16_QB;
-    const SkwXPrefill xp{row0, nq, slot, (long)d, (long)(frag ? Tpad : n_ctx) * d, (long)d, frag, ofrag ? d : 0};
-    hipLaunchKernelGGL(k_attn_encoder16<true>, dim3(qblocks * H * n_seq), dim3(256), 0, s, q, ck, cvt, out, (long)d, H, n_ctx, Tpad, 1.0f, qblocks, xp);
+    const SkwXPrefill xp{row0, nq, slot, (long)d, (long)(frag ? Tpad : n_ctx) * d, (long)d, frag, ofrag ? d : 0, slot_k, 0};
+    if (slot_k) hipLaunchKernelGGL((k_attn_encoder16<true, 2, true>), dim3(qblocks * H * n_seq), dim3(256), 0, s, q, ck, cvt, out, (long)d, H, n_ctx, Tpad, 1.0f, qblocks, xp);
+    else hipLaunchKernelGGL(k_attn_encoder16<true>, dim3(qblocks * H * n_seq), dim3(256), 0, s, q, ck, cvt, out, (long)d, H, n_ctx, Tpad, 1.0f, qblocks, xp);
 }
 
 // what a wave does with a finished 16 x 16 tile: lane (r16, g) holds rows-of-W 4g .. 4g+3 (four adjacent outputs) of row m

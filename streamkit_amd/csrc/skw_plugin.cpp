@@ -73,6 +73,9 @@ struct WhisperConfig {
     int batch_window_ms = 2; int max_batch = 64; bool flush_tail = false;
     bool mixed_batch = true;         // segments of differently configured instances share a GPU batch (skw_full_batch_mixed); false: a batch is cut at the first job whose parameters differ
     std::string precision = "exact"; // exact | f16_mfma  (include/skw_engine.h, SKW_PRECISION_*)
+    // skw_full_params.audio_ctx of this instance's segments: 0 (the model's context, the reference's behaviour), an integer 1 .. n_audio_ctx, or "auto" (skw_audio_ctx_for_samples per
+    // segment).  An integer out of range is the engine's refusal, per request: it stays with the segment that carries it
+    int audio_ctx = 0; bool audio_ctx_auto = false;
     std::string vad_device = "cpu";  // cpu (the libm Silero gate, frame by frame) | gpu (Silero in the contract arithmetic of include/skw_silero_net.h on gpu_device's GPU)
     int vad_batch_frames = 1;        // complete 512-sample frames held back before the gate is asked for their probabilities in one call
     uint32_t input_sample_rate = 16000; std::string input_resample_mode = "linear";   // linear (the audio::resampler node's rubato arithmetic, bit for bit) | polyphase
@@ -119,6 +122,12 @@ bool parse_config(const char* json, WhisperConfig* cfg, std::string* err) {
         if (x && x->type == skw::JsonValue::String) { if (x->str != "auto") { *err = "Invalid config: gpu_device must be an integer or \"auto\""; return false; } cfg->gpu_device_auto = true; }
         else { d = cfg->gpu_device; if (!num("gpu_device", &d)) return false; if (d != std::floor(d)) { *err = "Invalid config: gpu_device must be an integer";
         return false; } cfg->gpu_device = (int)d; }
+    }
+    {   // audio_ctx: an integer, or the string "auto"
+        const skw::JsonValue* x = v.get("audio_ctx");
+        if (x && x->type == skw::JsonValue::String) { if (x->str != "auto") { *err = "Invalid config: audio_ctx must be an integer or \"auto\""; return false; } cfg->audio_ctx_auto = true; }
+        else { d = cfg->audio_ctx; if (!num("audio_ctx", &d)) return false;
+               if (d != std::floor(d) || std::fabs(d) > 1e6) { *err = "Invalid config: audio_ctx must be an integer or \"auto\""; return false; } cfg->audio_ctx = (int)d; }
     }
     d = cfg->batch_window_ms; if (!num("batch_window_ms", &d)) return false; cfg->batch_window_ms = (int)d;
     d = cfg->max_batch; if (!num("max_batch", &d)) return false; cfg->max_batch = std::max(1, (int)d);
@@ -170,6 +179,7 @@ struct SharedEngine {
     int batch_limit = 64;       // scheduler: largest batch formed (the max_batch param of the instance created most recently; under mu)
     int window_ms = 2;          // scheduler: how long a batch waits for more jobs (batch_window_ms of the instance created most recently; under mu)
     bool multilingual = true;   // the model has language tokens (n_vocab >= 51865); set once at load
+    int n_audio_ctx = 1500;     // the model's encoder positions (what audio_ctx "auto" is capped at); set once at load
     bool mixed = true;          // scheduler: jobs join a batch whatever their parameters (mixed_batch of the instance created most recently; under mu)
     int precision = SKW_PRECISION_EXACT;
     static const int kMaxSamples = 16000 * 121;   // schema maximum of max_segment_duration_secs (120 s) + one VAD frame of slack: no segment is longer
@@ -339,7 +349,7 @@ std::shared_ptr<SharedEngine> get_engine(const WhisperConfig& cfg, WhisperPlugin
     eng->model = skw_model_load(cfg.model_path.c_str(), cfg.gpu_device, ebuf, sizeof ebuf);
     if (!eng->model) { *err = ebuf[0] ? ebuf : ("Failed to load Whisper model from '" + cfg.model_path + "'"); return nullptr; }
     g_model_loads.fetch_add(1);
-    { skw_hparams hp{}; skw_model_get_hparams(eng->model, &hp); eng->multilingual = hp.n_vocab >= 51865; }
+    { skw_hparams hp{}; skw_model_get_hparams(eng->model, &hp); eng->multilingual = hp.n_vocab >= 51865; eng->n_audio_ctx = hp.n_audio_ctx; }
     const auto t1 = std::chrono::steady_clock::now();
     eng->batch_limit = cfg.max_batch;
     eng->window_ms = cfg.batch_window_ms; eng->mixed = cfg.mixed_batch;
@@ -483,6 +493,8 @@ bool transcribe_and_emit(WhisperPlugin* self, const Emit& em, const skw::Segment
     job->params.lang_id = lang; job->params.translate = 0;
     job->params.suppress_blank = self->config.suppress_blank ? 1 : 0; job->params.suppress_nst = self->config.suppress_non_speech_tokens ? 1 : 0;
     job->params.n_threads = (int32_t)self->config.n_threads;
+    // (additive) the segment's audio context: what its instance is configured for now (update_params takes effect from the next segment); "auto" = the exported rule on its length
+    job->params.audio_ctx = self->config.audio_ctx_auto ? skw_audio_ctx_for_samples((int)job->n, self->engine->n_audio_ctx) : self->config.audio_ctx;
     job->rng = self->rng;
     if ((int)job->n > SharedEngine::kMaxSamples) { *err = "Whisper inference failed: segment longer than the engine workspace"; return false; }
     std::future<int> fut = job->done.get_future();
@@ -551,6 +563,7 @@ const char* const kSchema =
     "\"precision\":{\"type\":\"string\",\"description\":\"(additive) exact (f32-chain contractions, bit-reproducible; block-quantised model files run ggml's q8 arithmetic) | f16_mfma (f16 matrix cores; quantised files as their f16 twin)\",\"default\":\"exact\"},"
     "\"batch_window_ms\":{\"type\":\"integer\",\"description\":\"(additive) how long the per-GPU scheduler waits for concurrent instances before launching a batch\",\"default\":2},"
     "\"max_batch\":{\"type\":\"integer\",\"description\":\"(additive) largest number of segments transcribed in one GPU batch\",\"default\":64},"
+    "\"audio_ctx\":{\"type\":[\"integer\",\"string\"],\"description\":\"(additive) whisper.cpp's audio_ctx per segment: 0 = the model's 1500 positions (30 s); N = encode and attend only N positions (20 ms each: the audio beyond N/50 s is not heard); \\\"auto\\\" = the positions the segment covers + 0.5 s, in 32-position blocks. Segments with different values share a batch\",\"default\":0},"
     "\"mixed_batch\":{\"type\":\"boolean\",\"description\":\"(additive) segments of instances with different language / suppress_* settings share one GPU batch; false cuts a batch at the first differing job\",\"default\":true},"
     "\"flush_tail\":{\"type\":\"boolean\",\"description\":\"(additive) transcribe buffered speech when the input stream ends (the reference drops it)\",\"default\":false},"
     "\"input_sample_rate\":{\"type\":\"integer\",\"description\":\"(additive) sample rate of the mono f32 packets fed to this node; anything but 16000 is resampled to 16 kHz on the GPU with the audio::resampler node's arithmetic (chunk_frames 960) before VAD segmentation\",\"default\":16000,\"minimum\":1000,\"maximum\":768000},"

@@ -22,7 +22,8 @@ class FullParams(C.Structure):
                 ("no_timestamps", C.c_int32), ("single_segment", C.c_int32), ("max_tokens", C.c_int32),
                 ("max_initial_ts", C.c_float), ("entropy_thold", C.c_float), ("logprob_thold", C.c_float),
                 ("no_speech_thold", C.c_float), ("n_threads", C.c_int32),
-                ("temperature", C.c_float), ("temperature_inc", C.c_float)]
+                ("temperature", C.c_float), ("temperature_inc", C.c_float),
+                ("audio_ctx", C.c_int32)]      # 0 = the model's n_audio_ctx; K: the clip is encoded and attended over K positions (whisper_full_params.audio_ctx)
 
 
 class Segment(C.Structure):
@@ -99,6 +100,10 @@ def lib():
         L.skw_conv_stem.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.skw_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.skw_decode_logits.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.skw_conv_stem_actx.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.skw_encode_actx.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.skw_audio_ctx_for_samples.argtypes = [C.c_int, C.c_int]
+        L.skw_ctx_kernel_clock_keys.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.skw_dsp_create.restype = C.c_void_p
         L.skw_dsp_create.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
         L.skw_dsp_free.argtypes = [C.c_void_p]
@@ -151,6 +156,11 @@ def _result_to_dict(r):
         segs = [dict(t0=t0, t1=t1, tokens=[t[0] for t in toks[b:e]], text=text[o:o + n]) for (t0, t1, b, e, o, n) in sg]
     return dict(segments=segs, tokens=toks, n_windows=r.n_windows, n_decode_steps=r.n_decode_steps,
                 fallback_requested=r.fallback_requested, min_margin=r.min_margin, lang_id=r.lang_id)
+
+
+def audio_ctx_for_samples(n_samples, n_audio_ctx=1500):
+    """The "auto" rule for FullParams.audio_ctx (skw_audio_ctx_for_samples): the positions the audio covers, half a second of margin, whole 32-key blocks.  No GPU needed."""
+    return lib().skw_audio_ctx_for_samples(int(n_samples), int(n_audio_ctx))
 
 
 def rng_state_new():
@@ -299,6 +309,12 @@ class Context:
         self._check(lib().skw_ctx_kernel_clock_get(self.h, C.byref(n), C.byref(su), C.byref(sl), C.byref(mn), C.byref(mx), C.byref(khz)))
         return dict(launches=n.value, sum_us=su.value, sum_live_rows=sl.value, min_us=mn.value, max_us=mx.value, clock_khz=khz.value)
 
+    def kernel_clock_keys(self):
+        """keys walked by the recorded launches, summed over their live rows (algorithmic bytes = 4 B x this x n_text_state)"""
+        sk = C.c_double()
+        self._check(lib().skw_ctx_kernel_clock_keys(self.h, C.byref(sk)))
+        return sk.value
+
     def kernel_clock_records(self, cap=65536):
         """[(begin us, end us, live rows)] of every launch the last call recorded"""
         out = np.zeros((cap, 3), np.float64)
@@ -319,23 +335,35 @@ class Context:
         self._check(lib().skw_log_mel(self.h, pcm.ctypes.data, pcm.size, out.ctypes.data, cap, C.byref(n_len), C.byref(n_org)))
         return out[:hp.n_mels * n_len.value].reshape(hp.n_mels, n_len.value).copy(), n_org.value
 
-    def conv_stem(self, pcm, seek=0):
+    def conv_stem(self, pcm, seek=0, audio_ctx=None):
+        """audio_ctx=K (skw_conv_stem_actx; 0 = n_audio_ctx): the stem at K positions, [K][n_state]; None: the existing tap"""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         hp = self.model.hp
-        out = np.empty((hp.n_audio_ctx, hp.n_audio_state), dtype=np.float32)
-        self._check(lib().skw_conv_stem(self.h, pcm.ctypes.data, pcm.size, seek, out.ctypes.data))
+        if audio_ctx is None:
+            out = np.empty((hp.n_audio_ctx, hp.n_audio_state), dtype=np.float32)
+            self._check(lib().skw_conv_stem(self.h, pcm.ctypes.data, pcm.size, seek, out.ctypes.data))
+            return out
+        K = audio_ctx if 0 < audio_ctx <= hp.n_audio_ctx else hp.n_audio_ctx      # (the buffer's size; the library refuses what is out of range)
+        out = np.empty((K, hp.n_audio_state), dtype=np.float32)
+        self._check(lib().skw_conv_stem_actx(self.h, pcm.ctypes.data, pcm.size, seek, int(audio_ctx), out.ctypes.data))
         return out
 
-    def encode(self, pcm, seek=0, cross=True):
+    def encode(self, pcm, seek=0, cross=True, audio_ctx=None):
+        """audio_ctx=K (skw_encode_actx; 0 = n_audio_ctx): encoder output [K][n_state] and cross K / V [n_text_layer][K][n_state]; decode_logits then follows that K"""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         hp = self.model.hp
-        enc = np.empty((hp.n_audio_ctx, hp.n_audio_state), dtype=np.float32)
+        K = hp.n_audio_ctx if audio_ctx is None or not 0 < audio_ctx <= hp.n_audio_ctx else audio_ctx
+        enc = np.empty((K, hp.n_audio_state), dtype=np.float32)
         ck = cv = None
         if cross:
-            ck = np.empty((hp.n_text_layer, hp.n_audio_ctx, hp.n_text_state), dtype=np.float32)
+            ck = np.empty((hp.n_text_layer, K, hp.n_text_state), dtype=np.float32)
             cv = np.empty_like(ck)
-        self._check(lib().skw_encode(self.h, pcm.ctypes.data, pcm.size, seek, enc.ctypes.data,
-                                     ck.ctypes.data if cross else None, cv.ctypes.data if cross else None))
+        if audio_ctx is None:
+            self._check(lib().skw_encode(self.h, pcm.ctypes.data, pcm.size, seek, enc.ctypes.data,
+                                         ck.ctypes.data if cross else None, cv.ctypes.data if cross else None))
+        else:
+            self._check(lib().skw_encode_actx(self.h, pcm.ctypes.data, pcm.size, seek, int(audio_ctx), enc.ctypes.data,
+                                              ck.ctypes.data if cross else None, cv.ctypes.data if cross else None))
         return enc, ck, cv
 
     def decode_logits(self, tokens):

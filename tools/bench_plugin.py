@@ -38,6 +38,8 @@ def main():
     ap.add_argument("--vad-model", default=None, help="Silero .onnx file (default: the seeded file of tools/make_synth_silero.py)")
     ap.add_argument("--vad-device", default=None, choices=["cpu", "gpu"], help="the node's vad_device (not sent when absent)")
     ap.add_argument("--vad-batch-frames", type=int, default=None, help="the node's vad_batch_frames (not sent when absent)")
+    ap.add_argument("--audio-ctx", default=None, help="the node's audio_ctx: 0, an integer 1..n_audio_ctx, or auto (not sent when absent)")
+    ap.add_argument("--clip-s", default="30", help="clip length in seconds: one number, or lo-hi for lengths spread evenly over the instances (e.g. 1-9)")
     a = ap.parse_args()
     assert 1 <= a.param_sets <= 16 and a.reps >= 1
     tree = os.path.abspath(a.tree)
@@ -50,7 +52,8 @@ def main():
     batch_stats = getattr(minihost, "whisper_batch_stats", None)
     path = synth_model(a.size)
     plug = minihost.Plugin()
-    pcms = [synth.clip(c) for c in range(a.clips)]
+    lo, hi = (float(x) for x in (a.clip_s.split("-") if "-" in a.clip_s else (a.clip_s, a.clip_s)))
+    pcms = [synth.clip(c, int(16000 * (lo + (hi - lo) * (c * 7 % a.clips) / max(1, a.clips - 1)))) for c in range(a.clips)]
     gate = None
     if a.vad_mode != "always":
         pattern = ((20, 0.0), (60, 1.0), (30, 0.0), (40, 1.0), (50, 0.0))                    # frames on / off, as tests/silero_lib.speechlike
@@ -71,6 +74,7 @@ def main():
     params = {"model_path": path, "vad_mode": "always", "flush_tail": True, "max_batch": a.clips, "batch_window_ms": a.batch_window_ms, "precision": a.precision,
               "mixed_batch": bool(a.mixed_batch)}
     if gate: params.update(gate)
+    if a.audio_ctx is not None: params["audio_ctx"] = "auto" if a.audio_ctx == "auto" else int(a.audio_ctx)
     langs = ["en", "de", "es", "fr"]
     sets = [{"language": langs[k % 4], "suppress_non_speech_tokens": not (k // 4) & 1, "suppress_blank": not (k // 8) & 1} for k in range(a.param_sets)]
     best = None; walls = []; stats0 = None
@@ -103,7 +107,7 @@ def main():
             gate_report.update(speech_frame_share=round(n_speech / n_frames, 4), transcribed_audio_s=round(n_speech * 0.032, 1))
     print(json.dumps({"what": "plugin-level Oneshot batch (host PCM -> Transcription JSON), %d instances" % a.clips, "value": round(audio_s / (best * 1e-3), 1), "unit": "x real-time",
                       "wall_ms": round(best, 2), "packet_samples": a.packet, "batch_window_ms": a.batch_window_ms, "segments": n_seg, "model": a.size, "precision": a.precision,
-                      "wall_ms_reps": walls, "param_sets": a.param_sets, "mixed_batch": a.mixed_batch,
+                      "wall_ms_reps": walls, "param_sets": a.param_sets, "mixed_batch": a.mixed_batch, "audio_ctx": a.audio_ctx, "clip_s": a.clip_s,
                       "batch_stats": dict(zip(("engine_calls", "jobs", "mixed_calls"), [x - y for x, y in zip(batch_stats(), stats0)])) if batch_stats else None,
                       "gate": gate_report, "tree": os.path.relpath(tree, ROOT)}))
 

@@ -21,6 +21,7 @@ def main():
     ap.add_argument("--utterance-s", type=float, default=4.0); ap.add_argument("--gap-s", type=float, default=1.0); ap.add_argument("--batch-window-ms", type=float, default=2.0)
     ap.add_argument("--stagger-ms", type=float, default=0.0, help="offset between the streams' utterance boundaries (0 = all streams end segments together)")
     ap.add_argument("--precision", default="f16_mfma", choices=["exact", "f16_mfma"])
+    ap.add_argument("--audio-ctx", default=None, help="the node's audio_ctx: 0, an integer 1..n_audio_ctx, or auto (not sent when absent)")
     a = ap.parse_args()
     import torch  # noqa: F401
     from streamkit_amd import minihost
@@ -38,6 +39,7 @@ def main():
             x[pos:pos + ut] = synth.clip(100 * i + k, ut); pos += ut + gap; k += 1
         pcms.append(x)
     params = {"model_path": path, "vad_mode": "energy", "min_silence_duration_ms": 500, "batch_window_ms": a.batch_window_ms, "max_batch": max(8, a.streams), "precision": a.precision}
+    if a.audio_ctx is not None: params["audio_ctx"] = "auto" if a.audio_ctx == "auto" else int(a.audio_ctx)
     warm = plug.create_node(params); warm.process_audio(pcms[0][:ut + gap]); warm.destroy()          # model load + first-use costs outside the measurement
     nodes = [plug.create_node(params) for _ in range(a.streams)]
     n = a.streams; max_lat = 64
@@ -49,7 +51,8 @@ def main():
     for x in nodes: x.destroy()
     print(json.dumps({"what": "Dynamic sessions: %d paced streams on one GPU, %.0f s each, %.1f s utterances" % (n, a.seconds, a.utterance_s), "segments": int(ls.size),
                       "latency_ms": {"p50": round(float(np.percentile(ls, 50)), 1), "p95": round(float(np.percentile(ls, 95)), 1), "max": round(float(ls.max()), 1)},
-                      "aggregate_rtf": round(n * a.seconds / (wall.value * 1e-3), 2), "wall_s": round(wall.value * 1e-3, 2), "batch_window_ms": a.batch_window_ms, "stagger_ms": a.stagger_ms, "model": a.size}))
+                      "aggregate_rtf": round(n * a.seconds / (wall.value * 1e-3), 2), "wall_s": round(wall.value * 1e-3, 2), "batch_window_ms": a.batch_window_ms, "stagger_ms": a.stagger_ms, "model": a.size,
+                      "audio_ctx": a.audio_ctx}))
 
 
 if __name__ == "__main__":
