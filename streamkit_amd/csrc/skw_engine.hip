@@ -1943,8 +1943,97 @@ extern "C" int skw_debug_gemm16_out(skw_ctx* c, int kernel, int M, int N, int K,
     return 0;
 }
 
+// tests (tests/test_gpu_attn16.py): one f16_mfma attention launcher on host-supplied operands, to be held to a float64 softmax(Q K^T) V kernel by kernel.  Q [rows][H*64], K / V
+// [slot][n_ctx][H*64] arrive as f16 bit patterns in NATURAL order; this packs them into what the kernel reads (per-head rows of stride Tpad, V^T, the fragment-order images), launches
+// through the public launcher (the template dispatch is part of what is tested) and returns the output un-permuted as f32 [rows][H*64].
+//   form 0  skw_attn_encoder16: Q is [slot][n_ctx][H*64]; slot_k null: out rows = n_slots * n_ctx; given: n_slots * out_rows (out_rows 0: n_ctx)
+//   form 1  skw_xattn_prefill16: n_seq sequences (row0, nq, slot), frag = flags & 1, ofrag = flags & 2, slot_k null or [n_slots]
+//   form 2  skw_dec_cross_attn_vt, pv16 = 2 (one pass over the fragment-order images), ofrag = flags & 2;   form 3  the same, pv16 = 1 (two phases over the row layouts)
+//           active / seq / count (= n_keys) are [rows] or null and reach the kernel as fields of a SkwSeqState array (its stride is the launchers' contract)
+//   form 4  skw_dec_self_attn, fastv = 1: K / V are the caches [slot][n_ctx = n_text_ctx][H*64], count = pos [rows] (required), ofrag = flags & 2
+// Pad: every K position of slot s from fill_from[s] up (to Tpad where the layout has a Tpad) holds the bit pattern k_pad, every V position v_pad — what the kernel must not use is the
+// caller's to poison.  The output buffer starts as `sentinel` in every half, so rows the kernel must leave alone (inactive, past nq, past a slot's queries) are visible.
+extern "C" int skw_debug_attn16(skw_ctx* c, int form, int H, int n_ctx, int n_slots, int rows, int flags, int out_rows, const uint16_t* Q_host, const uint16_t* K_host,
+                                const uint16_t* V_host, const int* fill_from, int k_pad, int v_pad, const int* slot_k, int n_seq, const int* row0, const int* nq, const int* slot,
+                                const int* active, const int* seq, const int* count, int sentinel, float* out_host) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_attn16: %s", what); return -1; };
+    if (form < 0 || form > 4 || H < 1 || H > 32 || n_ctx < 1 || n_ctx > 4096 || n_slots < 1 || n_slots > 64 || rows < 1 || rows > 65536 || !fill_from) return bad("bad geometry");
+    const int d = H * 64, Tpad = (n_ctx + 31) & ~31, frag = flags & 1, ofrag = (flags >> 1) & 1;
+    for (int s = 0; s < n_slots; ++s) if (fill_from[s] < 0 || fill_from[s] > n_ctx) return bad("fill_from outside [0, n_ctx]");
+    int orows = rows, nq_max = 0;
+    if (form == 0) {
+        orows = n_slots * (slot_k && out_rows ? out_rows : n_ctx);
+        if (slot_k) for (int s = 0; s < n_slots; ++s) if ((out_rows ? out_rows : n_ctx) < std::min(n_ctx, std::max(1, slot_k[s]))) return bad("out_rows below a slot's query count");
+        if (ofrag || frag) return bad("the encoder form has no frag / ofrag");
+    } else if (form == 1) {
+        if (n_seq < 1 || n_seq > 64 || !row0 || !nq || !slot) return bad("the prompt pass needs row0 / nq / slot");
+        for (int i = 0; i < n_seq; ++i) {
+            if (row0[i] < 0 || nq[i] < 0 || row0[i] + nq[i] > rows || slot[i] < 0 || slot[i] >= n_slots) return bad("a sequence's rows or slot lie outside the buffers");
+            nq_max = std::max(nq_max, nq[i]);
+        }
+        if (nq_max < 1) return bad("no queries");
+    } else {
+        if (form == 3 && n_ctx > 24 * 64) return bad("the two-phase kernel holds at most 1536 keys");
+        if (form == 4 && (n_ctx > 7 * 64 || !count)) return bad("the self-attention form needs pos and n_text_ctx <= 448");
+        if (form == 4 && !skw_sw(SW_DEC_ATTN_FASTV)) return bad("SKW_DEC_ATTN_FASTV is off: the launcher would not reach the FASTV form");
+        if (frag || (ofrag && form == 3)) return bad("flag does not apply to this form");
+        for (int b = 0; b < rows; ++b) {
+            const int s = seq ? seq[b] : b;
+            if (s < 0 || s >= n_slots) return bad("a row's sequence lies outside the slots");
+            if (form == 4 && (count[b] < 0 || count[b] >= n_ctx)) return bad("pos outside the cache");
+        }
+    }
+    const int kfrag = (form == 1 && frag) || form == 2, vfrag = kfrag, kheads = form == 0, vrows = form == 4;      // which layouts this form reads
+    const int kkeys = (kfrag || kheads) ? Tpad : n_ctx, vkeys = vrows ? n_ctx : Tpad;
+    const size_t nQ = form == 0 ? (size_t)n_slots * Tpad * d : (size_t)rows * d, nK = (size_t)n_slots * kkeys * d, nV = (size_t)n_slots * vkeys * d;
+    const size_t nO = (size_t)(ofrag ? (orows + 15) & ~15 : orows) * d;
+    std::vector<uint16_t> q(nQ, (uint16_t)k_pad), k(nK, (uint16_t)k_pad), v(nV, (uint16_t)v_pad), o(nO, (uint16_t)sentinel);
+    if (form == 0) { for (int s = 0; s < n_slots; ++s) for (int i = 0; i < n_ctx; ++i) for (int n = 0; n < d; ++n)
+                         q[(((size_t)s * H + (n >> 6)) * Tpad + i) * 64 + skw_kperm(n & 63)] = Q_host[((size_t)s * n_ctx + i) * d + n]; }
+    else memcpy(q.data(), Q_host, nQ * 2);
+    for (int s = 0; s < n_slots; ++s) for (int i = 0; i < fill_from[s]; ++i) for (int n = 0; n < d; ++n) {
+        const uint16_t kv = K_host[((size_t)s * n_ctx + i) * d + n], vv = V_host[((size_t)s * n_ctx + i) * d + n];
+        const int p = skw_kperm(i);
+        if (kheads) k[(((size_t)s * H + (n >> 6)) * Tpad + i) * 64 + skw_kperm(n & 63)] = kv;
+        else if (kfrag) k[skw_kfrag_off(s, H, Tpad, i, n & ~7) + (n & 7)] = kv;
+        else k[((size_t)s * n_ctx + i) * d + n] = kv;
+        if (vrows) v[((size_t)s * n_ctx + i) * d + n] = vv;
+        else if (vfrag) v[skw_vtfrag_off(s, H, Tpad, n, p & ~7) + (p & 7)] = vv;
+        else v[((size_t)s * d + n) * Tpad + p] = vv;
+    }
+    std::vector<SkwSeqState> st(rows); memset((void*)st.data(), 0, sizeof(SkwSeqState) * rows);
+    if (form >= 2) for (int b = 0; b < rows; ++b) {
+        st[b].active = active ? active[b] : 1; st[b].pad = seq ? seq[b] : b; st[b].cur_pos = form == 4 ? count[b] : 0; st[b].n_keys = (form != 4 && count) ? count[b] : 0;
+    }
+    half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr; SkwSeqState* dst = nullptr; int* dmeta = nullptr;
+    auto cleanup = [&]() { hipFree(dq); hipFree(dk); hipFree(dv); hipFree(dout); hipFree(dst); hipFree(dmeta); };
+    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_attn16: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
+    if (!chk(hipMalloc((void**)&dq, nQ * 2)) || !chk(hipMalloc((void**)&dk, nK * 2)) || !chk(hipMalloc((void**)&dv, nV * 2)) || !chk(hipMalloc((void**)&dout, nO * 2))) return -1;
+    if (!chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * rows)) || !chk(hipMalloc((void**)&dmeta, sizeof(int) * (3 * 64 + 64)))) return -1;
+    if (!chk(hipMemcpy(dq, q.data(), nQ * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dk, k.data(), nK * 2, hipMemcpyHostToDevice))) return -1;
+    if (!chk(hipMemcpy(dv, v.data(), nV * 2, hipMemcpyHostToDevice))) return -1;
+    if (!chk(hipMemcpy(dout, o.data(), nO * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * rows, hipMemcpyHostToDevice))) return -1;
+    int meta[4 * 64] = {0};      // row0 | nq | slot | slot_k
+    if (form == 1) for (int i = 0; i < n_seq; ++i) { meta[i] = row0[i]; meta[64 + i] = nq[i]; meta[128 + i] = slot[i]; }
+    if (slot_k) for (int s = 0; s < n_slots; ++s) meta[192 + s] = slot_k[s];
+    if (!chk(hipMemcpy(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice))) return -1;
+    const int* dslot_k = slot_k ? dmeta + 192 : nullptr;
+    if (form == 0) skw_attn_encoder16(dq, dk, dv, dout, d, n_slots, H, n_ctx, Tpad, c->stream, dslot_k, out_rows);
+    else if (form == 1) skw_xattn_prefill16(dq, dk, dv, dout, n_seq, nq_max, dmeta, dmeta + 64, dmeta + 128, H, d, n_ctx, Tpad, c->stream, frag, ofrag, dslot_k);
+    else if (form == 4) skw_dec_self_attn(dq, dk, dv, &dst[0].cur_pos, rows, H, d, n_ctx, dout, active ? &dst[0].active : nullptr, c->stream, 0, SkwQ8Out{nullptr, nullptr, nullptr, 0},
+                                          seq ? &dst[0].pad : nullptr, 1, ofrag);
+    else skw_dec_cross_attn_vt(dq, dk, dv, rows, H, d, n_ctx, Tpad, dout, active ? &dst[0].active : nullptr, c->stream, 0, form == 2 ? 2 : 1, seq ? &dst[0].pad : nullptr, nullptr, nullptr,
+                               ofrag, nullptr, count ? &dst[0].n_keys : nullptr);
+    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(o.data(), dout, nO * 2, hipMemcpyDeviceToHost))) return -1;
+    cleanup();
+    for (int r = 0; r < orows; ++r) for (int n = 0; n < d; ++n)
+        out_host[(size_t)r * d + n] = skw_f16_to_f32(o[ofrag ? (size_t)skw_afrag_off(r, skw_kperm(n), d) : (size_t)r * d + skw_kperm(n)]);
+    return 0;
+}
+
 // the launch clock's records (SkwKClk, skw_kernels.h): one clock per (row group, decoder layer) graph node
-static const int KCLK_CAP = 1024;                                       // launches recorded per node and call (a 30 s window is <= 466 steps)
+static const int KCLK_CAP = 1024;                                      // launches recorded per node and call (a 30 s window is <= 466 steps)
 static size_t kclk_node_bytes() { return sizeof(SkwKClk) + sizeof(SkwKClkRec) * SKW_KCLK_SHARDS * (KCLK_CAP - 1); }
 // one launch's record: the maxima over its shards; false when no live workgroup stamped it
 static bool kclk_launch(const SkwKClk* k, int j, unsigned long long* t0, unsigned long long* t1, unsigned* live) {

@@ -134,6 +134,7 @@ def lib():
         L.skw_debug_switch_default.argtypes = [C.c_int]
         L.skw_debug_switch_get.argtypes = [C.c_char_p]
         L.skw_debug_switch_set.argtypes = [C.c_char_p, C.c_int]
+        L.skw_debug_attn16.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -395,6 +396,40 @@ class Context:
         self._check(fn(self.h, p if per_row else C.byref(p), R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
                        filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data))
         return toks, tr, filt
+
+    ATTN16_FORMS = {"encoder": 0, "prefill": 1, "cross16": 2, "cross2p": 3, "self": 4}
+
+    def attn16(self, form, H, n_ctx, Q, K, V, fill_from, k_pad=0x7E00, v_pad=0x7E00, frag=0, ofrag=0, slot_k=None, out_rows=0, row0=None, nq=None, slot=None,
+               active=None, seq=None, count=None, sentinel=0x5A5A):
+        """One f16_mfma attention launcher on caller-supplied operands (skw_debug_attn16, skw_engine.hip).  Q [rows][H*64], K / V [slots][n_ctx][H*64] as float16 (or their
+        uint16 bit patterns) in natural order; every K / V position of slot s from fill_from[s] up holds the bit pattern k_pad / v_pad when the kernel runs; the output buffer
+        starts as `sentinel` in every half.  form: "encoder" (slot_k, out_rows), "prefill" (row0, nq, slot per sequence; frag, ofrag, slot_k), "cross16" / "cross2p" (the one-pass
+        and the two-phase decode kernels; active, seq, count = n_keys per row; ofrag) or "self" (count = pos per row; active, seq; ofrag).  -> f32 [rows][H*64], natural order."""
+        d = H * 64
+        bits = lambda a: np.ascontiguousarray(a.view(np.uint16) if a.dtype == np.float16 else a, dtype=np.uint16)
+        ints = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        Q = bits(Q); K = bits(K); V = bits(V)
+        n_slots = K.shape[0]
+        assert K.shape == (n_slots, n_ctx, d) and V.shape == K.shape and Q.shape[-1] == d
+        f = self.ATTN16_FORMS[form]
+        rows = 1 if f == 0 else Q.shape[0]
+        if f == 0:
+            assert Q.shape == K.shape
+            orows = n_slots * (out_rows if (slot_k is not None and out_rows) else n_ctx)
+        else:
+            orows = rows
+        fill_from, slot_k, row0, nq, slot, active, seq, count = (ints(a) for a in (fill_from, slot_k, row0, nq, slot, active, seq, count))
+        assert fill_from.size == n_slots and (slot_k is None or slot_k.size == n_slots)
+        for a in (active, seq, count):
+            assert a is None or a.size == rows
+        n_seq = 0 if row0 is None else row0.size
+        assert n_seq == 0 or (nq.size == n_seq and slot.size == n_seq)
+        out = np.empty((orows, d), dtype=np.float32)
+        self._check(lib().skw_debug_attn16(self.h, f, H, n_ctx, n_slots, rows, (1 if frag else 0) | (2 if ofrag else 0), int(out_rows), Q.ctypes.data, K.ctypes.data, V.ctypes.data,
+                                           fill_from.ctypes.data, int(k_pad), int(v_pad), ptr(slot_k), n_seq, ptr(row0), ptr(nq), ptr(slot), ptr(active), ptr(seq), ptr(count),
+                                           int(sentinel), out.ctypes.data))
+        return out
 
     def math(self, kind, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
