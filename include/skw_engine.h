@@ -101,6 +101,10 @@ int skw_model_quant_type(const skw_model* m);
 void skw_model_free(skw_model*);
 void skw_model_get_hparams(const skw_model*, skw_hparams* out);
 const char* skw_model_token_text(const skw_model*, int id, int* len);
+/* whisper_tokenize: text -> token ids with whisper.cpp's tokenizer (a regex split into words, then inside each word the longest vocabulary entry at every position; only ids
+ * below <|endoftext|> take part).  Returns the count, or -needed when cap is too small (ids then holds nothing meaningful).  Nothing is put in front of the text: openai's
+ * reference prepends a space to an initial prompt (" " + prompt.strip()), whisper.cpp and this function do not.  Host code (streamkit_amd/csrc/skw_tokenizer.h); needs no device. */
+int skw_model_tokenize(const skw_model*, const char* text, int32_t* ids, int cap);
 int  skw_model_lang_id(const char* lang); /* whisper_lang_id; -1 if unknown */
 
 skw_ctx* skw_ctx_create(skw_model*, int max_batch, int max_samples_per_clip, char* err, size_t errlen);
@@ -154,6 +158,19 @@ int  skw_full_batch_rng(skw_ctx*, const skw_full_params*, const float* const* pc
  * segments through this call whatever their parameters (the reference sets language and the suppress_* flags per instance, lib.rs:624-641). */
 int  skw_full_batch_mixed(skw_ctx*, const skw_full_params* params /* [n_clips] */, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                           uint32_t* const* rng_state /* NULL, or [n_clips] with entries that may be NULL */, skw_result* results);
+/* Text that conditions decoding: an initial prompt (whisper_full_params.initial_prompt / prompt_tokens) and the context whisper.cpp carries from one whisper_full_with_state call
+ * of a state to the next (no_context = false: the state's prompt_past survives the call).  skw_full_batch_context is skw_full_batch_mixed with that token list handed in and out
+ * per clip, the way rng_state hands the generator in and out.
+ *   in   context[i][0] = n in 0 .. 512, context[i][1 .. n] = token ids, oldest first: whisper_state::prompt_past as it stands when whisper_full_with_state enters its window loop
+ *        (the host has done the no_context clear and has put the initial prompt's tokens in front).  Every window — the first included — then follows the engine's one rule:
+ *        a pass at temperature < 0.5 decodes behind [prev] + the last min(n_text_ctx / 2, n, room) tokens; the language-detection pass takes none.
+ *   out  prompt_past as the call leaves it: what the last window's prompt took, then that window's kept tokens unless it was classed no-speech.  A clip too short to transcribe
+ *        leaves its context as it was.
+ * context = NULL or context[i] = NULL: an empty context that is not returned; such rows are skw_full_batch_mixed's, bit for bit and launch for launch.  n outside 0 .. 512 or an id
+ * outside [0, n_vocab) fails the call (naming the clip) before anything runs; a failed call writes no context back. */
+#define SKW_CONTEXT_WORDS 513   /* [0] = n in 0..512, [1..n] = token ids, oldest first: whisper_state::prompt_past */
+int  skw_full_batch_context(skw_ctx*, const skw_full_params* params /* [n_clips] */, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                            uint32_t* const* rng_state /* as skw_full_batch_mixed */, int32_t* const* context /* NULL, or [n_clips] with entries that may be NULL */, skw_result* results);
 
 /* ---- decision trace / teacher forcing (parity instrumentation of the hot path; the reference has no counterpart) ----
  * skw_full_batch_traced is skw_full_batch that also returns, per clip, one record for EVERY sampling decision it made, in execution order
@@ -170,6 +187,10 @@ typedef struct { int32_t n; skw_trace_step* steps; } skw_trace;
 int  skw_full_batch_traced(skw_ctx*, const skw_full_params*, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                            const int32_t* const* forced_ids /* [n_clips] or NULL */, const int32_t* n_forced /* [n_clips] or NULL */,
                            skw_trace* traces /* [n_clips] out; release with skw_trace_free */, skw_result* results);
+/* the same with each clip's context handed in and out as skw_full_batch_context does (context NULL, or [n_clips] with entries that may be NULL): teacher forcing of clips that decode
+ * behind carried text */
+int  skw_full_batch_traced_context(skw_ctx*, const skw_full_params*, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                                   const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, int32_t* const* context, skw_result* results);
 void skw_trace_free(skw_trace*);
 
 /* timing of the last skw_full_batch (milliseconds, GPU events on the engine's stream) */

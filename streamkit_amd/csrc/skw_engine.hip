@@ -7,6 +7,7 @@
 #include "../../include/skw_math.h"
 #include "../../include/skw_ggml_quant.h"
 #include "skw_kernels.h"
+#include "skw_tokenizer.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -69,6 +70,7 @@ struct skw_model {
     skw_hparams hp{};
     int device = 0;
     std::vector<std::string> tok_str;
+    SkwTokenizer tokz;      // text -> ids (skw_model_tokenize): the entries below <|endoftext|>
     int tok_eot, tok_sot, tok_translate, tok_transcribe, tok_solm, tok_prev, tok_nosp, tok_not, tok_beg;
     int tok_space = -1, tok_sp_dash = -1, tok_sp_quote = -1; std::vector<int> nst_ids; int n_lang = 99;
     // device
@@ -221,6 +223,7 @@ static skw_model* model_load_impl(const char* path, int device, int quant_mode, 
         else snprintf(buf, sizeof buf, "[_extra_token_%d]", i);
         m->tok_str[i] = buf;
     }
+    m->tokz.build(m->tok_str, m->tok_eot);
     { // token_to_id lookups performed by whisper_process_logits (a later duplicate string wins, as std::map::operator[] does)
         std::map<std::string, int> t2i; for (int i = 0; i < NV; ++i) t2i[m->tok_str[i]] = i;
         auto get = [&](const std::string& s) { auto it = t2i.find(s); return it == t2i.end() ? -1 : it->second; };
@@ -405,6 +408,9 @@ extern "C" const char* skw_model_token_text(const skw_model* m, int id, int* len
     if (id < 0 || id >= m->hp.n_vocab) { if (len) *len = 0; return ""; }
     if (len) *len = (int)m->tok_str[id].size(); return m->tok_str[id].c_str();
 }
+extern "C" int skw_model_tokenize(const skw_model* m, const char* text, int32_t* ids, int cap) {
+    try { return m->tokz.tokenize_into(text, ids, (ids && cap > 0) ? cap : 0); } catch (const std::exception&) { return 0; }      // (nothing may unwind across the C ABI)
+}
 // the "auto" audio context of a clip: the positions its audio covers (20 ms each), half a second of margin, whole 32-key blocks — never more than the model's context
 extern "C" int skw_audio_ctx_for_samples(int n_samples, int n_audio_ctx) {
     if (n_samples >= WHISPER_SAMPLE_RATE * WHISPER_CHUNK_SIZE) return n_audio_ctx;
@@ -507,6 +513,7 @@ struct skw_ctx {
     int max_tok = 0;
     // the prompt ([prev] + past text + sot / language / task) in one multi-row pass instead of one token per step; SKW_PROMPT_PASS=0 or skw_debug_set_prompt_pass(ctx, 0)
     int prompt_pass_on = 1;
+    int prompt_xattn_mq_on = 1;      // the exact precision's prompt pass: the 16-queries-per-workgroup cross attention (skw_debug_set_prompt_xattn_mq; same bits either way)
     int* pf_meta = nullptr; int pf_nseq = 0, pf_nq_max = 0;      // the pass's sequences on the device: [row0 | nq | slot] x max_batch (the multi-query cross attention of the f16_mfma prompt pass)
     int rows_cap = 0; SkwSeqState* pf_st = nullptr;  // decode-step scratch rows (>= max_batch: the prompt pass runs one row per prompt token) and the prompt pass's per-token pseudo-states
     int ln_stats_on = 1;                             // LayerNorm folded into the decode GEMMs (f16_mfma); SKW_DEC_LN_STATS=0 or skw_debug_set_ln_stats(ctx, 0): LayerNorm kernels
@@ -693,6 +700,8 @@ extern "C" int skw_debug_make_wfrag(const uint16_t* w_host, int N, int K, int pe
 // tests: f16_mfma cross K / V^T as fragment-order images (one-pass cross attention) / as rows (two-phase kernel); takes effect at the next encoder pass
 extern "C" void skw_debug_set_kv_frag(skw_ctx* c, int on) { c->kv_frag_on = on != 0; }
 extern "C" void skw_debug_set_prompt_pass(skw_ctx* c, int on) { c->prompt_pass_on = on != 0; }     // tests: the prompt as one pass / one token per step
+// tests / tools: the exact precision's prompt pass with the multi-query cross attention (default) or the single-query kernel on every prompt row
+extern "C" void skw_debug_set_prompt_xattn_mq(skw_ctx* c, int on) { c->prompt_xattn_mq_on = on != 0; }
 extern "C" void skw_debug_set_ln_stats(skw_ctx* c, int on) { c->ln_stats_on = on != 0; }      // tests: the decode step with / without the LayerNorm launches (f16_mfma)
 extern "C" void skw_debug_enable(int on) { g_taps_on = on != 0; g_taps.clear(); }
 extern "C" long skw_debug_get(const char* name, float* out, size_t cap) {
@@ -981,6 +990,9 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
     // per-clip audio context: the rows' key counts sit next to `active` in device memory, so a captured step holds none; null while every slot is full length (today's launches)
     const int* nkeys = c->var_k ? &st[0].n_keys : nullptr;
     const long kv_ld = prefill ? 0 : (long)ntc * dt;
+    // The prompt pass in the exact precision: one read of a sequence's cross K / V^T per 16 of its prompt tokens (k_xattn_prefill_exact) instead of one per token.  Every output is
+    // the single-query kernel's, bit for bit, so the cut below is a speed choice alone: passes whose longest prompt is shorter keep the single-query kernel on every row.
+    const bool xq_mq = prefill && c->precision == SKW_PRECISION_EXACT && c->prompt_xattn_mq_on && c->pf_nseq > 0 && c->pf_nq_max >= SKW_XATTN_MQ_MIN_NQ;
     if (use_q8(c)) {   // quantised file, exact precision: ggml's arithmetic (see run_encoder); the row group's q8 scratch starts at its first row
         float* dy32 = c->dy32 + (size_t)r0 * dt; float* datt32 = c->datt32 + (size_t)r0 * dt; float* dh32 = c->dh32 + (size_t)r0 * 4 * dt;
         skw_dec_embed_f32(m->te32, m->d_pe, &st[0].cur_token, &st[0].cur_pos, Bw, dt, dx, s);
@@ -998,6 +1010,8 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
             Q8_LN(c, dx, Bw, dt, L.cross_ln, r0, dy32);
             { SkwGemmArgs a = q8_args(Bw, dq16, dt, EPI_F16_PLAIN); a.scale = KQscale; a.has_scale = 1; Q8_GEMM(c, a, L.cq, r0, true); }
             { ProfScope p_(c, PC_DEC_XATTN, 4.0 * live * (double)nc * dt, 4.0 * live * (double)nc * dt);
+            if (!(xq_mq && skw_xattn_prefill_exact(dq16, ck, cv, (half_t*)datt32, c->pf_nseq, c->pf_nq_max, c->pf_meta, c->pf_meta + c->max_batch, c->pf_meta + 2 * c->max_batch, H, dt, nc,
+                                                   c->Tpad, s, 1, c->var_k ? c->slot_k : nullptr)))
             skw_dec_cross_attn_vt(dq16, ck, cv, Bw, H, dt, nc, c->Tpad, (half_t*)datt32, &st[0].active, s, 1, 0, seqp, nullptr, nullptr, 0, nullptr, nkeys); }
             Q8_ROWS(c, datt32, dt, Bw, dt, r0);
             { SkwGemmArgs a = q8_args(Bw, dx, dt, EPI_F32); a.res = dx; a.ldres = dt; Q8_GEMM(c, a, L.co, r0, true); }
@@ -1068,6 +1082,8 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
                 ProfScope p_(c, PC_DEC_XATTN, 4.0 * Bw * (double)nc * 64.0 * H, 4.0 * c->pf_nseq * (double)nc * dt);
                 skw_xattn_prefill16(dq16, ck, cv, datt16, c->pf_nseq, c->pf_nq_max, c->pf_meta, c->pf_meta + c->max_batch, c->pf_meta + 2 * c->max_batch, H, dt, nc, c->Tpad, s, c->kv_frag(), xa_frag,
                                     c->var_k ? c->slot_k : nullptr);
+            } else if (xq_mq && skw_xattn_prefill_exact(dq16, ck, cv, datt16, c->pf_nseq, c->pf_nq_max, c->pf_meta, c->pf_meta + c->max_batch, c->pf_meta + 2 * c->max_batch, H, dt, nc,
+                                                        c->Tpad, s, 0, c->var_k ? c->slot_k : nullptr)) {
             } else
             { ProfScope p_(c, PC_DEC_XATTN, 4.0 * live * (double)nc * dt, 4.0 * live * (double)nc * dt, true);
             skw_dec_cross_attn_vt(dq16, ck, cv, Bw, H, dt, nc, c->Tpad, datt16, &st[0].active, s, 0, c->kv_frag() ? 2 : c->precision == SKW_PRECISION_F16_MFMA, seqp, p_.ev_a(), p_.ev_b(), xa_frag,
@@ -1241,7 +1257,7 @@ static int move_retry_slots(skw_ctx* c, const std::vector<int>& old_slots) {
 // device memory (skw_dec_sample_rows).  Without pv every P(clip) is *p and the launches are the uniform ones.
 static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device, skw_result* results,
                            const int32_t* const* forced_ids, const int32_t* n_forced, std::vector<std::vector<SkwTraceStep>>* traces, uint32_t* const* rng_state = nullptr,
-                           const skw_full_params* pv = nullptr) {
+                           const skw_full_params* pv = nullptr, int32_t* const* context = nullptr) {
     char* errbuf = c->errbuf; errbuf[0] = 0;
     WS_READY(c);
     if (n_clips < 1 || n_clips > c->max_batch) { snprintf(errbuf, 512, "n_clips %d outside [1, %d]", n_clips, c->max_batch); return -1; }
@@ -1250,6 +1266,13 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
     for (int i = 0; i < n_clips; ++i) if (P(i).audio_ctx < 0 || P(i).audio_ctx > c->m->hp.n_audio_ctx) {
         snprintf(errbuf, 512, "clip %d: audio_ctx %d outside [0, %d] (0 = the model's n_audio_ctx)", i, P(i).audio_ctx, c->m->hp.n_audio_ctx); return -3; }
     auto K_of = [&](int ci) { return P(ci).audio_ctx > 0 ? P(ci).audio_ctx : c->m->hp.n_audio_ctx; };      // the clip's audio context, every window of it
+    // contexts handed in (skw_full_batch_context) are checked before anything is launched: a refused call leaves every context, like every generator state, as it was
+    if (context) for (int i = 0; i < n_clips; ++i) if (context[i]) {
+        const int32_t* cx = context[i]; const int n = cx[0];
+        if (n < 0 || n > SKW_CONTEXT_WORDS - 1) { snprintf(errbuf, 512, "clip %d: context of %d tokens outside [0, %d]", i, n, SKW_CONTEXT_WORDS - 1); return -3; }
+        for (int k = 0; k < n; ++k) if (cx[1 + k] < 0 || cx[1 + k] >= c->m->hp.n_vocab) {
+            snprintf(errbuf, 512, "clip %d: context token %d (id %d) outside [0, %d)", i, k, cx[1 + k], c->m->hp.n_vocab); return -3; }
+    }
     HIPCHK(hipSetDevice(c->m->device));
     const bool tracing = traces != nullptr;
     std::vector<int> f_cursor(n_clips, 0);      // tracing: decisions of clip i made so far (= its position in forced_ids[i])
@@ -1280,6 +1303,8 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
     std::vector<int> tidx(n_clips, 0), retry_slot(n_clips, -1);   // retry_slot: the window slot whose cross K/V a retrying clip left behind (-1: not retrying)
     // prompt_past (whisper_full_with_state): text already produced in this call conditions the next window of the same clip
     std::vector<std::vector<int>> prompt_past(n_clips); std::vector<int> last_take(n_clips, 0);
+    // a clip's context (skw_full_batch_context) is its prompt_past as whisper_full_with_state's window loop finds it: the first window takes from it under the rules of every later one
+    if (context) for (int i = 0; i < n_clips; ++i) if (context[i]) prompt_past[i].assign(context[i] + 1, context[i] + 1 + context[i][0]);
     // the sampled passes' generator: whisper.cpp keeps ONE std::mt19937 per state (decoder 0, seeded with 0 when the state is created) and lets it run on across calls.  A caller
     // that owns such a stream per clip (the plugin: one per instance, lib.rs:377-379) hands its state in and gets it back (skw_full_batch_rng); without one the stream starts at
     // seed 0 in every call (D2': what a batch of unrelated clips can do)
@@ -1555,6 +1580,11 @@ static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* co
         HIPCHK(hipMemcpyAsync(rng_state[i], c->rng + (size_t)i * SKW_RNG_WORDS, sizeof(uint32_t) * SKW_RNG_WORDS, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipGetLastError());          // a launch that failed (bad configuration, lost device) must not look like a transcript
+    // prompt_past as the call leaves it goes back to its owner (the newest SKW_CONTEXT_WORDS - 1 tokens: kept prompt + one window is below that for every n_text_ctx <= 512)
+    if (context) for (int i = 0; i < n_clips; ++i) if (context[i]) {
+        const std::vector<int>& pp = prompt_past[i]; const int n = std::min((int)pp.size(), SKW_CONTEXT_WORDS - 1);
+        context[i][0] = n; for (int k = 0; k < n; ++k) context[i][1 + k] = pp[pp.size() - n + k];
+    }
     for (int i = 0; i < n_clips; ++i) {
         skw_result& R = results[i]; SeqAcc& A = acc[i];
         R.n_segments = (int)A.seg.size(); R.n_tokens = (int)A.tok.size(); R.text_len = (int)A.text.size();
@@ -1590,14 +1620,21 @@ extern "C" int skw_full_batch_mixed(skw_ctx* c, const skw_full_params* params, c
         return full_batch_impl(c, params, pcm, n_samples, n_clips, pcm_on_device, results, nullptr, nullptr, nullptr, rng_state, params);
     } catch (const std::exception& e) { snprintf(c->errbuf, 512, "skw_full_batch_mixed: %s", e.what()); return -5; }
 }
-extern "C" int skw_full_batch_traced(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
-                                     const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, skw_result* results) {
+extern "C" int skw_full_batch_context(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                                      uint32_t* const* rng_state, int32_t* const* context, skw_result* results) {
+    try {
+        if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_context: params is NULL (one skw_full_params per clip)"); return -1; }
+        return full_batch_impl(c, params, pcm, n_samples, n_clips, pcm_on_device, results, nullptr, nullptr, nullptr, rng_state, params, context);
+    } catch (const std::exception& e) { snprintf(c->errbuf, 512, "skw_full_batch_context: %s", e.what()); return -5; }
+}
+extern "C" int skw_full_batch_traced_context(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                                             const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, int32_t* const* context, skw_result* results) {
     static_assert(sizeof(skw_trace_step) == sizeof(SkwTraceStep), "skw_trace_step is SkwTraceStep");
     try {
         if (!traces || (forced_ids && !n_forced)) { snprintf(c->errbuf, 512, "skw_full_batch_traced: bad arguments"); return -1; }
         for (int i = 0; i < n_clips; ++i) { traces[i].n = 0; traces[i].steps = nullptr; }
         std::vector<std::vector<SkwTraceStep>> tr(std::max(0, n_clips));
-        const int rc = full_batch_impl(c, p, pcm, n_samples, n_clips, pcm_on_device, results, forced_ids, n_forced, &tr);
+        const int rc = full_batch_impl(c, p, pcm, n_samples, n_clips, pcm_on_device, results, forced_ids, n_forced, &tr, nullptr, nullptr, context);
         if (rc) return rc;
         for (int i = 0; i < n_clips; ++i) {
             traces[i].n = (int32_t)tr[i].size(); traces[i].steps = (skw_trace_step*)malloc(sizeof(skw_trace_step) * std::max<size_t>(1, tr[i].size()));
@@ -1605,6 +1642,10 @@ extern "C" int skw_full_batch_traced(skw_ctx* c, const skw_full_params* p, const
         }
         return 0;
     } catch (const std::exception& e) { snprintf(c->errbuf, 512, "skw_full_batch_traced: %s", e.what()); return -5; }
+}
+extern "C" int skw_full_batch_traced(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                                     const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, skw_result* results) {
+    return skw_full_batch_traced_context(c, p, pcm, n_samples, n_clips, pcm_on_device, forced_ids, n_forced, traces, nullptr, results);
 }
 // Test hook (tests/test_gpu_logit_rules.py): K11 on its own.  n_rows decoders whose tokens sampled so far in their window are hist[r][0 .. n_hist[r]) meet
 // caller-supplied logits; ONE launch of the sampler (form 0: the one the decode step uses; form 1: the streaming kernel, which leaves the filtered row in
@@ -2029,6 +2070,53 @@ extern "C" int skw_debug_attn16(skw_ctx* c, int form, int H, int n_ctx, int n_sl
     cleanup();
     for (int r = 0; r < orows; ++r) for (int n = 0; n < d; ++n)
         out_host[(size_t)r * d + n] = skw_f16_to_f32(o[ofrag ? (size_t)skw_afrag_off(r, skw_kperm(n), d) : (size_t)r * d + skw_kperm(n)]);
+    return 0;
+}
+
+// Test hook (tests/test_gpu_xattn_mq_exact.py): the exact precision's two prompt-pass cross attentions on caller-supplied operands, in the style of skw_debug_attn16.
+//   Q [rows][H*64] f16 bit patterns, plain order; K / V [n_slots][n_ctx][H*64] f16 bit patterns in natural order (the hook lays them out as the exact precision keeps them: K rows,
+//   V^T per head in kperm key order); every K / V position of slot s from fill_from[s] up holds k_pad / v_pad when the kernel runs, and so do the pad keys n_ctx .. Tpad of V^T.
+//   n_seq sequences (row0, nq, slot); slot_k null or [n_slots].  mq = 0: skw_dec_cross_attn_vt (pv16 = 0), one row per query, `seq` / `nkeys` built from the same description;
+//   mq = 1: skw_xattn_prefill_exact.  The output buffer starts as `sentinel` in every 16-bit half; out: the raw buffer, rows x H*64 x (f32_out ? 4 : 2) bytes (f16 rows in kperm order).
+extern "C" int skw_debug_xattn_exact(skw_ctx* c, int mq, int H, int n_ctx, int n_slots, int rows, int f32_out, const uint16_t* Q_host, const uint16_t* K_host, const uint16_t* V_host,
+                                     const int* fill_from, int k_pad, int v_pad, const int* slot_k, int n_seq, const int* row0, const int* nq, const int* slot, int sentinel, void* out_host) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_xattn_exact: %s", what); return -1; };
+    if (H < 1 || H > 32 || n_ctx < 1 || n_ctx > SKW_XATTN_MQ_MAX_CTX || n_slots < 1 || n_slots > 64 || rows < 1 || rows > 65536 || !fill_from) return bad("bad geometry");
+    if (n_seq < 1 || n_seq > 64 || !row0 || !nq || !slot) return bad("the prompt pass needs row0 / nq / slot");
+    const int d = H * 64, Tpad = (n_ctx + 31) & ~31; int nq_max = 0;
+    for (int s = 0; s < n_slots; ++s) if (fill_from[s] < 0 || fill_from[s] > n_ctx) return bad("fill_from outside [0, n_ctx]");
+    std::vector<SkwSeqState> st(rows); memset((void*)st.data(), 0, sizeof(SkwSeqState) * rows);      // rows outside every sequence stay inactive: the single-query kernel skips them
+    for (int i = 0; i < n_seq; ++i) {
+        if (row0[i] < 0 || nq[i] < 0 || row0[i] + nq[i] > rows || slot[i] < 0 || slot[i] >= n_slots) return bad("a sequence's rows or slot lie outside the buffers");
+        nq_max = std::max(nq_max, nq[i]);
+        for (int r = row0[i]; r < row0[i] + nq[i]; ++r) { if (st[r].active) return bad("sequences overlap"); st[r].active = 1; st[r].pad = slot[i]; st[r].n_keys = slot_k ? slot_k[slot[i]] : 0; }
+    }
+    if (nq_max < 1) return bad("no queries");
+    const size_t nQ = (size_t)rows * d, nK = (size_t)n_slots * n_ctx * d, nV = (size_t)n_slots * Tpad * d, nO = (size_t)rows * d * (f32_out ? 2 : 1);
+    std::vector<uint16_t> k(nK, (uint16_t)k_pad), v(nV, (uint16_t)v_pad), o(nO, (uint16_t)sentinel);
+    for (int s = 0; s < n_slots; ++s) for (int i = 0; i < fill_from[s]; ++i) for (int n = 0; n < d; ++n) {
+        k[((size_t)s * n_ctx + i) * d + n] = K_host[((size_t)s * n_ctx + i) * d + n];
+        v[((size_t)s * d + n) * Tpad + skw_kperm(i)] = V_host[((size_t)s * n_ctx + i) * d + n];
+    }
+    half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr; SkwSeqState* dst = nullptr; int* dmeta = nullptr;
+    auto cleanup = [&]() { hipFree(dq); hipFree(dk); hipFree(dv); hipFree(dout); hipFree(dst); hipFree(dmeta); };
+    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_xattn_exact: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
+    if (!chk(hipMalloc((void**)&dq, nQ * 2)) || !chk(hipMalloc((void**)&dk, nK * 2)) || !chk(hipMalloc((void**)&dv, nV * 2)) || !chk(hipMalloc((void**)&dout, nO * 2))) return -1;
+    if (!chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * rows)) || !chk(hipMalloc((void**)&dmeta, sizeof(int) * 4 * 64))) return -1;
+    if (!chk(hipMemcpy(dq, Q_host, nQ * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dk, k.data(), nK * 2, hipMemcpyHostToDevice))) return -1;
+    if (!chk(hipMemcpy(dv, v.data(), nV * 2, hipMemcpyHostToDevice))) return -1;
+    if (!chk(hipMemcpy(dout, o.data(), nO * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * rows, hipMemcpyHostToDevice))) return -1;
+    int meta[4 * 64] = {0};      // row0 | nq | slot | slot_k
+    for (int i = 0; i < n_seq; ++i) { meta[i] = row0[i]; meta[64 + i] = nq[i]; meta[128 + i] = slot[i]; }
+    if (slot_k) for (int s = 0; s < n_slots; ++s) meta[192 + s] = slot_k[s];
+    if (!chk(hipMemcpy(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice))) return -1;
+    if (mq) {
+        if (!skw_xattn_prefill_exact(dq, dk, dv, dout, n_seq, nq_max, dmeta, dmeta + 64, dmeta + 128, H, d, n_ctx, Tpad, c->stream, f32_out, slot_k ? dmeta + 192 : nullptr)) {
+            cleanup(); return bad("the multi-query launcher refused the geometry"); }
+    } else skw_dec_cross_attn_vt(dq, dk, dv, rows, H, d, n_ctx, Tpad, dout, &dst[0].active, c->stream, f32_out, 0, &dst[0].pad, nullptr, nullptr, 0, nullptr, slot_k ? &dst[0].n_keys : nullptr);
+    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(out_host, dout, nO * 2, hipMemcpyDeviceToHost))) return -1;
+    cleanup();
     return 0;
 }
 

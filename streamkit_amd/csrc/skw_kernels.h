@@ -159,6 +159,15 @@ void skw_dec_self_attn(const half_t* q, const half_t* kc, const half_t* vc, cons
 #define SKW_KCLK_MAX_WG 4096
 struct SkwKClkRec { unsigned long long t0_inv, t1; unsigned live_rows, keys; };      // keys: summed over the live rows, the keys each walked
 struct SkwKClk { unsigned cap, pad0, pad1, pad2; unsigned cnt[SKW_KCLK_MAX_WG]; SkwKClkRec rec[1][SKW_KCLK_SHARDS]; };      // rec[cap][SKW_KCLK_SHARDS] follows
+// The exact precision's prompt-pass cross attention, 16 queries per workgroup (k_xattn_prefill_exact): the bits of skw_dec_cross_attn_vt(pv16 = 0) for every row, K / V^T read once per
+// 16 queries.  Returns false without launching when n_ctx exceeds SKW_XATTN_MQ_MAX_CTX (the callers then keep the single-query kernel).
+#define SKW_XATTN_MQ_MAX_CTX 1536      // the single-query kernel's bound (24 tiles of 64 keys); 16 x 1540 floats of scores + four K slabs = 133 KiB of LDS
+// Below this many queries in the pass's longest prompt the prompt pass keeps the single-query kernel (same bits; a speed choice).  4: a prompt without carried text is at most
+// sot, language, task, notimestamps — three rows — so windows that decode behind nothing make exactly the launches they made before this kernel existed.  Not a measured
+// crossover: tools/bench_context.py --sweep times both kernels per prompt length; until its figures are in DESIGN.md section 3 ("Carried context") the cut is this argument alone.
+#define SKW_XATTN_MQ_MIN_NQ 4
+bool skw_xattn_prefill_exact(const half_t* q, const half_t* ck, const half_t* cvt, half_t* out, int n_seq, int nq_max, const int* row0, const int* nq, const int* slot,
+                             int H, int d, int n_ctx, int Tpad, hipStream_t s, int f32_out, const int* slot_k);
 void skw_dec_cross_attn_vt(const half_t* q, const half_t* ck, const half_t* cvt, int B, int H, int d, int n_ctx, int Tpad, half_t* out, const int* active, hipStream_t s,
     int f32_out = 0, int pv16 = 0, const int* seq = nullptr,
                            // ofrag (one-pass kernel only): the output rows as the fragment-order A image of the projection that follows; events: stamped at the kernel's

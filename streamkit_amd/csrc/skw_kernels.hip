@@ -1314,6 +1314,151 @@ void skw_dec_cross_attn_vt(const half_t* q, const half_t* ck, const half_t* cvt,
     else hipLaunchKernelGGL((k_dec_cross_attn<24, 4, 3>), grid, blk, 0, s, q, (long)d, ck, (long)n_ctx * d, (long)d, cvt, n_ctx, Tpad, H, out, (long)d, active, as, f32_out & 1, seq, nkeys);
 }
 
+// ------------------------------------------------------------------ the exact precision's prompt pass: cross attention of 16 queries per workgroup
+// A prompt of up to 224 tokens is 224 rows of ONE decoder pass that attend over the same cross K / V^T; k_dec_cross_attn streams the sequence's 4.6 MB per layer once per row.
+// Here one workgroup (four waves) serves 16 queries of one (sequence, head): every K / V^T byte is loaded once per 16 queries, and every output element is the bits
+// k_dec_cross_attn<24, 4, 3> produces for that row, because each (query, key) and each (channel, query) keeps its own chain:
+//   scores   S[key][query] on v_mfma_f32_16x16x4_f32: A = 16 keys x 4 d, B = 4 d x 16 queries, 16 instructions chained over d — the d-ascending chain from 0 of f16-valued
+//            products in f32 that the single-query kernel writes as fmas (the columns it would spend on a broadcast hold the other 15 queries).  Wave w takes the 64-key tiles
+//            w, w + 4, ..: K rows come in coalesced (16 B per lane), are transposed through a per-wave LDS slab (row stride 144 B) and the next tile's loads fly meanwhile.
+//            Keys at or past the row's count are -inf.  The scores of all 16 queries stay in LDS: 16 x (64 nt + 4) floats, 96 KiB at 1500 keys (one workgroup per CU).
+//   softmax  wave w owns queries 4 w .. 4 w + 3.  Maximum over all keys (exact in any order), e = skw_expf(s - max), and the f64 sum in the single-query kernel's grouping:
+//            its WPH = 4 waves split the nt tiles into contiguous parts of ceil(nt / 4), each lane (key mod 64) adds its part's tiles in ascending order, wave_sum_f64 folds
+//            the lanes, the four parts add in ascending order.  An f64 sum of floats is not exact, so the grouping is part of the contract.  p = h2f(f2h(e * (float)(1 / tot))).
+//   P.V      wave w owns channels 16 w .. 16 w + 15: O^T[channel][query] += V^T[channel][key] * p[query][key], one MFMA per four keys, 32-key blocks in skw_kperm order
+//            (lane group g of element e holds key 4 e + g), so the chain per (channel, query) is key-ascending; V^T of keys past the row's count is replaced by zeros.
+// Rows outside every sequence and query slots past nq in a sequence's last tile are not written.
+#define SKW_XQ_SLAB (64 * 72)      // halves of one wave's K slab
+__global__ __launch_bounds__(256, 1) void k_xattn_prefill_exact(const half_t* q, long ldq, const half_t* kbase, long k_slot_stride, long ldk, const half_t* vtbase, int n_ctx, int Tpad, int H,
+                                                                half_t* out, long ldo, int f32_out, const int* row0, const int* nq, const int* slot, const int* slot_k) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char xq_lds[];
+    const int sq = blockIdx.z, h = blockIdx.y, qt = blockIdx.x;
+    const int nqs = nq[sq];
+    if (qt * 16 >= nqs) return;                  // uniform per workgroup
+    const int r0 = row0[sq] + qt * 16, nqt = min(16, nqs - qt * 16), sl = slot[sq];
+    if (slot_k) { const int nk = slot_k[sl]; if (nk > 0) n_ctx = min(nk, n_ctx); }      // per-clip audio context: the slot's key count; n_ctx and Tpad stay the strides
+    const int nt = (n_ctx + 63) >> 6, SP = nt * 64 + 4;      // (+ 4: the 16 queries' rows start 4 banks apart, so the P.V reads of a lane group do not collide)
+    float* pl = (float*)xq_lds;
+    half_t* klds = (half_t*)(xq_lds + (size_t)16 * SP * 4);
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r16 = lane & 15, g = lane >> 4;
+    // ---- scores
+    const half_t* K = kbase + (long)sl * k_slot_stride + h * 64;
+    float qf[16];
+    {
+        const half_t* qp = q + (long)(r0 + min(r16, nqt - 1)) * ldq + h * 64;      // query slots past nq repeat the last row (computed, never stored)
+#pragma unroll
+        for (int m = 0; m < 16; ++m) qf[m] = h2f(qp[4 * m + g]);
+    }
+    half_t* kl = klds + w * SKW_XQ_SLAB;
+    const int lrow = lane >> 3, lseg = lane & 7;
+    u32x4 kr[8];
+    auto kload = [&](int t) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) kr[i] = *(const u32x4*)(K + (long)min(t * 64 + i * 8 + lrow, n_ctx - 1) * ldk + lseg * 8);
+    };
+    if (w < nt) kload(w);
+    for (int t = w; t < nt; t += 4) {            // wave-uniform
+#pragma unroll
+        for (int i = 0; i < 8; ++i) *(u32x4*)(kl + (i * 8 + lrow) * 72 + lseg * 8) = kr[i];
+        __builtin_amdgcn_wave_barrier();         // same wave, LDS in order: a compiler-level fence is all that is needed
+        if (t + 4 < nt) kload(t + 4);
+        f32x4 acc[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int m = 0; m < 16; ++m)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc[s] = MFMA16(h2f(kl[(s * 16 + r16) * 72 + 4 * m + g]), qf[m], acc[s]);      // S[key][query] += K[key][d] * q[query][d], d = 4 m + g
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {            // D: lane (r16, g) holds keys 4 g .. 4 g + 3 of the sub-tile for query r16
+            const int key0 = t * 64 + s * 16 + 4 * g; f32x4 v = acc[s];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (key0 + r >= n_ctx) v[r] = -INFINITY;
+            *(f32x4*)(pl + r16 * SP + key0) = v;
+        }
+    }
+    // V^T ring: the first loads fly during the softmax
+    __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(vtbase + ((long)sl * H + h) * 64 * Tpad), 0, (unsigned)(64 * Tpad * 2), 0x00020000);
+    const unsigned vo = (unsigned)(((w * 16 + r16) * Tpad + g * 8) * 2);
+    const int nkb = (n_ctx + 31) >> 5;
+    constexpr int RD = 8;
+    H8v ring[RD];
+#pragma unroll
+    for (int j = 0; j < RD; ++j) { ring[j].v = __builtin_amdgcn_raw_buffer_load_b128(rv, (j < nkb) ? vo + j * 64 : 0x7fffff00u, 0, 0); __builtin_amdgcn_sched_barrier(0); }
+    __syncthreads();
+    // ---- softmax, four queries per wave
+    const int nth = (nt + 3) >> 2;
+    for (int jq = 0; jq < 4; ++jq) {
+        const int j = w * 4 + jq;
+        if (j >= nqt) break;                     // wave-uniform
+        float* pj = pl + j * SP;
+        float lmax = -INFINITY;
+        for (int t = 0; t < nt; ++t) lmax = fmaxf(lmax, pj[t * 64 + lane]);
+        lmax = skw_wave_max_f32(lmax);
+        double tot = 0.0;
+        for (int part = 0; part < 4; ++part) {
+            const int t_lo = part * nth, t_hi = min(nt, t_lo + nth);
+            double lsum = 0.0;
+            for (int t = t_lo; t < t_hi; ++t) { float e = skw_expf(pj[t * 64 + lane] - lmax); pj[t * 64 + lane] = e; lsum += (double)e; }   // exp(-inf) == 0 for masked keys
+            lsum = wave_sum_f64(lsum);
+            tot = part == 0 ? lsum : tot + lsum;
+        }
+        const float inv = (float)(1.0 / tot);
+        for (int t = 0; t < nt; ++t) pj[t * 64 + lane] = h2f(f2h(pj[t * 64 + lane] * inv));
+    }
+    __syncthreads();
+    // ---- P.V
+    f32x4 oacc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float* pq = pl + r16 * SP + g;
+    for (int kb0 = 0; kb0 < nkb; kb0 += RD) {
+#pragma unroll
+        for (int j = 0; j < RD; ++j) {
+            const int kb = kb0 + j;
+            if (kb < nkb) {                      // wave-uniform
+                H8v vf = ring[j];
+                const int nb = kb + RD;
+                ring[j].v = __builtin_amdgcn_raw_buffer_load_b128(rv, (nb < nkb) ? vo + nb * 64 : 0x7fffff00u, 0, 0);
+                // keys past the row's count in its last block: V^T there is an earlier, longer call's (or a don't-care encoder row's) — replaced by zeros, never multiplied by p = 0
+                if (kb * 32 + 32 > n_ctx) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) if (kb * 32 + 4 * e + g >= n_ctx) vf.h[e] = f2h(0.0f);
+                }
+                float pe[8], xv[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { pe[e] = pq[kb * 32 + 4 * e]; xv[e] = h2f(vf.h[e]); }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) oacc = MFMA16(xv[e], pe[e], oacc);      // O^T[c][query] += V^T[c][key] * p[query][key]
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+    // D: lane (r16, g) holds channels 16 w + 4 g .. + 3 of query r16
+    if (r16 < nqt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) att_store(out, (long)(r0 + r16) * ldo, h * 64 + w * 16 + 4 * g + r, oacc[r], f32_out);
+    }
+}
+size_t skw_xattn_prefill_exact_lds(int n_ctx) { return (size_t)16 * ((size_t)((n_ctx + 63) >> 6) * 64 + 4) * 4 + (size_t)4 * SKW_XQ_SLAB * 2; }
+// the prompt pass's cross attention in the exact precision: n_seq sequences, sequence i's queries are rows row0[i] .. row0[i] + nq[i] of q [rows][d] (plain f16, already scaled), its
+// K (rows [n_ctx][d]) / V^T ([H][64][Tpad], kperm) those of window slot slot[i]; out: f16 kperm rows, or f32 rows (f32_out) — what skw_dec_cross_attn_vt(pv16 = 0) writes for each row.
+// False (nothing launched): a geometry the kernel does not hold (more than SKW_XATTN_MQ_MAX_CTX keys).
+bool skw_xattn_prefill_exact(const half_t* q, const half_t* ck, const half_t* cvt, half_t* out, int n_seq, int nq_max, const int* row0, const int* nq, const int* slot,
+                             int H, int d, int n_ctx, int Tpad, hipStream_t s, int f32_out, const int* slot_k) {
+    if (n_seq < 1 || nq_max < 1 || n_ctx < 1 || n_ctx > SKW_XATTN_MQ_MAX_CTX) return false;
+    const size_t lds = skw_xattn_prefill_exact_lds(n_ctx);
+    if (lds > 64 * 1024) {      // more dynamic LDS than the default limit: raise it on this device (per device: several GPUs may run in one process)
+        static std::atomic<bool> raised[64]; int dev = 0; if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+        if (!raised[dev].load(std::memory_order_acquire)) { hipFuncSetAttribute((const void*)k_xattn_prefill_exact, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        raised[dev].store(true, std::memory_order_release); }
+    }
+    hipLaunchKernelGGL(k_xattn_prefill_exact, dim3((nq_max + 15) / 16, H, n_seq), dim3(256), lds, s, q, (long)d, ck, (long)n_ctx * d, (long)d, cvt, n_ctx, Tpad, H, out, (long)d,
+                       f32_out & 1, row0, nq, slot, slot_k);
+    return true;
+}
+
 void skw_dec_self_attn(const half_t* q, const half_t* kc, const half_t* vc, const int* pos, int B, int H, int d, int n_text_ctx, half_t* out, const int* active,
     hipStream_t s, int f32_out, SkwQ8Out q8, const int* seq, int fastv, int ofrag) {
     if (fastv && skw_sw(SW_DEC_ATTN_FASTV) && !q8.q && !f32_out) { hipLaunchKernelGGL((k_dec_attn<7, true>), dim3((H + 3) / 4, B), dim3(256), 0, s, q, (long)d, kc, vc, (long)n_text_ctx * d, (long)d,

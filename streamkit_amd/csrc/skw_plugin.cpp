@@ -5,7 +5,7 @@
 // ABI: include/streamkit_native_abi.h.
 //
 // Params beyond the reference's are ADDITIVE (unknown keys are ignored by the reference's serde config, lib.rs:66-104):
-// vad_mode, batch_window_ms, max_batch, mixed_batch, flush_tail, precision, gpu_device: "auto", and input_sample_rate / input_resample_mode (the
+// vad_mode, batch_window_ms, max_batch, mixed_batch, flush_tail, precision, gpu_device: "auto", initial_prompt, carry_context, and input_sample_rate / input_resample_mode (the
 // audio::resampler node's arithmetic run inside this plugin, skw_resampler_core.h: a 48 kHz Opus source then needs no node in between).
 // One BEHAVIOURAL difference remains and is not additive: with the default vad_mode "auto" the Silero model at `vad_model_path`
 // gates what Whisper sees exactly as in the reference (skw_silero.h) only when that file exists; when it does not, the
@@ -78,6 +78,9 @@ struct WhisperConfig {
     int audio_ctx = 0; bool audio_ctx_auto = false;
     std::string vad_device = "cpu";  // cpu (the libm Silero gate, frame by frame) | gpu (Silero in the contract arithmetic of include/skw_silero_net.h on gpu_device's GPU)
     int vad_batch_frames = 1;        // complete 512-sample frames held back before the gate is asked for their probabilities in one call
+    // Text that conditions decoding (skw_full_batch_context).  The defaults are the reference's behaviour: whisper-rs leaves no_context = true and sets no prompt (lib.rs:624-641).
+    std::string initial_prompt;      // whisper_full_params.initial_prompt: tokenised with whisper.cpp's tokenizer (nothing is put in front of it), in front of every segment's context
+    bool carry_context = false;      // whisper_full_params.no_context = false: the text of this instance's segment n conditions its segment n + 1
     uint32_t input_sample_rate = 16000; std::string input_resample_mode = "linear";   // linear (the audio::resampler node's rubato arithmetic, bit for bit) | polyphase
 };
 
@@ -100,7 +103,7 @@ bool parse_config(const char* json, WhisperConfig* cfg, std::string* err) {
     if (!str("model_path", &cfg->model_path) || !str("language", &cfg->language) || !str("vad_model_path", &cfg->vad_model_path) || !str("vad_mode", &cfg->vad_mode)
         || !str("precision", &cfg->precision)) return false;
     if (cfg->precision != "exact" && cfg->precision != "f16_mfma") { *err = "Invalid config: precision must be \"exact\" or \"f16_mfma\""; return false; }
-    if (!str("vad_device", &cfg->vad_device)) return false;
+    if (!str("vad_device", &cfg->vad_device) || !str("initial_prompt", &cfg->initial_prompt)) return false;
     if (cfg->vad_device != "cpu" && cfg->vad_device != "gpu") { *err = "Invalid config: vad_device must be \"cpu\" or \"gpu\""; return false; }
     d = cfg->vad_batch_frames; if (!num("vad_batch_frames", &d)) return false;
     if (d < 1 || d > 65536 || d != std::floor(d)) { *err = "Invalid config: vad_batch_frames must be an integer between 1 and 65536"; return false; }
@@ -132,7 +135,7 @@ bool parse_config(const char* json, WhisperConfig* cfg, std::string* err) {
     d = cfg->batch_window_ms; if (!num("batch_window_ms", &d)) return false; cfg->batch_window_ms = (int)d;
     d = cfg->max_batch; if (!num("max_batch", &d)) return false; cfg->max_batch = std::max(1, (int)d);
     if (!boo("use_gpu", &cfg->use_gpu) || !boo("suppress_blank", &cfg->suppress_blank) || !boo("suppress_non_speech_tokens", &cfg->suppress_non_speech_tokens) ||
-        !boo("emit_vad_events", &cfg->emit_vad_events) || !boo("flush_tail", &cfg->flush_tail) || !boo("mixed_batch", &cfg->mixed_batch)) return false;
+        !boo("emit_vad_events", &cfg->emit_vad_events) || !boo("flush_tail", &cfg->flush_tail) || !boo("mixed_batch", &cfg->mixed_batch) || !boo("carry_context", &cfg->carry_context)) return false;
     return true;
 }
 
@@ -163,6 +166,11 @@ struct Job {
     std::vector<float> pcm_pageable; PinnedPool::Buf pinned{nullptr, 0}; size_t n = 0;
     skw_full_params params; std::promise<int> done; skw_result result{}; std::string error;
     uint32_t* rng = nullptr;      // the owning instance's std::mt19937 stream (WhisperPlugin::rng): continued by this segment's sampled passes, if it needs any
+    // the text this segment decodes behind (prompt_past as whisper_full_with_state's window loop finds it: the instance's initial prompt, then what it carries) and, after the call,
+    // what the call leaves.  want_ctx: the instance has a prompt or carries context (an instance that carries hands in its context even while it is empty: that is how it gets the
+    // first one back); without it the job takes no part in a context call
+    int32_t ctx[SKW_CONTEXT_WORDS] = {0}; bool want_ctx = false;
+    int32_t* context() { return want_ctx ? ctx : nullptr; }
     void set_samples(const std::vector<float>& v) {
         n = v.size(); pinned = PinnedPool::get().acquire(n);
         if (pinned.p) memcpy(pinned.p, v.data(), n * sizeof(float)); else pcm_pageable = v;      // (no page-locked memory to be had: the ordinary copy path)
@@ -171,6 +179,7 @@ struct Job {
     ~Job() { PinnedPool::get().release(pinned); }
 };
 std::atomic<long> g_engine_calls{0}, g_batch_jobs{0}, g_mixed_calls{0};      // skw_whisper_plugin_batch_stats
+std::atomic<long> g_context_calls{0};                                        // skw_whisper_plugin_context_stats: engine calls that carried at least one context
 struct SharedEngine {
     skw_model* model = nullptr;
     skw_ctx* ctx = nullptr;
@@ -180,6 +189,7 @@ struct SharedEngine {
     int window_ms = 2;          // scheduler: how long a batch waits for more jobs (batch_window_ms of the instance created most recently; under mu)
     bool multilingual = true;   // the model has language tokens (n_vocab >= 51865); set once at load
     int n_audio_ctx = 1500;     // the model's encoder positions (what audio_ctx "auto" is capped at); set once at load
+    int n_text_ctx = 448;       // the model's decoder positions (a prompt takes at most half of them); set once at load
     bool mixed = true;          // scheduler: jobs join a batch whatever their parameters (mixed_batch of the instance created most recently; under mu)
     int precision = SKW_PRECISION_EXACT;
     static const int kMaxSamples = 16000 * 121;   // schema maximum of max_segment_duration_secs (120 s) + one VAD frame of slack: no segment is longer
@@ -252,10 +262,15 @@ struct SharedEngine {
                     std::vector<uint32_t*> rngs(n); for (int i = 0; i < n; ++i) rngs[i] = batch[i]->rng;
                     std::vector<skw_full_params> pv(n); bool differ = false;
                     for (int i = 0; i < n; ++i) { pv[i] = batch[i]->params; differ = differ || memcmp(&pv[0], &pv[i], sizeof(skw_full_params)) != 0; }
+                    // a batch in which no job has a prompt or carries context makes exactly the calls it made before contexts existed; otherwise ONE context call serves it (jobs without
+                    // text hand in NULL: their rows are skw_full_batch_mixed's)
+                    std::vector<int32_t*> cxs(n); bool any_ctx = false;
+                    for (int i = 0; i < n; ++i) { cxs[i] = batch[i]->context(); any_ctx = any_ctx || cxs[i] != nullptr; }
                     // (jobs that all share one parameter block run the uniform call: the same launches as before mixed batches existed)
-                    rc = differ ? skw_full_batch_mixed(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), res.data())
+                    rc = any_ctx ? skw_full_batch_context(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), cxs.data(), res.data())
+                       : differ ? skw_full_batch_mixed(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), res.data())
                                 : skw_full_batch_rng(ctx, &pv[0], ptrs.data(), ns.data(), n, 0, rngs.data(), res.data());
-                    g_engine_calls.fetch_add(1); g_batch_jobs.fetch_add(n); if (differ) g_mixed_calls.fetch_add(1);
+                    g_engine_calls.fetch_add(1); g_batch_jobs.fetch_add(n); if (differ) g_mixed_calls.fetch_add(1); if (any_ctx) g_context_calls.fetch_add(1);
                     if (rc == 0) for (int i = 0; i < n; ++i) batch[i]->result = res[i]; else why = skw_ctx_last_error(ctx);
                     if (rc != 0 && differ) {
                         // A refusal must stay with the request that earned it: jobs of differently configured instances share this call, and one of them being refused
@@ -263,7 +278,8 @@ struct SharedEngine {
                         // parameters; every job gets its own outcome.  (Jobs with equal blocks share their configuration, and shared the call before mixed batches too.)
                         for (int i = 0; i < n; ++i) {
                             skw_result one{}; const float* pp = ptrs[i]; uint32_t* rg = rngs[i];
-                            int r1 = skw_full_batch_rng(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &one);
+                            int32_t* cx = cxs[i];      // (the refused call wrote no context back: each job's own, as it was queued)
+                            int r1 = cx ? skw_full_batch_context(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &cx, &one) : skw_full_batch_rng(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &one);
                             g_engine_calls.fetch_add(1);
                             if (r1 == 0) batch[i]->result = one;
                             else { try { batch[i]->error = skw_ctx_last_error(ctx); } catch (const std::exception&) { r1 = -1; } }      // (a promise is satisfied once)
@@ -309,7 +325,16 @@ struct WhisperPlugin {
     // reference creates one state per instance (lib.rs:377-379) and a new one when update_params swaps the context (lib.rs:520-535).  This is that generator: every segment of
     // this instance continues it (skw_full_batch_rng), whichever batch the segment lands in.
     uint32_t rng[SKW_RNG_STATE_WORDS];
-    void hold(std::shared_ptr<SharedEngine> e) { if (e) e->instance_added(); if (engine) engine->instance_gone(); engine = std::move(e); skw_rng_state_init(rng); }
+    // whisper.cpp's other per-state memory: prompt_past, the text a call leaves for the next one when no_context is false.  context[0] = n, then n ids, oldest first — what this
+    // instance's last segment handed back (carry_context), WITHOUT the initial prompt, which goes in front of it again for every segment as whisper_full_with_state does.
+    // An instance never has two segments in flight: plugin_process_packet (and plugin_flush) run transcribe_and_emit on the caller's thread and wait there on the job's promise
+    // before the segmenter hands over the next cut, and the host serialises the calls on one instance.  Segment n + 1 therefore always sees what segment n left.
+    int32_t context[SKW_CONTEXT_WORDS] = {0};
+    std::vector<int32_t> prompt_tokens; bool prompt_ready = false;      // initial_prompt tokenised with this instance's model: once, and again when either changes
+    void hold(std::shared_ptr<SharedEngine> e) {
+        if (e) e->instance_added(); if (engine) engine->instance_gone(); engine = std::move(e); skw_rng_state_init(rng);
+        context[0] = 0; prompt_ready = false;      // a new state starts with no text, and another model may tokenise the prompt differently
+    }
     ~WhisperPlugin() { if (engine) engine->instance_gone(); }
     std::unique_ptr<skw::ResamplerCore> front;      // input_sample_rate != 16000: the audio::resampler node's arithmetic on the GPU, feeding the segmenter
     CLogCallback log_cb = nullptr; void* log_ud = nullptr;
@@ -318,6 +343,35 @@ struct WhisperPlugin {
         log_cb(lv, "whisper_plugin_native", buf, log_ud);
     }
 };
+
+// initial_prompt -> tokens (whisper_tokenize); a prompt longer than half the decoder's context keeps its END, as whisper_full_with_state's own cut of prompt_past would
+void ensure_prompt_tokens(WhisperPlugin* self) {
+    if (self->prompt_ready) return;
+    self->prompt_tokens.clear(); self->prompt_ready = true;
+    if (self->config.initial_prompt.empty()) return;
+    std::vector<int32_t> ids(64);
+    int n = skw_model_tokenize(self->engine->model, self->config.initial_prompt.c_str(), ids.data(), (int)ids.size());
+    if (n < 0) { ids.resize((size_t)-n); n = skw_model_tokenize(self->engine->model, self->config.initial_prompt.c_str(), ids.data(), (int)ids.size()); }
+    if (n < 0) n = 0;
+    ids.resize((size_t)n);
+    const int cap = self->engine->n_text_ctx / 2;
+    if (n > cap) {
+        self->log(SK_LOG_WARN, "initial_prompt is %d tokens; only its last %d (half the model's text context) condition decoding", n, cap);
+        ids.erase(ids.begin(), ids.end() - cap);
+    }
+    self->prompt_tokens = ids;
+}
+// The context a segment is queued with (whisper_full_with_state before its window loop): no carry -> the carried part is cleared (no_context); then the prompt's tokens go to the
+// FRONT (whisper.cpp: push_back + rotate); when the total exceeds what the engine takes, the oldest tokens behind the prompt go.
+void build_job_context(WhisperPlugin* self, int32_t* out) {
+    ensure_prompt_tokens(self);
+    const int cap = SKW_CONTEXT_WORDS - 1, np = (int)self->prompt_tokens.size();
+    int nc = self->config.carry_context ? self->context[0] : 0;
+    if (np + nc > cap) nc = cap - np;
+    out[0] = np + nc;
+    for (int i = 0; i < np; ++i) out[1 + i] = self->prompt_tokens[i];
+    for (int i = 0; i < nc; ++i) out[1 + np + i] = self->context[1 + self->context[0] - nc + i];
+}
 
 std::shared_ptr<SharedEngine> get_engine(const WhisperConfig& cfg, WhisperPlugin* who, std::string* err) {
     char keybuf[96];
@@ -349,7 +403,7 @@ std::shared_ptr<SharedEngine> get_engine(const WhisperConfig& cfg, WhisperPlugin
     eng->model = skw_model_load(cfg.model_path.c_str(), cfg.gpu_device, ebuf, sizeof ebuf);
     if (!eng->model) { *err = ebuf[0] ? ebuf : ("Failed to load Whisper model from '" + cfg.model_path + "'"); return nullptr; }
     g_model_loads.fetch_add(1);
-    { skw_hparams hp{}; skw_model_get_hparams(eng->model, &hp); eng->multilingual = hp.n_vocab >= 51865; eng->n_audio_ctx = hp.n_audio_ctx; }
+    { skw_hparams hp{}; skw_model_get_hparams(eng->model, &hp); eng->multilingual = hp.n_vocab >= 51865; eng->n_audio_ctx = hp.n_audio_ctx; eng->n_text_ctx = hp.n_text_ctx; }
     const auto t1 = std::chrono::steady_clock::now();
     eng->batch_limit = cfg.max_batch;
     eng->window_ms = cfg.batch_window_ms; eng->mixed = cfg.mixed_batch;
@@ -496,12 +550,15 @@ bool transcribe_and_emit(WhisperPlugin* self, const Emit& em, const skw::Segment
     // (additive) the segment's audio context: what its instance is configured for now (update_params takes effect from the next segment); "auto" = the exported rule on its length
     job->params.audio_ctx = self->config.audio_ctx_auto ? skw_audio_ctx_for_samples((int)job->n, self->engine->n_audio_ctx) : self->config.audio_ctx;
     job->rng = self->rng;
+    build_job_context(self, job->ctx); job->want_ctx = self->config.carry_context || job->ctx[0] > 0;
     if ((int)job->n > SharedEngine::kMaxSamples) { *err = "Whisper inference failed: segment longer than the engine workspace"; return false; }
     std::future<int> fut = job->done.get_future();
     { std::lock_guard<std::mutex> l(self->engine->mu); self->engine->queue.push_back(job); }
     self->engine->cv.notify_all();
     int rc = fut.get();
     if (rc != 0) { *err = "Whisper inference failed: " + job->error; return false; }
+    // what the call left is this instance's carried text from here on (a failed call hands nothing back: the carried part stays as it was); without carry nothing is kept
+    if (self->config.carry_context) memcpy(self->context, job->ctx, sizeof self->context); else self->context[0] = 0;
     // segments with absolute timestamps (lib.rs:648-677)
     struct Seg { std::string text; uint64_t t0, t1; };
     std::vector<Seg> segs;
@@ -565,6 +622,8 @@ const char* const kSchema =
     "\"max_batch\":{\"type\":\"integer\",\"description\":\"(additive) largest number of segments transcribed in one GPU batch\",\"default\":64},"
     "\"audio_ctx\":{\"type\":[\"integer\",\"string\"],\"description\":\"(additive) whisper.cpp's audio_ctx per segment: 0 = the model's 1500 positions (30 s); N = encode and attend only N positions (20 ms each: the audio beyond N/50 s is not heard); \\\"auto\\\" = the positions the segment covers + 0.5 s, in 32-position blocks. Segments with different values share a batch\",\"default\":0},"
     "\"mixed_batch\":{\"type\":\"boolean\",\"description\":\"(additive) segments of instances with different language / suppress_* settings share one GPU batch; false cuts a batch at the first differing job\",\"default\":true},"
+    "\"initial_prompt\":{\"type\":\"string\",\"description\":\"(additive) whisper.cpp's initial_prompt: text (domain vocabulary, spellings) every segment is decoded behind; tokenised with whisper.cpp's tokenizer, which puts nothing in front of it (start it with a space to match openai's reference); at most half the model's text context (224 tokens), longer prompts keep their end\",\"default\":\"\"},"
+    "\"carry_context\":{\"type\":\"boolean\",\"description\":\"(additive) whisper.cpp's no_context = false: the text of this instance's previous segment conditions the next one; cleared when model_path, language or initial_prompt change\",\"default\":false},"
     "\"flush_tail\":{\"type\":\"boolean\",\"description\":\"(additive) transcribe buffered speech when the input stream ends (the reference drops it)\",\"default\":false},"
     "\"input_sample_rate\":{\"type\":\"integer\",\"description\":\"(additive) sample rate of the mono f32 packets fed to this node; anything but 16000 is resampled to 16 kHz on the GPU with the audio::resampler node's arithmetic (chunk_frames 960) before VAD segmentation\",\"default\":16000,\"minimum\":1000,\"maximum\":768000},"
     "\"input_resample_mode\":{\"type\":\"string\",\"description\":\"(additive) linear (rubato FastFixedIn/Linear, bit for bit what audio::resampler gives) | polyphase (Kaiser-windowed sinc)\",\"default\":\"linear\"}"
@@ -672,6 +731,8 @@ CResult plugin_update_params(CPluginHandle handle, const char* params) {
         self->seg.set_batch_frames((size_t)nc.vad_batch_frames);
         if (nc.min_silence_duration_ms != self->config.min_silence_duration_ms) self->seg.set_min_silence_ms(nc.min_silence_duration_ms);
         self->seg.set_threshold(nc.vad_threshold); self->seg.set_max_duration_secs(nc.max_segment_duration_secs);
+        // another model, language or prompt: what was carried belongs to the old ones (hold() has already cleared it for a new model); the prompt is tokenised again
+        if (nc.model_path != self->config.model_path || nc.language != self->config.language || nc.initial_prompt != self->config.initial_prompt) { self->context[0] = 0; self->prompt_ready = false; }
         nc.input_sample_rate = self->config.input_sample_rate; nc.input_resample_mode = self->config.input_resample_mode;   // the front end's rate is fixed at creation (a stream does not change rate)
         self->config = nc;
         return ok_result();
@@ -716,6 +777,8 @@ extern "C" void skw_whisper_plugin_batch_stats(long* engine_calls, long* jobs, l
     if (jobs) *jobs = g_batch_jobs.load();
     if (mixed_calls) *mixed_calls = g_mixed_calls.load();
 }
+// additive, for tests: engine calls that carried at least one context (skw_full_batch_context); a process whose instances set neither initial_prompt nor carry_context stays at 0
+extern "C" void skw_whisper_plugin_context_stats(long* context_calls) { if (context_calls) *context_calls = g_context_calls.load(); }
 // additive, for tests: cached engines (models resident), how many of them hold a batch workspace right now, and live plugin instances over all of them
 extern "C" void skw_whisper_plugin_workspace_stats(int* engines, int* workspaces, int* instances) {
     EngineCache& cache = engine_cache();

@@ -91,10 +91,18 @@ def lib():
         L.skw_full_batch.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Result)]
         L.skw_full_batch_rng.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(Result)]
         L.skw_full_batch_mixed.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(Result)]
+        L.skw_full_batch_context.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_void_p), C.POINTER(Result)]
+        L.skw_model_tokenize.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int]
+        L.skw_debug_set_prompt_pass.argtypes = [C.c_void_p, C.c_int]
+        L.skw_debug_set_prompt_xattn_mq.argtypes = [C.c_void_p, C.c_int]
+        L.skw_debug_xattn_exact.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
         L.skw_rng_state_init.argtypes = [C.c_void_p]
         L.skw_result_free.argtypes = [C.POINTER(Result)]
         L.skw_full_batch_traced.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int,
                                             C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(Trace), C.POINTER(Result)]
+        L.skw_full_batch_traced_context.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                                    C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(Trace), C.POINTER(C.c_void_p), C.POINTER(Result)]
         L.skw_trace_free.argtypes = [C.POINTER(Trace)]
         L.skw_log_mel.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.skw_conv_stem.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -164,6 +172,23 @@ def audio_ctx_for_samples(n_samples, n_audio_ctx=1500):
     return lib().skw_audio_ctx_for_samples(int(n_samples), int(n_audio_ctx))
 
 
+CONTEXT_WORDS = 513      # SKW_CONTEXT_WORDS
+
+
+def context_new(ids=()):
+    """A clip owner's carried text (whisper_state::prompt_past) as an int32[513]: [0] = n, [1 .. n] = token ids, oldest first (at most 512)"""
+    ids = [int(x) for x in ids]
+    assert len(ids) <= CONTEXT_WORDS - 1
+    a = np.zeros(CONTEXT_WORDS, np.int32)
+    a[0] = len(ids)
+    a[1:1 + len(ids)] = ids
+    return a
+
+
+def context_ids(a):
+    return [int(x) for x in a[1:1 + int(a[0])]]
+
+
 def rng_state_new():
     """std::mt19937(0) as a uint32[625] (mt + index): the generator a freshly created whisper_state owns"""
     s = np.zeros(625, np.uint32)
@@ -187,6 +212,17 @@ class Model:
         n = C.c_int()
         p = lib().skw_model_token_text(self.h, i, C.byref(n))
         return C.string_at(p, n.value)
+
+    def tokenize(self, text):
+        """whisper_tokenize (skw_model_tokenize): whisper.cpp's tokenizer on `text` (str or bytes) -> list of ids.  Nothing is put in front of the text."""
+        b = text.encode() if isinstance(text, str) else bytes(text)
+        n = lib().skw_model_tokenize(self.h, b, None, 0)
+        if n == 0:
+            return []
+        ids = np.zeros(-n, np.int32)
+        n = lib().skw_model_tokenize(self.h, b, ids.ctypes.data, ids.size)
+        assert n == ids.size
+        return ids.tolist()
 
     def close(self):
         if self.h:
@@ -225,14 +261,17 @@ class Context:
         lib().skw_full_default_params(C.byref(p))
         return p
 
-    def full_batch(self, clips, params=None, device_ptrs=None, n_samples=None, trace=False, forced=None, rng_states=None):
+    def full_batch(self, clips, params=None, device_ptrs=None, n_samples=None, trace=False, forced=None, rng_states=None, contexts=None):
         """clips: list of 1-D float32 numpy arrays (host), or device_ptrs + n_samples for HBM-resident PCM.
         trace=True (or forced=[per-clip int32 id sequences]): skw_full_batch_traced — returns (results, traces), traces[i] a structured
         array (TRACE_DT) with one record per sampling decision of clip i; with `forced` the decoder is fed those ids (teacher forcing).
         rng_states=[uint32[625] or None per clip] (rng_state_new()): the temperature ladder's std::mt19937 stream of each clip's OWNER, continued and updated in place
         (skw_full_batch_rng: whisper.cpp keeps one generator per state and lets it run on across calls).
         params=[FullParams per clip]: skw_full_batch_mixed — every clip decodes under its own parameters in the one batch (rng_states allowed with it).  Tracing / teacher
-        forcing takes one FullParams and no rng_states: either combination raises ValueError."""
+        forcing takes one FullParams and no rng_states: either combination raises ValueError.
+        contexts=[int32[513] or None per clip] (context_new()): skw_full_batch_context — each clip decodes behind its owner's carried text (prompt_past: [0] = n, then n ids,
+        an initial prompt's tokens in front) and the array is updated in place to what the call leaves, like rng_states.  One FullParams is repeated per clip.  With trace / forced:
+        skw_full_batch_traced_context."""
         per_clip = isinstance(params, (list, tuple))
         if trace or forced is not None:      # (checked before anything touches the library or the device)
             if per_clip:
@@ -254,14 +293,27 @@ class Context:
         if per_clip and len(params) != n:
             raise ValueError("full_batch: %d parameter blocks for %d clips" % (len(params), n))
         res = (Result * n)()
-        if trace or forced is not None:
+        cp = None
+        if contexts is not None:
+            if len(contexts) != n:
+                raise ValueError("full_batch: %d contexts for %d clips" % (len(contexts), n))
+            assert all(x is None or (x.dtype == np.int32 and x.size == CONTEXT_WORDS and x.flags["C_CONTIGUOUS"]) for x in contexts)
+            cp = (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in contexts])
+        if contexts is not None and not (trace or forced is not None):
+            sp = None
+            if rng_states is not None:
+                assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
+                sp = (C.c_void_p * n)(*[None if s is None else s.ctypes.data for s in rng_states])
+            pp = p if per_clip else (FullParams * n)(*([p] * n))
+            self._check(lib().skw_full_batch_context(self.h, pp, ptrs, ns, n, on_dev, sp, cp, res))
+        elif trace or forced is not None:
             tr = (Trace * n)()
             fptr = fn = None
             if forced is not None:
                 keep = [np.ascontiguousarray(f, dtype=np.int32) for f in forced]
                 fptr = (C.c_void_p * n)(*[k.ctypes.data for k in keep])
                 fn = (C.c_int32 * n)(*[k.size for k in keep])
-            self._check(lib().skw_full_batch_traced(self.h, C.byref(p), ptrs, ns, n, on_dev, fptr, fn, tr, res))
+            self._check(lib().skw_full_batch_traced_context(self.h, C.byref(p), ptrs, ns, n, on_dev, fptr, fn, tr, cp, res))
             traces = []
             for i in range(n):
                 a = np.frombuffer((C.c_char * (tr[i].n * TRACE_DT.itemsize)).from_address(tr[i].steps), dtype=TRACE_DT).copy() if tr[i].n else np.zeros(0, TRACE_DT)
@@ -284,6 +336,14 @@ class Context:
         if trace or forced is not None:
             return out, traces
         return out
+
+    def set_prompt_pass(self, on):
+        """test hook (skw_debug_set_prompt_pass): 0 = the prompt is stepped token by token instead of evaluated in one pass"""
+        lib().skw_debug_set_prompt_pass(self.h, 1 if on else 0)
+
+    def set_prompt_xattn_mq(self, on):
+        """test hook (skw_debug_set_prompt_xattn_mq): 0 = the exact precision's prompt pass keeps the single-query cross attention (same bits, one K / V^T read per prompt row)"""
+        lib().skw_debug_set_prompt_xattn_mq(self.h, 1 if on else 0)
 
     def timing(self):
         t = Timing()
@@ -429,6 +489,24 @@ class Context:
         self._check(lib().skw_debug_attn16(self.h, f, H, n_ctx, n_slots, rows, (1 if frag else 0) | (2 if ofrag else 0), int(out_rows), Q.ctypes.data, K.ctypes.data, V.ctypes.data,
                                            fill_from.ctypes.data, int(k_pad), int(v_pad), ptr(slot_k), n_seq, ptr(row0), ptr(nq), ptr(slot), ptr(active), ptr(seq), ptr(count),
                                            int(sentinel), out.ctypes.data))
+        return out
+
+    def xattn_exact(self, mq, H, n_ctx, Q, K, V, fill_from, row0, nq, slot, slot_k=None, f32_out=False, k_pad=0x7E00, v_pad=0x7E00, sentinel=0x5A5A):
+        """The exact precision's prompt-pass cross attention on caller-supplied operands (skw_debug_xattn_exact).  Q [rows][H*64], K / V [slots][n_ctx][H*64] as float16 (or uint16
+        bit patterns), natural order; sequences (row0, nq, slot); slot_k None or a key count per slot.  mq=0: the single-query kernel on every owned row, mq=1: the
+        16-queries-per-workgroup kernel.  -> the raw output buffer as uint16 [rows][H*64 * (2 if f32_out else 1)] (f16 rows are in kperm order), `sentinel` where nothing was written."""
+        d = H * 64
+        bits = lambda a: np.ascontiguousarray(a.view(np.uint16) if a.dtype == np.float16 else a, dtype=np.uint16)
+        ints = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        Q = bits(Q); K = bits(K); V = bits(V)
+        n_slots, rows = K.shape[0], Q.shape[0]
+        assert K.shape == (n_slots, n_ctx, d) and V.shape == K.shape and Q.shape == (rows, d)
+        fill_from, row0, nq, slot, slot_k = (ints(a) for a in (fill_from, row0, nq, slot, slot_k))
+        assert fill_from.size == n_slots and (slot_k is None or slot_k.size == n_slots) and row0.size == nq.size == slot.size
+        out = np.empty((rows, d * (2 if f32_out else 1)), dtype=np.uint16)
+        self._check(lib().skw_debug_xattn_exact(self.h, int(mq), H, n_ctx, n_slots, rows, 1 if f32_out else 0, Q.ctypes.data, K.ctypes.data, V.ctypes.data, fill_from.ctypes.data,
+                                                int(k_pad), int(v_pad), None if slot_k is None else slot_k.ctypes.data, row0.size, row0.ctypes.data, nq.ctypes.data, slot.ctypes.data,
+                                                int(sentinel), out.ctypes.data))
         return out
 
     def math(self, kind, x):

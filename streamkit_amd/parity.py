@@ -32,19 +32,23 @@ def bounds_for(hp):
     return (LOGIT_ERR_BOUND if d >= 768 else SMALL_MODEL_LOGIT_ERR_BOUND if d >= 256 else MICRO_MODEL_LOGIT_ERR_BOUND), MARGIN_BOUND
 
 
-def teacher_forced_compare(ctx, clips=None, params=None, device_ptrs=None, n_samples=None, logit_err_bound=None, margin_bound=None):
+def teacher_forced_compare(ctx, clips=None, params=None, device_ptrs=None, n_samples=None, logit_err_bound=None, margin_bound=None, contexts=None):
     """Runs the batch in the exact precision (free, traced), then in f16_mfma fed with the exact run's decisions.  Returns a dict of counts and
     the two result lists; leaves the context in the precision it was in.  The bounds are in logit units and belong to a model's logit scale (the
-    defaults: bounds_for(model)); a model with another scale passes its own (tests/test_gpu_f16.py: 7e-4 of the range)."""
+    defaults: bounds_for(model)); a model with another scale passes its own (tests/test_gpu_f16.py: 7e-4 of the range).
+    contexts=[int32[513] or None per clip]: each clip decodes behind that carried text in both runs (engine.context_new); the arrays are left as they were, what the runs leave
+    comes back as contexts_exact / contexts_forced."""
     eb, mb = bounds_for(ctx.model.hp)
     logit_err_bound = eb if logit_err_bound is None else logit_err_bound
     margin_bound = mb if margin_bound is None else margin_bound
     was = ctx.get_precision()
     kw = dict(device_ptrs=device_ptrs, n_samples=n_samples)
     ctx.set_precision("exact")
-    res_e, tr_e = ctx.full_batch(clips, params, trace=True, **kw)
+    cx_e = None if contexts is None else [None if x is None else x.copy() for x in contexts]
+    cx_f = None if contexts is None else [None if x is None else x.copy() for x in contexts]
+    res_e, tr_e = ctx.full_batch(clips, params, trace=True, contexts=cx_e, **kw)
     ctx.set_precision("f16_mfma")
-    res_f, tr_f = ctx.full_batch(clips, params, forced=[t["chosen_id"] for t in tr_e], **kw)
+    res_f, tr_f = ctx.full_batch(clips, params, forced=[t["chosen_id"] for t in tr_e], contexts=cx_f, **kw)
     ctx.set_precision(was)
     steps = disagree = 0
     worst_margin = 0.0          # largest exact-mode margin at a step where the f16_mfma argmax differs
@@ -79,4 +83,4 @@ def teacher_forced_compare(ctx, clips=None, params=None, device_ptrs=None, n_sam
                 max_margin_at_disagreement=worst_margin if disagree else None, max_logit_err=worst_err,
                 logit_err_bound=logit_err_bound, margin_bound=margin_bound,
                 ok=bool(worst_err <= logit_err_bound and (not disagree or worst_margin < margin_bound)),
-                per_clip=per_clip, results_exact=res_e, results_forced=res_f, traces_exact=tr_e, traces_forced=tr_f)
+                per_clip=per_clip, results_exact=res_e, results_forced=res_f, traces_exact=tr_e, traces_forced=tr_f, contexts_exact=cx_e, contexts_forced=cx_f)
