@@ -2,6 +2,7 @@
 // conversions with pinned rounding, ggml's GELU table lookup, and the GEMM epilogues (identical in both precisions: only the
 // contraction differs).
 #pragma once
+#define SKW_WINDOW_RULES_DEVICE_PART      // (kernel files: skw_window_rules.h without its host rules)
 #include "skw_kernels.h"
 #include "../../include/skw_math.h"
 #include "../../include/skw_ggml_quant.h"

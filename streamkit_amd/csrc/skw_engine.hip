@@ -1188,17 +1188,6 @@ static SkwLogitParams mixed_logit_params(const skw_model* m) {
     return make_logit_params(m, &z);
 }
 
-struct SeqAcc { std::vector<skw_segment> seg; std::vector<skw_token> tok; std::string text; };
-
-// whisper_sequence_score: avg_logprobs + entropy of the last 32 tokens
-static void sequence_score(const SkwTokenOut* tk, int result_len, double* avg_logprobs, double* entropy) {
-    *avg_logprobs = -INFINITY; *entropy = 0.0; if (result_len == 0) return;
-    double result = 0.0; for (int i = 0; i < result_len; ++i) result += tk[i].plog;
-    *avg_logprobs = result / result_len;
-    std::map<int, int> cnts; int cnt = 0; for (int i = std::max(0, result_len - 32); i < result_len; ++i) { cnts[tk[i].id]++; cnt++; }
-    double e = 0.0; for (auto& kv : cnts) { double pp = kv.second / (double)cnt; e -= pp * log(pp); } *entropy = e;
-}
-
 static int load_clips(skw_ctx* c, const float* const* pcm, const int32_t* n_samples, int n, int on_device, std::vector<int>& n_len, std::vector<int>& n_len_org) {
     char* errbuf = c->errbuf;
     std::vector<long> off(n); std::vector<int> ns(n); n_len.resize(n); n_len_org.resize(n);
@@ -1253,356 +1242,405 @@ static int move_retry_slots(skw_ctx* c, const std::vector<int>& old_slots) {
     return 0;
 }
 
-// pv: skw_full_batch_mixed — one skw_full_params per clip (p is then unused).  Everything a request decides is read through P(clip); the sampler takes the rows' rules from
-// device memory (skw_dec_sample_rows).  Without pv every P(clip) is *p and the launches are the uniform ones.
-static int full_batch_impl(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device, skw_result* results,
-                           const int32_t* const* forced_ids, const int32_t* n_forced, std::vector<std::vector<SkwTraceStep>>* traces, uint32_t* const* rng_state = nullptr,
-                           const skw_full_params* pv = nullptr, int32_t* const* context = nullptr) {
-    char* errbuf = c->errbuf; errbuf[0] = 0;
-    WS_READY(c);
-    if (n_clips < 1 || n_clips > c->max_batch) { snprintf(errbuf, 512, "n_clips %d outside [1, %d]", n_clips, c->max_batch); return -1; }
-    const bool mixed = pv != nullptr;
-    auto P = [&](int ci) -> const skw_full_params& { return mixed ? pv[ci] : *p; };
-    for (int i = 0; i < n_clips; ++i) if (P(i).audio_ctx < 0 || P(i).audio_ctx > c->m->hp.n_audio_ctx) {
-        snprintf(errbuf, 512, "clip %d: audio_ctx %d outside [0, %d] (0 = the model's n_audio_ctx)", i, P(i).audio_ctx, c->m->hp.n_audio_ctx); return -3; }
-    auto K_of = [&](int ci) { return P(ci).audio_ctx > 0 ? P(ci).audio_ctx : c->m->hp.n_audio_ctx; };      // the clip's audio context, every window of it
+// ---- skw_full_batch*: one call = validate, load, detect languages, then window batches (plan, stage, prompt pass, step loop, collect) until no clip has audio left, finish.
+// The rules of whisper_full_with_state a window is decided by (ladder, prompt, verdict, prompt_past, segment cut, seek advance, contexts) are skw_window_rules.h; what is here
+// is the GPU orchestration around them.
+
+// What an entry point asks for.  pv: skw_full_batch_mixed — one skw_full_params per clip (p is then unused).  Everything a request decides is read through P(clip); the sampler
+// takes the rows' rules from device memory (skw_dec_sample_rows).  Without pv every P(clip) is *p and the launches are the uniform ones.
+namespace {      // (internal linkage: none of this reaches the library's symbol table)
+struct FullRequest {
+    const skw_full_params* p = nullptr; const skw_full_params* pv = nullptr;
+    const float* const* pcm = nullptr; const int32_t* n_samples = nullptr; int n_clips = 0; int pcm_on_device = 0; skw_result* results = nullptr;
+    const int32_t* const* forced_ids = nullptr; const int32_t* n_forced = nullptr; std::vector<std::vector<SkwTraceStep>>* traces = nullptr;      // tracing / teacher forcing
+    uint32_t* const* rng_state = nullptr; int32_t* const* context = nullptr;
+    bool mixed() const { return pv != nullptr; }
+    bool tracing() const { return traces != nullptr; }
+    const skw_full_params& P(int ci) const { return pv ? pv[ci] : *p; }
+    int K_of(int ci, const skw_hparams& hp) const { return P(ci).audio_ctx > 0 ? P(ci).audio_ctx : hp.n_audio_ctx; }      // the clip's audio context, every window of it
+};
+// The call's host state, per clip unless said otherwise
+struct CallState {
+    explicit CallState(int n) : seek(n, 0), acc(n), temps(n), tidx(n, 0), retry_slot(n, -1), prompt_past(n), last_take(n, 0), lang(n), f_cursor(n, 0) {}
+    std::vector<int> n_len, n_len_org, seek; std::vector<SeqAcc> acc;
+    std::vector<std::vector<float>> temps; std::vector<int> tidx;      // the clip's temperature ladder and the index its current window is decoded at
+    std::vector<int> retry_slot;                                      // the window slot whose cross K/V a retrying clip left behind (-1: not retrying)
+    std::vector<std::vector<int>> prompt_past; std::vector<int> last_take;      // text already produced conditions the next window of the same clip; what the last prompt took of it
+    std::vector<int> lang, f_cursor;                                  // f_cursor (tracing): decisions of the clip made so far (= its position in forced_ids[i])
+    SkwLogitParams lp;
+    float enc_ms = 0.f, dec_ms = 0.f; int tot_windows = 0, tot_steps = 0; long tot_row_steps = 0; int used_groups = 1, used_group_rows = 0;
+};
+// One window batch.  Every vector here is the source of an asynchronous copy: the batch lives until collect_window has synchronised the stream.
+struct WindowBatch {
+    std::vector<int> act, retry_old;      // the clips of the rows; the slots the first R of them (retries) left their cross K/V in
+    int R = 0, Bw = 0, enc_rows = 0, prefill_passes = 0;
+    std::vector<int> sk, ks, pbuf, np_row, fbuf; std::vector<SkwRowRules> rules;      // per row: seek, key count, prompt (SKW_PROMPT_CAP ids) and its length, forced tokens, request rules
+};
+struct RowGroups { int G = 0; int r0[skw_ctx::MAX_GROUPS], n[skw_ctx::MAX_GROUPS]; bool live[skw_ctx::MAX_GROUPS]; };
+}
+
+// finish_call copies the accumulators into the results as bytes: SkwSegment is skw_segment and SkwTokenOut is skw_token, field for field
+#define SAME_FIELD(A, B, f) (offsetof(A, f) == offsetof(B, f) && sizeof(A::f) == sizeof(B::f))
+static_assert(sizeof(SkwSegment) == sizeof(skw_segment) && SAME_FIELD(SkwSegment, skw_segment, t0) && SAME_FIELD(SkwSegment, skw_segment, t1) &&
+              SAME_FIELD(SkwSegment, skw_segment, tok_begin) && SAME_FIELD(SkwSegment, skw_segment, tok_end) && SAME_FIELD(SkwSegment, skw_segment, text_off) &&
+              SAME_FIELD(SkwSegment, skw_segment, text_len), "SkwSegment is skw_segment");
+static_assert(sizeof(SkwTokenOut) == sizeof(skw_token) && SAME_FIELD(SkwTokenOut, skw_token, id) && SAME_FIELD(SkwTokenOut, skw_token, tid) && SAME_FIELD(SkwTokenOut, skw_token, p) &&
+              SAME_FIELD(SkwTokenOut, skw_token, plog) && SAME_FIELD(SkwTokenOut, skw_token, pt) && SAME_FIELD(SkwTokenOut, skw_token, ptsum) &&
+              SAME_FIELD(SkwTokenOut, skw_token, margin), "SkwTokenOut is skw_token");
+#undef SAME_FIELD
+
+static int ensure_trace_buffers(skw_ctx* c) {
+    if (c->trace_dev) return 0;
+    int* f = nullptr; SkwTraceStep* t = nullptr;
+    if (hipMalloc((void**)&f, sizeof(int) * (size_t)c->max_batch * c->max_tok) != hipSuccess || hipMalloc((void**)&t, sizeof(SkwTraceStep) * (size_t)c->max_batch * c->max_tok) != hipSuccess) {
+        hipFree(f); snprintf(c->errbuf, 512, "trace buffers: device allocation failed"); return -1; }
+    c->forced_dev = f; c->trace_dev = t;
+    return 0;
+}
+
+static int validate_request(skw_ctx* c, const FullRequest& rq) {
+    char* errbuf = c->errbuf; const skw_hparams& hp = c->m->hp;
+    if (rq.n_clips < 1 || rq.n_clips > c->max_batch) { snprintf(errbuf, 512, "n_clips %d outside [1, %d]", rq.n_clips, c->max_batch); return -1; }
+    for (int i = 0; i < rq.n_clips; ++i) if (rq.P(i).audio_ctx < 0 || rq.P(i).audio_ctx > hp.n_audio_ctx) {
+        snprintf(errbuf, 512, "clip %d: audio_ctx %d outside [0, %d] (0 = the model's n_audio_ctx)", i, rq.P(i).audio_ctx, hp.n_audio_ctx); return -3; }
     // contexts handed in (skw_full_batch_context) are checked before anything is launched: a refused call leaves every context, like every generator state, as it was
-    if (context) for (int i = 0; i < n_clips; ++i) if (context[i]) {
-        const int32_t* cx = context[i]; const int n = cx[0];
-        if (n < 0 || n > SKW_CONTEXT_WORDS - 1) { snprintf(errbuf, 512, "clip %d: context of %d tokens outside [0, %d]", i, n, SKW_CONTEXT_WORDS - 1); return -3; }
-        for (int k = 0; k < n; ++k) if (cx[1 + k] < 0 || cx[1 + k] >= c->m->hp.n_vocab) {
-            snprintf(errbuf, 512, "clip %d: context token %d (id %d) outside [0, %d)", i, k, cx[1 + k], c->m->hp.n_vocab); return -3; }
-    }
-    HIPCHK(hipSetDevice(c->m->device));
-    const bool tracing = traces != nullptr;
-    std::vector<int> f_cursor(n_clips, 0);      // tracing: decisions of clip i made so far (= its position in forced_ids[i])
-    if (tracing && !c->trace_dev) {
-        int* f = nullptr; SkwTraceStep* t = nullptr;
-        if (hipMalloc((void**)&f, sizeof(int) * (size_t)c->max_batch * c->max_tok) != hipSuccess || hipMalloc((void**)&t, sizeof(SkwTraceStep) * (size_t)c->max_batch * c->max_tok) != hipSuccess) {
-            hipFree(f); snprintf(errbuf, 512, "trace buffers: device allocation failed"); return -1; }
-        c->forced_dev = f; c->trace_dev = t;
-    }
-    skw_model* m = c->m; const skw_hparams& hp = m->hp; const int NV = hp.n_vocab;
-    for (int i = 0; i < n_clips; ++i) { memset(&results[i], 0, sizeof(skw_result)); results[i].min_margin = INFINITY; }
-    std::vector<int> n_len, n_len_org;
+    if (rq.context) for (int i = 0; i < rq.n_clips; ++i) if (rq.context[i] && !skw_context_check(rq.context[i], SKW_CONTEXT_WORDS - 1, hp.n_vocab, i, errbuf, 512)) return -3;
+    return 0;
+}
+
+// clips to the device, the static mask(s), log-mel; the call's per-clip host state
+static int load_call(skw_ctx* c, const FullRequest& rq, CallState& cs) {
+    char* errbuf = c->errbuf; const int n_clips = rq.n_clips;
+    for (int i = 0; i < n_clips; ++i) { memset(&rq.results[i], 0, sizeof(skw_result)); rq.results[i].min_margin = INFINITY; }
     if (c->kclk_on && kclk_reset(c)) return -1;
     HIPCHK(hipEventRecord(c->ev[0], c->stream));
-    if (load_clips(c, pcm, n_samples, n_clips, pcm_on_device, n_len, n_len_org)) return -1;
-    if (mixed) build_static_mask_pair(c); else build_static_mask(c, p);
+    if (load_clips(c, rq.pcm, rq.n_samples, n_clips, rq.pcm_on_device, cs.n_len, cs.n_len_org)) return -1;
+    if (rq.mixed()) build_static_mask_pair(c); else build_static_mask(c, rq.p);
     run_mel(c, n_clips);
     HIPCHK(hipEventRecord(c->ev[1], c->stream));
-    float enc_ms = 0.f, dec_ms = 0.f; int tot_windows = 0, tot_steps = 0, tot_tokens = 0; long tot_row_steps = 0; int used_groups = 1, used_group_rows = 0;
-
-    std::vector<int> seek(n_clips, 0); std::vector<SeqAcc> acc(n_clips);
-    // temperature ladder (whisper_full_with_state): per clip, the index of the temperature its current window is decoded at
-    std::vector<std::vector<float>> temps(n_clips);      // (a clip's own ladder: temperature and temperature_inc are the request's)
-    for (int ci = 0; ci < n_clips; ++ci) {
-        std::vector<float>& tl = temps[ci]; const skw_full_params& q = P(ci); tl.push_back(q.temperature);
-        if (q.temperature_inc > 0.0f) for (float t = q.temperature + q.temperature_inc; t < 1.0f + 1e-6f && tl.size() < 16; t += q.temperature_inc) tl.push_back(t);
-    }
-    std::vector<int> tidx(n_clips, 0), retry_slot(n_clips, -1);   // retry_slot: the window slot whose cross K/V a retrying clip left behind (-1: not retrying)
-    // prompt_past (whisper_full_with_state): text already produced in this call conditions the next window of the same clip
-    std::vector<std::vector<int>> prompt_past(n_clips); std::vector<int> last_take(n_clips, 0);
+    for (int ci = 0; ci < n_clips; ++ci) cs.temps[ci] = skw_temperature_ladder(rq.P(ci).temperature, rq.P(ci).temperature_inc);      // (a clip's own ladder)
     // a clip's context (skw_full_batch_context) is its prompt_past as whisper_full_with_state's window loop finds it: the first window takes from it under the rules of every later one
-    if (context) for (int i = 0; i < n_clips; ++i) if (context[i]) prompt_past[i].assign(context[i] + 1, context[i] + 1 + context[i][0]);
+    if (rq.context) for (int i = 0; i < n_clips; ++i) if (rq.context[i]) cs.prompt_past[i].assign(rq.context[i] + 1, rq.context[i] + 1 + rq.context[i][0]);
     // the sampled passes' generator: whisper.cpp keeps ONE std::mt19937 per state (decoder 0, seeded with 0 when the state is created) and lets it run on across calls.  A caller
     // that owns such a stream per clip (the plugin: one per instance, lib.rs:377-379) hands its state in and gets it back (skw_full_batch_rng); without one the stream starts at
     // seed 0 in every call (D2': what a batch of unrelated clips can do)
     skw_rng_seed(c->rng, n_clips, 0u, c->stream);
-    if (rng_state) for (int i = 0; i < n_clips; ++i) if (rng_state[i]) {
-        if (rng_state[i][624] > 624u) { snprintf(errbuf, 512, "clip %d: the generator state handed in is not a std::mt19937 state (index %u)", i, rng_state[i][624]); return -1; }
-        HIPCHK(hipMemcpyAsync(c->rng + (size_t)i * SKW_RNG_WORDS, rng_state[i], sizeof(uint32_t) * SKW_RNG_WORDS, hipMemcpyHostToDevice, c->stream));
+    if (rq.rng_state) for (int i = 0; i < n_clips; ++i) if (rq.rng_state[i]) {
+        if (rq.rng_state[i][624] > 624u) { snprintf(errbuf, 512, "clip %d: the generator state handed in is not a std::mt19937 state (index %u)", i, rq.rng_state[i][624]); return -1; }
+        HIPCHK(hipMemcpyAsync(c->rng + (size_t)i * SKW_RNG_WORDS, rq.rng_state[i], sizeof(uint32_t) * SKW_RNG_WORDS, hipMemcpyHostToDevice, c->stream));
     }
-    // language: fixed by the caller, or (lang_id < 0, whisper.cpp's "auto") detected per clip from the [sot] step on the first window
-    std::vector<int> lang(n_clips); bool any_auto = false;
-    for (int i = 0; i < n_clips; ++i) { lang[i] = P(i).lang_id; results[i].lang_id = lang[i]; if (lang[i] < 0 && !any_auto) { any_auto = true;
-        if (NV < 51865) { if (mixed) snprintf(errbuf, 512, "failed to auto-detect language: the model is not multilingual (clip %d)", i);
+    return 0;
+}
+
+// language: fixed by the caller, or (lang_id < 0, whisper.cpp's "auto") detected per clip from the [sot] step on the first window
+static int detect_languages(skw_ctx* c, const FullRequest& rq, CallState& cs) {
+    char* errbuf = c->errbuf; skw_model* m = c->m; const int NV = m->hp.n_vocab, n_clips = rq.n_clips; std::vector<int>& lang = cs.lang;
+    bool any_auto = false;
+    for (int i = 0; i < n_clips; ++i) { lang[i] = rq.P(i).lang_id; rq.results[i].lang_id = lang[i]; if (lang[i] < 0 && !any_auto) { any_auto = true;
+        if (NV < 51865) { if (rq.mixed()) snprintf(errbuf, 512, "failed to auto-detect language: the model is not multilingual (clip %d)", i);
                           else snprintf(errbuf, 512, "failed to auto-detect language: the model is not multilingual");
                           return -3; } } }
-    if (any_auto) {      // the detection pass runs on the rows that asked for it
-        std::vector<int> act, zero(n_clips, 0); for (int i = 0; i < n_clips; ++i) if (lang[i] < 0 && n_len_org[i] > 0) act.push_back(i);
-        const int Bd = (int)act.size();
-        if (Bd > 0) {
-            HIPCHK(hipMemcpyAsync(c->clip_idx, act.data(), sizeof(int) * Bd, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->seek, zero.data(), sizeof(int) * Bd, hipMemcpyHostToDevice, c->stream));
-            std::vector<int> kd(Bd); for (int j = 0; j < Bd; ++j) kd[j] = K_of(act[j]);      // detection sees the first window as the clip's own audio_ctx shapes it
-            const int rows_d = set_slot_k(c, kd.data(), Bd, 0, c->stream);
-            run_conv(c, Bd, 0, rows_d); run_encoder(c, Bd, false, true, 0, rows_d);
-            hipLaunchKernelGGL(k_set_tokens, dim3(Bd), dim3(1), 0, c->stream, c->st, m->tok_sot, 0, c->slot_k);
-            run_decoder_step(c, 0, Bd, 0, true, c->stream);
-            hipLaunchKernelGGL(k_lang_argmax, dim3(Bd), dim3(64), 0, c->stream, c->logits, NV, m->tok_sot, m->n_lang, c->row_tok);
-            std::vector<int> det(Bd); HIPCHK(hipMemcpyAsync(det.data(), c->row_tok, sizeof(int) * Bd, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
-            for (int j = 0; j < Bd; ++j) { lang[act[j]] = det[j]; results[act[j]].lang_id = det[j]; }
-        }
-        for (int i = 0; i < n_clips; ++i) if (lang[i] < 0) { lang[i] = 0; results[i].lang_id = 0; }
+    if (!any_auto) return 0;
+    // the detection pass runs on the rows that asked for it
+    std::vector<int> act, zero(n_clips, 0); for (int i = 0; i < n_clips; ++i) if (lang[i] < 0 && cs.n_len_org[i] > 0) act.push_back(i);
+    const int Bd = (int)act.size();
+    if (Bd > 0) {
+        HIPCHK(hipMemcpyAsync(c->clip_idx, act.data(), sizeof(int) * Bd, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->seek, zero.data(), sizeof(int) * Bd, hipMemcpyHostToDevice, c->stream));
+        std::vector<int> kd(Bd); for (int j = 0; j < Bd; ++j) kd[j] = rq.K_of(act[j], m->hp);      // detection sees the first window as the clip's own audio_ctx shapes it
+        const int rows_d = set_slot_k(c, kd.data(), Bd, 0, c->stream);
+        run_conv(c, Bd, 0, rows_d); run_encoder(c, Bd, false, true, 0, rows_d);
+        hipLaunchKernelGGL(k_set_tokens, dim3(Bd), dim3(1), 0, c->stream, c->st, m->tok_sot, 0, c->slot_k);
+        run_decoder_step(c, 0, Bd, 0, true, c->stream);
+        hipLaunchKernelGGL(k_lang_argmax, dim3(Bd), dim3(64), 0, c->stream, c->logits, NV, m->tok_sot, m->n_lang, c->row_tok);
+        std::vector<int> det(Bd); HIPCHK(hipMemcpyAsync(det.data(), c->row_tok, sizeof(int) * Bd, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
+        for (int j = 0; j < Bd; ++j) { lang[act[j]] = det[j]; rq.results[act[j]].lang_id = det[j]; }
     }
-    // sot, language, task (, notimestamps): the tail of a row's prompt, from its clip's request
-    auto prompt_tail = [&](int ci, int32_t* out) {
-        const skw_full_params& q = P(ci); int n = 0;
-        out[n++] = m->tok_sot;
-        if (NV >= 51865) { out[n++] = m->tok_sot + 1 + lang[ci]; out[n++] = q.translate ? m->tok_translate : m->tok_transcribe; }
-        if (q.no_timestamps) out[n++] = m->tok_not;
-        return n;
-    };
-    SkwLogitParams lp = mixed ? mixed_logit_params(m) : make_logit_params(m, p);
+    for (int i = 0; i < n_clips; ++i) if (lang[i] < 0) { lang[i] = 0; rq.results[i].lang_id = 0; }
+    return 0;
+}
 
-    while (true) {
-        // clips that still have audio to decode ("if only 100ms left, then stop"; "input is too short": delta_min = 10 frames, whisper.cpp #2065)
-        // Windows that are decoded again at the next temperature come first: their cross K/V are still in HBM (at last round's slot) and move
-        // to slots 0 .. R-1; the encoder then runs only on the new windows, slots R .. Bw-1.
-        std::vector<int> act, retry_old;
-        for (int i = 0; i < n_clips; ++i) if (retry_slot[i] >= 0) { act.push_back(i); retry_old.push_back(retry_slot[i]); }
-        const int R = (int)act.size();
-        for (int i = 0; i < n_clips; ++i) if (retry_slot[i] < 0 && n_len_org[i] >= SKW_DELTA_MIN && seek[i] + SKW_DELTA_MIN < n_len_org[i]) act.push_back(i);
-        if (act.empty()) break;
-        const int Bw = (int)act.size();
-        if (R > 0 && move_retry_slots(c, retry_old)) return -1;
-        for (int j = 0; j < Bw; ++j) retry_slot[act[j]] = -1;
-        std::vector<int> sk(Bw); for (int j = 0; j < Bw; ++j) sk[j] = seek[act[j]];
-        HIPCHK(hipMemcpyAsync(c->clip_idx, act.data(), sizeof(int) * Bw, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->seek, sk.data(), sizeof(int) * Bw, hipMemcpyHostToDevice, c->stream));
-        // the slots' audio contexts: a retried window (slots 0 .. R-1) keeps its clip's K with the cross K/V it moved
-        std::vector<int> ks(Bw); for (int j = 0; j < Bw; ++j) ks[j] = K_of(act[j]);
-        const int enc_rows = set_slot_k(c, ks.data(), Bw, R, c->stream);
-        // per-row prompt: [prev] + the last n_text_ctx/2 tokens of the clip's prompt_past (passes at t < 0.5 only) + sot, language, task (, notimestamps)
-        std::vector<int> pbuf((size_t)Bw * SKW_PROMPT_CAP, 0), np_row(Bw, 0);
+// sot, language, task (, notimestamps): the tail of a row's prompt, from its clip's request
+static int prompt_tail(const skw_model* m, const skw_full_params& q, int lang, int32_t* out) {
+    int n = 0;
+    out[n++] = m->tok_sot;
+    if (m->hp.n_vocab >= 51865) { out[n++] = m->tok_sot + 1 + lang; out[n++] = q.translate ? m->tok_translate : m->tok_transcribe; }
+    if (q.no_timestamps) out[n++] = m->tok_not;
+    return n;
+}
+
+// The clips that still have audio to decode ("if only 100ms left, then stop"; "input is too short": delta_min = 10 frames, whisper.cpp #2065).  Windows that are decoded again at
+// the next temperature come first: their cross K/V are still in HBM (at last round's slot) and move to slots 0 .. R-1; the encoder then runs only on the new windows, slots
+// R .. Bw-1.  false: nothing is left.
+static bool plan_window(const FullRequest& rq, const CallState& cs, WindowBatch& w) {
+    for (int i = 0; i < rq.n_clips; ++i) if (cs.retry_slot[i] >= 0) { w.act.push_back(i); w.retry_old.push_back(cs.retry_slot[i]); }
+    w.R = (int)w.act.size();
+    for (int i = 0; i < rq.n_clips; ++i) if (cs.retry_slot[i] < 0 && cs.n_len_org[i] >= SKW_DELTA_MIN && cs.seek[i] + SKW_DELTA_MIN < cs.n_len_org[i]) w.act.push_back(i);
+    w.Bw = (int)w.act.size();
+    return w.Bw > 0;
+}
+
+// retried slots moved, the rows' seeks / key counts / prompts / rules / forced tokens uploaded, the encoder on the new windows, the rows' decoder state (host side)
+static int stage_window(skw_ctx* c, const FullRequest& rq, CallState& cs, WindowBatch& w) {
+    char* errbuf = c->errbuf; skw_model* m = c->m; const skw_hparams& hp = m->hp; const int Bw = w.Bw, R = w.R; const std::vector<int>& act = w.act;
+    if (R > 0 && move_retry_slots(c, w.retry_old)) return -1;
+    for (int j = 0; j < Bw; ++j) cs.retry_slot[act[j]] = -1;
+    w.sk.resize(Bw); for (int j = 0; j < Bw; ++j) w.sk[j] = cs.seek[act[j]];
+    HIPCHK(hipMemcpyAsync(c->clip_idx, act.data(), sizeof(int) * Bw, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->seek, w.sk.data(), sizeof(int) * Bw, hipMemcpyHostToDevice, c->stream));
+    // the slots' audio contexts: a retried window (slots 0 .. R-1) keeps its clip's K with the cross K/V it moved
+    w.ks.resize(Bw); for (int j = 0; j < Bw; ++j) w.ks[j] = rq.K_of(act[j], hp);
+    w.enc_rows = set_slot_k(c, w.ks.data(), Bw, R, c->stream);
+    w.pbuf.assign((size_t)Bw * SKW_PROMPT_CAP, 0); w.np_row.assign(Bw, 0);
+    for (int j = 0; j < Bw; ++j) {
+        const int ci = act[j]; int32_t tail[8]; const int n_tail = prompt_tail(m, rq.P(ci), cs.lang[ci], tail);
+        w.np_row[j] = skw_row_prompt(cs.prompt_past[ci], cs.temps[ci][cs.tidx[ci]], tail, n_tail, hp.n_text_ctx, cs.lp.n_max, m->tok_prev, w.pbuf.data() + (size_t)j * SKW_PROMPT_CAP,
+                                     &cs.last_take[ci]);
+    }
+    HIPCHK(hipMemcpyAsync(c->prompt_buf, w.pbuf.data(), sizeof(int) * w.pbuf.size(), hipMemcpyHostToDevice, c->stream));
+    if (rq.mixed()) {
+        w.rules.resize(Bw); for (int j = 0; j < Bw; ++j) w.rules[j] = make_row_rules(m, &rq.P(act[j]));
+        HIPCHK(hipMemcpyAsync(c->row_rules, w.rules.data(), sizeof(SkwRowRules) * Bw, hipMemcpyHostToDevice, c->stream));
+    }
+    cs.lp.any_sampled = 0; for (int j = 0; j < Bw; ++j) if (cs.temps[act[j]][cs.tidx[act[j]]] > 0.0f) cs.lp.any_sampled = 1;      // (part of the step graph's key: greedy passes run the lean sampler)
+    if (rq.tracing()) {      // this pass's forced tokens per row: the clip's sequence from its cursor on (-1 = none: the row feeds its own choices)
+        w.fbuf.assign((size_t)Bw * c->max_tok, -1);
+        if (rq.forced_ids) for (int j = 0; j < Bw; ++j) { const int ci = act[j]; if (!rq.forced_ids[ci]) continue;
+            for (int k = 0; k < c->max_tok && cs.f_cursor[ci] + k < rq.n_forced[ci]; ++k) w.fbuf[(size_t)j * c->max_tok + k] = rq.forced_ids[ci][cs.f_cursor[ci] + k]; }
+        HIPCHK(hipMemcpyAsync(c->forced_dev, w.fbuf.data(), sizeof(int) * w.fbuf.size(), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(hipEventRecord(c->ev[2], c->stream));
+    if (R < Bw) { run_conv(c, Bw, R, w.enc_rows); run_encoder(c, Bw, false, true, R, w.enc_rows); }
+    HIPCHK(hipEventRecord(c->ev[3], c->stream));
+    // decoder state
+    for (int j = 0; j < Bw; ++j) {
+        SkwSeqState& s = c->h_st[j]; memset(&s, 0, sizeof s);
+        s.active = 1; s.seek_delta = SKW_WINDOW_FRAMES; s.seek = w.sk[j];
+        s.seek_end = cs.n_len_org[act[j]]; s.n_prompt = w.np_row[j]; s.min_margin = INFINITY; s.cur_token = w.pbuf[(size_t)j * SKW_PROMPT_CAP]; s.cur_pos = 0;
+        s.temperature = cs.temps[act[j]][cs.tidx[act[j]]]; s.n_keys = w.ks[j];
+    }
+    return 0;
+}
+
+// The prompt in one pass (whisper.cpp evaluates it in one whisper_decode call): every prompt token but a row's last becomes a row of ONE decoder pass —
+// the step's own kernels, a row per (sequence, position), the caches addressed through the row's sequence — which fills the self-attention K / V
+// of those positions in every layer; the rows then start at their last prompt token, whose logits the first sampling step needs.  A window of a long
+// file carries up to 224 tokens of previous text in its prompt: 225 steps of 1.4 ms become one pass.  Per-row arithmetic does not depend on what else is
+// in the batch, so the results are the stepped ones, bit for bit (tests/test_gpu_parity.py).  Ends with the rows' decoder state on the device.
+static int prompt_pass(skw_ctx* c, WindowBatch& w) {
+    char* errbuf = c->errbuf; const int Bw = w.Bw;
+    if (c->prompt_pass_on) {
+        const int ntc = c->m->hp.n_text_ctx;
+        std::vector<SkwSeqState> pf; std::vector<int> row_end;      // row_end: cumulative rows after each sequence (chunks are whole sequences)
         for (int j = 0; j < Bw; ++j) {
-            const int ci = act[j]; int* pr = pbuf.data() + (size_t)j * SKW_PROMPT_CAP; int n = 0, take = 0;
-            int32_t prompt[8]; const int n_prompt = prompt_tail(ci, prompt);
-            if (!prompt_past[ci].empty() && temps[ci][tidx[ci]] < 0.5f) {
-                // the last bound only binds with no_timestamps: every position stays inside n_text_ctx
-                take = std::min(std::min(hp.n_text_ctx / 2, (int)prompt_past[ci].size()), hp.n_text_ctx - lp.n_max - n_prompt - 1);
-                pr[n++] = m->tok_prev; for (int i = 0; i < take; ++i) pr[n++] = prompt_past[ci][prompt_past[ci].size() - take + i];
-            }
-            last_take[ci] = take;
-            for (int t = 0; t < n_prompt; ++t) pr[n++] = prompt[t];
-            np_row[j] = n;
+            for (int k = 0; k + 1 < w.np_row[j]; ++k) { SkwSeqState t; memset(&t, 0, sizeof t);
+            t.active = 1; t.cur_token = w.pbuf[(size_t)j * SKW_PROMPT_CAP + k]; t.cur_pos = k; t.pad = j; t.seek = j * ntc + k; t.n_keys = w.ks[j]; pf.push_back(t); }
+            row_end.push_back((int)pf.size());
+            c->h_st[j].cur_token = w.pbuf[(size_t)j * SKW_PROMPT_CAP + w.np_row[j] - 1]; c->h_st[j].cur_pos = w.np_row[j] - 1;
         }
-        HIPCHK(hipMemcpyAsync(c->prompt_buf, pbuf.data(), sizeof(int) * pbuf.size(), hipMemcpyHostToDevice, c->stream));
-        std::vector<SkwRowRules> rules;      // (alive until the stream is synchronised at the end of the window)
-        if (mixed) {
-            rules.resize(Bw); for (int j = 0; j < Bw; ++j) rules[j] = make_row_rules(m, &P(act[j]));
-            HIPCHK(hipMemcpyAsync(c->row_rules, rules.data(), sizeof(SkwRowRules) * Bw, hipMemcpyHostToDevice, c->stream));
-        }
-        lp.any_sampled = 0; for (int j = 0; j < Bw; ++j) if (temps[act[j]][tidx[act[j]]] > 0.0f) lp.any_sampled = 1;      // (part of the step graph's key: greedy passes run the lean sampler)
-        std::vector<int> fbuf;
-        if (tracing) {      // this pass's forced tokens per row: the clip's sequence from its cursor on (-1 = none: the row feeds its own choices)
-            fbuf.assign((size_t)Bw * c->max_tok, -1);
-            if (forced_ids) for (int j = 0; j < Bw; ++j) { const int ci = act[j]; if (!forced_ids[ci]) continue;
-                for (int k = 0; k < c->max_tok && f_cursor[ci] + k < n_forced[ci]; ++k) fbuf[(size_t)j * c->max_tok + k] = forced_ids[ci][f_cursor[ci] + k]; }
-            HIPCHK(hipMemcpyAsync(c->forced_dev, fbuf.data(), sizeof(int) * fbuf.size(), hipMemcpyHostToDevice, c->stream));
-        }
-        HIPCHK(hipEventRecord(c->ev[2], c->stream));
-        if (R < Bw) { run_conv(c, Bw, R, enc_rows); run_encoder(c, Bw, false, true, R, enc_rows); }
-        HIPCHK(hipEventRecord(c->ev[3], c->stream));
-        // decoder state
-        for (int j = 0; j < Bw; ++j) {
-            SkwSeqState& s = c->h_st[j]; memset(&s, 0, sizeof s);
-            s.active = 1; s.seek_delta = 100 * WHISPER_CHUNK_SIZE; s.seek = sk[j];
-            s.seek_end = n_len_org[act[j]]; s.n_prompt = np_row[j]; s.min_margin = INFINITY; s.cur_token = pbuf[(size_t)j * SKW_PROMPT_CAP]; s.cur_pos = 0;
-            s.temperature = temps[act[j]][tidx[act[j]]]; s.n_keys = ks[j];
-        }
-        // The prompt in one pass (whisper.cpp evaluates it in one whisper_decode call): every prompt token but a row's last becomes a row of ONE decoder pass —
-        // the step's own kernels, a row per (sequence, position), the caches addressed through the row's sequence — which fills the self-attention K / V
-        // of those positions in every layer; the rows then start at their last prompt token, whose logits the first sampling step needs.  A window of a long
-        // file carries up to 224 tokens of previous text in its prompt: 225 steps of 1.4 ms become one pass.  Per-row arithmetic does not depend on what else is
-        // in the batch, so the results are the stepped ones, bit for bit (tests/test_gpu_parity.py).
-        int prefill_passes = 0;
-        if (c->prompt_pass_on) {
-            const int ntc = hp.n_text_ctx;
-            std::vector<SkwSeqState> pf; std::vector<int> row_end;      // row_end: cumulative rows after each sequence (chunks are whole sequences)
-            for (int j = 0; j < Bw; ++j) {
-                for (int k = 0; k + 1 < np_row[j]; ++k) { SkwSeqState t; memset(&t, 0, sizeof t);
-                t.active = 1; t.cur_token = pbuf[(size_t)j * SKW_PROMPT_CAP + k]; t.cur_pos = k; t.pad = j; t.seek = j * ntc + k; t.n_keys = ks[j]; pf.push_back(t); }
-                row_end.push_back((int)pf.size());
-                c->h_st[j].cur_token = pbuf[(size_t)j * SKW_PROMPT_CAP + np_row[j] - 1]; c->h_st[j].cur_pos = np_row[j] - 1;
+        size_t lo = 0; int jlo = 0;
+        while (lo < pf.size()) {
+            int jhi = jlo; while (jhi < Bw && row_end[jhi] - (int)lo <= c->rows_cap) ++jhi;      // sequences jlo .. jhi-1 fit (a prompt is at most SKW_PROMPT_CAP - 1 <= rows_cap rows)
+            const size_t hi = row_end[jhi - 1]; const int n = (int)(hi - lo);
+            if (n > 0) {
+                HIPCHK(hipMemcpyAsync(c->pf_st, pf.data() + lo, sizeof(SkwSeqState) * n, hipMemcpyHostToDevice, c->stream));
+                std::vector<int> meta((size_t)3 * c->max_batch, 0); int ns = 0, nqmax = 0;
+                for (int j = jlo; j < jhi; ++j) { const int r0j = (j ? row_end[j - 1] : 0) - (int)lo, nqj = row_end[j] - (j ? row_end[j - 1] : 0); if (nqj <= 0) continue;
+                    meta[ns] = r0j; meta[c->max_batch + ns] = nqj; meta[2 * c->max_batch + ns] = j; nqmax = std::max(nqmax, nqj); ++ns; }
+                HIPCHK(hipMemcpyAsync(c->pf_meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, c->stream));
+                c->pf_nseq = ns; c->pf_nq_max = nqmax;
+                run_decoder_step(c, 0, n, 0, false, c->stream, true);
+                c->pf_nseq = 0;
+                HIPCHK(hipStreamSynchronize(c->stream));      // (pf and meta are host vectors and pf_st is reused by the next chunk)
+                ++w.prefill_passes;
             }
-            size_t lo = 0; int jlo = 0;
-            while (lo < pf.size()) {
-                int jhi = jlo; while (jhi < Bw && row_end[jhi] - (int)lo <= c->rows_cap) ++jhi;      // sequences jlo .. jhi-1 fit (a prompt is at most SKW_PROMPT_CAP - 1 <= rows_cap rows)
-                const size_t hi = row_end[jhi - 1]; const int n = (int)(hi - lo);
-                if (n > 0) {
-                    HIPCHK(hipMemcpyAsync(c->pf_st, pf.data() + lo, sizeof(SkwSeqState) * n, hipMemcpyHostToDevice, c->stream));
-                    std::vector<int> meta((size_t)3 * c->max_batch, 0); int ns = 0, nqmax = 0;
-                    for (int j = jlo; j < jhi; ++j) { const int r0j = (j ? row_end[j - 1] : 0) - (int)lo, nqj = row_end[j] - (j ? row_end[j - 1] : 0); if (nqj <= 0) continue;
-                        meta[ns] = r0j; meta[c->max_batch + ns] = nqj; meta[2 * c->max_batch + ns] = j; nqmax = std::max(nqmax, nqj); ++ns; }
-                    HIPCHK(hipMemcpyAsync(c->pf_meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, c->stream));
-                    c->pf_nseq = ns; c->pf_nq_max = nqmax;
-                    run_decoder_step(c, 0, n, 0, false, c->stream, true);
-                    c->pf_nseq = 0;
-                    HIPCHK(hipStreamSynchronize(c->stream));      // (pf is a host vector and pf_st is reused by the next chunk)
-                    ++prefill_passes;
-                }
-                lo = hi; jlo = jhi;
-            }
-        }
-        HIPCHK(hipMemcpyAsync(c->st, c->h_st, sizeof(SkwSeqState) * Bw, hipMemcpyHostToDevice, c->stream));
-        // row groups: G contiguous ranges of the window batch, each on its own stream (one group while profiling, so kernel times do not overlap)
-        const bool profiling = c->prof && c->prof->on;
-        // Default: ONE row group in both precisions.  Rounds 3-4 shipped two groups for f16_mfma at >= 64 rows (+1.3 % on the step in a same-box A/B, profiles/r04g).  Round 5's in-kernel
-        // launch clock (skw_ctx_kernel_clock) showed what that bought and cost: the groups' cross-attention launches overlap for 27 % of their time and stretch each other from 28 to
-        // 35-37 us, a profiler serialises the two streams (its per-kernel averages then describe launches that never ran: decode 129 -> 197 ms under rocprofv3), and the dispatch
-        // front end is a serial resource — two chains of small kernels on two streams gain ~20 % over one (tools/probe/probe_stream_overlap.hip) while the launch count doubles.
-        // Same-box, round 5 (profiles/r05d): 167.13 ms (two groups) vs 167.59 ms (one) per 64-clip step — inside the +-1.5 % two builds differ by — with the dominant kernel at
-        // 0.47 of HBM peak per launch (0.66 while any launch is in flight) against 0.77 as one group.  One group: clock, HIP events and rocprofv3 agree on every launch within 2 %.
-        // The exact precision loses 3 % with two groups, smaller batches more (16-row launches).  SKW_DECODE_GROUPS=n overrides.
-        const int n_groups = c->n_groups > 0 ? c->n_groups : 1;
-        // (f16_mfma, one group: eager launches 8 steps ahead measure the same 179 ms; the graph leaves the host idle, which matters with eight ranks on one node)
-        const bool use_graphs = c->use_graphs >= 0 ? c->use_graphs != 0 : true;
-        // Groups are cut at multiples of 16 rows: the f16_mfma step keeps its attention / FC1 outputs as fragment-order images (skw_afrag_off), which
-        // scatter a group's rows over whole 16-row tiles of its scratch — two groups sharing a tile would overwrite each other.
-        int g_r0[skw_ctx::MAX_GROUPS], g_n[skw_ctx::MAX_GROUPS]; bool g_live[skw_ctx::MAX_GROUPS];
-        int G = 0;
-        {
-            const int Gw = std::max(1, std::min(n_groups, Bw / 8));
-            int prev = 0;
-            for (int g = 1; g <= Gw; ++g) {
-                const int cut = g == Gw ? Bw : std::min(Bw, (int)(((long)Bw * g / Gw + 8) & ~15L));
-                if (cut > prev) { g_r0[G] = prev; g_n[G] = cut - prev; g_live[G] = true; ++G; prev = cut; }
-            }
-        }
-        used_groups = G; used_group_rows = g_n[0];
-        for (int j = 0; j < Bw; ++j) c->h_row_live[j] = 1;      // (every kernel of the previous window has drained: c->stream was synchronised at its end)
-        HIPCHK(hipEventRecord(c->ev[5], c->stream));
-        for (int g = 0; g < G; ++g) HIPCHK(hipStreamWaitEvent(c->gstream[g], c->ev[5], 0));
-        // every step = decoder step (token and position from the device state) + k_dec_sample, which feeds the next prompt token
-        // while a row is still inside its prompt and samples afterwards; rows have prompts of different lengths
-        hipGraphExec_t gexec[skw_ctx::MAX_GROUPS] = {};
-        if (use_graphs && !profiling && !tracing) for (int g = 0; g < G; ++g) gexec[g] = step_graph(c, g, g_r0[g], g_n[g], lp, mixed);   // nullptr -> eager launches
-        auto sample = [&](int g) {
-            c->cur = c->gstream[g];
-            { ProfScope p_(c, PC_DEC_SAMPLE, 0, 4.0 * g_n[g] * NV);
-              if (mixed) skw_dec_sample_rows(c->logits + (size_t)g_r0[g] * NV, c->static_mask_pair, lp, c->row_rules + g_r0[g], c->st + g_r0[g],
-                c->toks + (size_t)g_r0[g] * c->max_tok, c->max_tok, g_n[g], c->d_row_live + g_r0[g], c->probs + (size_t)g_r0[g] * skw_probs_row_floats(NV), c->rng,
-                c->clip_idx + g_r0[g], c->prompt_buf + (size_t)g_r0[g] * SKW_PROMPT_CAP, c->gstream[g]);
-              else skw_dec_sample(c->logits + (size_t)g_r0[g] * NV, c->static_mask, lp, c->st + g_r0[g],
-                c->toks + (size_t)g_r0[g] * c->max_tok, c->max_tok, g_n[g], c->d_row_live + g_r0[g], c->probs + (size_t)g_r0[g] * skw_probs_row_floats(NV), c->rng,
-                c->clip_idx + g_r0[g], c->prompt_buf + (size_t)g_r0[g] * SKW_PROMPT_CAP, c->gstream[g],
-                                                                                     tracing ? c->forced_dev + (size_t)g_r0[g] * c->max_tok : nullptr,
-                                                                                         tracing ? c->trace_dev + (size_t)g_r0[g] * c->max_tok : nullptr); }
-            c->cur = c->stream;
-            return hipSuccess;
-        };
-        // The host learns whether a group still has live rows only by waiting for its stream, and a wait + relaunch per step leaves the
-        // GPU idle for the turnaround.  So steps are enqueued `ahead` at a time and the count is read once per block: a step that
-        // runs after the last row of its group has finished changes nothing (its attention and sampling kernels return at once for
-        // finished rows; what the GEMMs write for them is scratch), it only costs its launches.
-        const int step_cap = SKW_PROMPT_CAP + lp.n_max + 2;
-        const int ahead = profiling ? 1 : 8;
-        for (int i = 0; i < step_cap; i += ahead) {
-            const int nstep = std::min(ahead, step_cap - i);
-            for (int k = 0; k < nstep; ++k)
-                for (int g = 0; g < G; ++g) if (g_live[g]) {
-                    if (gexec[g]) HIPCHK(hipGraphLaunch(gexec[g], c->gstream[g]));
-                    else {
-                        // (ahead == 1: the previous step has drained)
-                        if (profiling) { int lv = 0; for (int j = g_r0[g]; j < g_r0[g] + g_n[g]; ++j) lv += ((volatile int*)c->h_row_live)[j] != 0; c->live_rows_hint = lv; }
-                        c->cur_group = g;
-                        run_decoder_step(c, g_r0[g], g_n[g], i + k, true, c->gstream[g]); c->live_rows_hint = -1; c->cur_group = 0; HIPCHK(sample(g));
-                    }
-                }
-            bool any = false;
-            for (int g = 0; g < G; ++g) if (g_live[g]) { HIPCHK(hipStreamSynchronize(c->gstream[g]));
-            int live = 0; for (int j = g_r0[g]; j < g_r0[g] + g_n[g]; ++j) live += ((volatile int*)c->h_row_live)[j] != 0;
-                                                        if (live <= 0) g_live[g] = false; else any = true; }
-            if (!any) break;
-        }
-        for (int g = 0; g < G; ++g) { HIPCHK(hipEventRecord(c->gev[g], c->gstream[g])); HIPCHK(hipStreamWaitEvent(c->stream, c->gev[g], 0)); }
-        HIPCHK(hipMemcpyAsync(c->h_st, c->st, sizeof(SkwSeqState) * Bw, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(c->h_toks, c->toks, sizeof(SkwTokenOut) * Bw * c->max_tok, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipEventRecord(c->ev[4], c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (tracing) {
-            std::vector<SkwTraceStep> tb((size_t)Bw * c->max_tok);
-            HIPCHK(hipMemcpy(tb.data(), c->trace_dev, sizeof(SkwTraceStep) * tb.size(), hipMemcpyDeviceToHost));
-            for (int j = 0; j < Bw; ++j) {
-                const int ci = act[j], n = std::min(c->h_st[j].n_tokens, c->max_tok);
-                if (forced_ids && forced_ids[ci] && f_cursor[ci] + n > n_forced[ci]) { snprintf(errbuf, 512,
-                    "clip %d: forced token sequence exhausted (%d given, decision %d reached): the runs' control flow diverged", ci, n_forced[ci], f_cursor[ci] + n);
-                return -4; }
-                (*traces)[ci].insert((*traces)[ci].end(), tb.begin() + (size_t)j * c->max_tok, tb.begin() + (size_t)j * c->max_tok + n);
-                f_cursor[ci] += n;
-            }
-        }
-        { float a = 0, b = 0; hipEventElapsedTime(&a, c->ev[2], c->ev[3]); hipEventElapsedTime(&b, c->ev[3], c->ev[4]); enc_ms += a; dec_ms += b; }
-        tot_windows += Bw;
-        // decoder passes until the last row finished (the prompt pass counts as one); row-steps: (row, token) pairs that streamed cross K / V, prompt tokens included
-        { int mx = 0; for (int j = 0; j < Bw; ++j) { const int rs = c->h_st[j].n_prompt - 1 + c->h_st[j].n_tokens;
-        mx = std::max(mx, c->prompt_pass_on ? c->h_st[j].n_tokens : rs); tot_row_steps += rs; } tot_steps += mx + prefill_passes; }
-        // per-clip: ranking, segment assembly, seek update (whisper_full_with_state tail)
-        for (int j = 0; j < Bw; ++j) {
-            const int ci = act[j]; const SkwSeqState& s = c->h_st[j]; const SkwTokenOut* tk = c->h_toks + (size_t)j * c->max_tok; skw_result& R = results[ci]; SeqAcc& A = acc[ci];
-            const skw_full_params* p = &P(ci);      // the clip's own request from here on
-            if (tidx[ci] == 0) R.n_windows++;
-            R.n_decode_steps += 1 + std::max(0, s.n_tokens - 1);     // the prompt is one decode call in whisper.cpp, then one per sampled token but the last
-            bool failed = s.failed != 0; int n_tok = s.n_tokens; const int result_len = s.result_len;
-            double avg_logprobs = -INFINITY, entropy = 0.0;
-            if (!failed) { n_tok = result_len; sequence_score(tk, result_len, &avg_logprobs, &entropy); if (result_len > 32 && entropy < p->entropy_thold) failed = true; }
-            if (s.min_margin < R.min_margin) R.min_margin = s.min_margin;
-            if (failed || (avg_logprobs < p->logprob_thold && s.no_speech_prob < p->no_speech_thold)) {
-                R.fallback_requested++;
-                if (tidx[ci] + 1 < (int)temps[ci].size()) { tidx[ci]++; retry_slot[ci] = j; continue; }   // this window again, at the next temperature, on the cross K/V it already has (slot j)
-            }
-            tidx[ci] = 0;
-            int seek_delta = s.seek_delta;
-            const bool is_no_speech = (s.no_speech_prob > p->no_speech_thold && avg_logprobs < p->logprob_thold);
-            {   // update prompt_past: what this window's prompt took from it is always kept; this window's tokens only when it is speech
-                std::vector<int>& pp = prompt_past[ci]; std::vector<int> keep(pp.end() - last_take[ci], pp.end());
-                pp = keep;
-                if (!is_no_speech) for (int i = 0; i < result_len; ++i) pp.push_back(tk[i].id);
-            }
-            if (n_tok > 0 && !is_no_speech) {
-                int i0 = 0; int64_t t0 = seek[ci] + 2 * (tk[0].tid - m->tok_beg); std::string text;
-                auto push = [&](int64_t a, int64_t b, int from, int to) {
-                    skw_segment sg{}; sg.t0 = a; sg.t1 = b; sg.tok_begin = (int)A.tok.size();
-                    for (int q = from; q < to; ++q) { skw_token o{tk[q].id, tk[q].tid, tk[q].p, tk[q].plog, tk[q].pt, tk[q].ptsum, tk[q].margin}; A.tok.push_back(o); }
-                    sg.tok_end = (int)A.tok.size(); sg.text_off = (int)A.text.size(); sg.text_len = (int)text.size(); A.text += text; A.seg.push_back(sg);
-                };
-                for (int i = 0; i < n_tok; ++i) {
-                    if (tk[i].id < m->tok_eot) text += m->tok_str[tk[i].id];
-                    if (tk[i].id > m->tok_beg && !p->single_segment) {
-                        const int64_t t1 = seek[ci] + 2 * (tk[i].tid - m->tok_beg);
-                        if (!text.empty()) push(t0, t1, i0, i + 1);
-                        text.clear();
-                        while (i < n_tok && tk[i].id > m->tok_beg) i++;
-                        i--; t0 = t1; i0 = i + 1;
-                    }
-                }
-                if (!text.empty()) push(t0, seek[ci] + seek_delta, i0, n_tok);
-            }
-            const bool single_timestamp_ending = n_tok > 1 && tk[n_tok - 2].id < m->tok_beg && tk[n_tok - 1].id > m->tok_beg;
-            if (single_timestamp_ending) seek_delta = std::min(n_len_org[ci] - seek[ci], WHISPER_CHUNK_SIZE * 100);
-            seek[ci] += seek_delta;
+            lo = hi; jlo = jhi;
         }
     }
+    HIPCHK(hipMemcpyAsync(c->st, c->h_st, sizeof(SkwSeqState) * Bw, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+// row groups: G contiguous ranges of the window batch, each on its own stream (one group while profiling, so kernel times do not overlap)
+// Default: ONE row group in both precisions.  Rounds 3-4 shipped two groups for f16_mfma at >= 64 rows (+1.3 % on the step in a same-box A/B, profiles/r04g).  Round 5's in-kernel
+// launch clock (skw_ctx_kernel_clock) showed what that bought and cost: the groups' cross-attention launches overlap for 27 % of their time and stretch each other from 28 to
+// 35-37 us, a profiler serialises the two streams (its per-kernel averages then describe launches that never ran: decode 129 -> 197 ms under rocprofv3), and the dispatch
+// front end is a serial resource — two chains of small kernels on two streams gain ~20 % over one (tools/probe/probe_stream_overlap.hip) while the launch count doubles.
+// Same-box, round 5 (profiles/r05d): 167.13 ms (two groups) vs 167.59 ms (one) per 64-clip step — inside the +-1.5 % two builds differ by — with the dominant kernel at
+// 0.47 of HBM peak per launch (0.66 while any launch is in flight) against 0.77 as one group.  One group: clock, HIP events and rocprofv3 agree on every launch within 2 %.
+// The exact precision loses 3 % with two groups, smaller batches more (16-row launches).  SKW_DECODE_GROUPS=n overrides.
+// Groups are cut at multiples of 16 rows: the f16_mfma step keeps its attention / FC1 outputs as fragment-order images (skw_afrag_off), which
+// scatter a group's rows over whole 16-row tiles of its scratch — two groups sharing a tile would overwrite each other.
+static RowGroups cut_row_groups(const skw_ctx* c, int Bw) {
+    RowGroups rg; const int n_groups = c->n_groups > 0 ? c->n_groups : 1;
+    const int Gw = std::max(1, std::min(n_groups, Bw / 8));
+    int prev = 0;
+    for (int g = 1; g <= Gw; ++g) {
+        const int cut = g == Gw ? Bw : std::min(Bw, (int)(((long)Bw * g / Gw + 8) & ~15L));
+        if (cut > prev) { rg.r0[rg.G] = prev; rg.n[rg.G] = cut - prev; rg.live[rg.G] = true; ++rg.G; prev = cut; }
+    }
+    return rg;
+}
+
+// one group's sampler launch (eager steps: profiling, tracing, or no graph)
+static void sample_group(skw_ctx* c, const FullRequest& rq, const SkwLogitParams& lp, const RowGroups& rg, int g) {
+    const int NV = c->m->hp.n_vocab, r0 = rg.r0[g], n = rg.n[g]; const bool tracing = rq.tracing();
+    c->cur = c->gstream[g];
+    { ProfScope p_(c, PC_DEC_SAMPLE, 0, 4.0 * n * NV);
+      if (rq.mixed()) skw_dec_sample_rows(c->logits + (size_t)r0 * NV, c->static_mask_pair, lp, c->row_rules + r0, c->st + r0,
+        c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->d_row_live + r0, c->probs + (size_t)r0 * skw_probs_row_floats(NV), c->rng,
+        c->clip_idx + r0, c->prompt_buf + (size_t)r0 * SKW_PROMPT_CAP, c->gstream[g]);
+      else skw_dec_sample(c->logits + (size_t)r0 * NV, c->static_mask, lp, c->st + r0,
+        c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->d_row_live + r0, c->probs + (size_t)r0 * skw_probs_row_floats(NV), c->rng,
+        c->clip_idx + r0, c->prompt_buf + (size_t)r0 * SKW_PROMPT_CAP, c->gstream[g],
+        tracing ? c->forced_dev + (size_t)r0 * c->max_tok : nullptr, tracing ? c->trace_dev + (size_t)r0 * c->max_tok : nullptr); }
+    c->cur = c->stream;
+}
+
+// every step = decoder step (token and position from the device state) + k_dec_sample, which feeds the next prompt token
+// while a row is still inside its prompt and samples afterwards; rows have prompts of different lengths
+static int step_loop(skw_ctx* c, const FullRequest& rq, CallState& cs, const WindowBatch& w) {
+    char* errbuf = c->errbuf; const int Bw = w.Bw; const SkwLogitParams& lp = cs.lp;
+    const bool profiling = c->prof && c->prof->on, tracing = rq.tracing();
+    // (f16_mfma, one group: eager launches 8 steps ahead measure the same 179 ms; the graph leaves the host idle, which matters with eight ranks on one node)
+    const bool use_graphs = c->use_graphs >= 0 ? c->use_graphs != 0 : true;
+    RowGroups rg = cut_row_groups(c, Bw); const int G = rg.G;
+    cs.used_groups = G; cs.used_group_rows = rg.n[0];
+    for (int j = 0; j < Bw; ++j) c->h_row_live[j] = 1;      // (every kernel of the previous window has drained: c->stream was synchronised at its end)
     HIPCHK(hipEventRecord(c->ev[5], c->stream));
-    if (rng_state) for (int i = 0; i < n_clips; ++i) if (rng_state[i])
-        HIPCHK(hipMemcpyAsync(rng_state[i], c->rng + (size_t)i * SKW_RNG_WORDS, sizeof(uint32_t) * SKW_RNG_WORDS, hipMemcpyDeviceToHost, c->stream));
+    for (int g = 0; g < G; ++g) HIPCHK(hipStreamWaitEvent(c->gstream[g], c->ev[5], 0));
+    hipGraphExec_t gexec[skw_ctx::MAX_GROUPS] = {};
+    if (use_graphs && !profiling && !tracing) for (int g = 0; g < G; ++g) gexec[g] = step_graph(c, g, rg.r0[g], rg.n[g], lp, rq.mixed());   // nullptr -> eager launches
+    // The host learns whether a group still has live rows only by waiting for its stream, and a wait + relaunch per step leaves the
+    // GPU idle for the turnaround.  So steps are enqueued `ahead` at a time and the count is read once per block: a step that
+    // runs after the last row of its group has finished changes nothing (its attention and sampling kernels return at once for
+    // finished rows; what the GEMMs write for them is scratch), it only costs its launches.
+    const int step_cap = SKW_PROMPT_CAP + lp.n_max + 2;
+    const int ahead = profiling ? 1 : 8;
+    for (int i = 0; i < step_cap; i += ahead) {
+        const int nstep = std::min(ahead, step_cap - i);
+        for (int k = 0; k < nstep; ++k)
+            for (int g = 0; g < G; ++g) if (rg.live[g]) {
+                if (gexec[g]) HIPCHK(hipGraphLaunch(gexec[g], c->gstream[g]));
+                else {
+                    // (ahead == 1: the previous step has drained)
+                    if (profiling) { int lv = 0; for (int j = rg.r0[g]; j < rg.r0[g] + rg.n[g]; ++j) lv += ((volatile int*)c->h_row_live)[j] != 0; c->live_rows_hint = lv; }
+                    c->cur_group = g;
+                    run_decoder_step(c, rg.r0[g], rg.n[g], i + k, true, c->gstream[g]); c->live_rows_hint = -1; c->cur_group = 0; sample_group(c, rq, lp, rg, g);
+                }
+            }
+        bool any = false;
+        for (int g = 0; g < G; ++g) if (rg.live[g]) { HIPCHK(hipStreamSynchronize(c->gstream[g]));
+            int live = 0; for (int j = rg.r0[g]; j < rg.r0[g] + rg.n[g]; ++j) live += ((volatile int*)c->h_row_live)[j] != 0;
+            if (live <= 0) rg.live[g] = false; else any = true; }
+        if (!any) break;
+    }
+    for (int g = 0; g < G; ++g) { HIPCHK(hipEventRecord(c->gev[g], c->gstream[g])); HIPCHK(hipStreamWaitEvent(c->stream, c->gev[g], 0)); }
+    return 0;
+}
+
+// The rows' state and tokens come back and the stream drains (the batch's host vectors may go after this); then per row the pass's verdict — this window again at the next
+// temperature, or its output and the advance of seek (whisper_full_with_state's tail, skw_window_rules.h)
+static int collect_window(skw_ctx* c, const FullRequest& rq, CallState& cs, const WindowBatch& w) {
+    char* errbuf = c->errbuf; const skw_model* m = c->m; const int Bw = w.Bw; const std::vector<int>& act = w.act;
+    HIPCHK(hipMemcpyAsync(c->h_st, c->st, sizeof(SkwSeqState) * Bw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_toks, c->toks, sizeof(SkwTokenOut) * Bw * c->max_tok, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->ev[4], c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (rq.tracing()) {
+        std::vector<SkwTraceStep> tb((size_t)Bw * c->max_tok);
+        HIPCHK(hipMemcpy(tb.data(), c->trace_dev, sizeof(SkwTraceStep) * tb.size(), hipMemcpyDeviceToHost));
+        for (int j = 0; j < Bw; ++j) {
+            const int ci = act[j], n = std::min(c->h_st[j].n_tokens, c->max_tok);
+            if (rq.forced_ids && rq.forced_ids[ci] && cs.f_cursor[ci] + n > rq.n_forced[ci]) { snprintf(errbuf, 512,
+                "clip %d: forced token sequence exhausted (%d given, decision %d reached): the runs' control flow diverged", ci, rq.n_forced[ci], cs.f_cursor[ci] + n);
+            return -4; }
+            (*rq.traces)[ci].insert((*rq.traces)[ci].end(), tb.begin() + (size_t)j * c->max_tok, tb.begin() + (size_t)j * c->max_tok + n);
+            cs.f_cursor[ci] += n;
+        }
+    }
+    { float a = 0, b = 0; hipEventElapsedTime(&a, c->ev[2], c->ev[3]); hipEventElapsedTime(&b, c->ev[3], c->ev[4]); cs.enc_ms += a; cs.dec_ms += b; }
+    cs.tot_windows += Bw;
+    // decoder passes until the last row finished (the prompt pass counts as one); row-steps: (row, token) pairs that streamed cross K / V, prompt tokens included
+    { int mx = 0; for (int j = 0; j < Bw; ++j) { const int rs = c->h_st[j].n_prompt - 1 + c->h_st[j].n_tokens;
+    mx = std::max(mx, c->prompt_pass_on ? c->h_st[j].n_tokens : rs); cs.tot_row_steps += rs; } cs.tot_steps += mx + w.prefill_passes; }
+    for (int j = 0; j < Bw; ++j) {
+        const int ci = act[j]; const SkwSeqState& s = c->h_st[j]; const SkwTokenOut* tk = c->h_toks + (size_t)j * c->max_tok; skw_result& res = rq.results[ci];
+        const skw_full_params& q = rq.P(ci);      // the clip's own request
+        if (cs.tidx[ci] == 0) res.n_windows++;
+        res.n_decode_steps += 1 + std::max(0, s.n_tokens - 1);     // the prompt is one decode call in whisper.cpp, then one per sampled token but the last
+        const SkwVerdict v = skw_pass_verdict(s, tk, q.entropy_thold, q.logprob_thold, q.no_speech_thold);
+        if (s.min_margin < res.min_margin) res.min_margin = s.min_margin;
+        if (v.fallback) {
+            res.fallback_requested++;
+            // this window again, at the next temperature, on the cross K/V it already has (slot j)
+            if (cs.tidx[ci] + 1 < (int)cs.temps[ci].size()) { cs.tidx[ci]++; cs.retry_slot[ci] = j; continue; }
+        }
+        cs.tidx[ci] = 0;
+        skw_prompt_past_update(cs.prompt_past[ci], cs.last_take[ci], tk, s.result_len, v.no_speech);
+        cs.seek[ci] += skw_window_output(tk, v.n_tok, cs.seek[ci], s.seek_delta, cs.n_len_org[ci], m->tok_beg, m->tok_eot, q.single_segment, v.no_speech, m->tok_str.data(),
+                                         cs.acc[ci]);
+    }
+    return 0;
+}
+
+// generator states and contexts go back to their owners, the clips' accumulators become the results, the call's timing
+static int finish_call(skw_ctx* c, const FullRequest& rq, CallState& cs) {
+    char* errbuf = c->errbuf; const int n_clips = rq.n_clips; int tot_tokens = 0;
+    HIPCHK(hipEventRecord(c->ev[5], c->stream));
+    if (rq.rng_state) for (int i = 0; i < n_clips; ++i) if (rq.rng_state[i])
+        HIPCHK(hipMemcpyAsync(rq.rng_state[i], c->rng + (size_t)i * SKW_RNG_WORDS, sizeof(uint32_t) * SKW_RNG_WORDS, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipGetLastError());          // a launch that failed (bad configuration, lost device) must not look like a transcript
-    // prompt_past as the call leaves it goes back to its owner (the newest SKW_CONTEXT_WORDS - 1 tokens: kept prompt + one window is below that for every n_text_ctx <= 512)
-    if (context) for (int i = 0; i < n_clips; ++i) if (context[i]) {
-        const std::vector<int>& pp = prompt_past[i]; const int n = std::min((int)pp.size(), SKW_CONTEXT_WORDS - 1);
-        context[i][0] = n; for (int k = 0; k < n; ++k) context[i][1 + k] = pp[pp.size() - n + k];
-    }
+    if (rq.context) for (int i = 0; i < n_clips; ++i) if (rq.context[i]) skw_context_write(cs.prompt_past[i], SKW_CONTEXT_WORDS - 1, rq.context[i]);
     for (int i = 0; i < n_clips; ++i) {
-        skw_result& R = results[i]; SeqAcc& A = acc[i];
-        R.n_segments = (int)A.seg.size(); R.n_tokens = (int)A.tok.size(); R.text_len = (int)A.text.size();
-        R.segments = (skw_segment*)malloc(sizeof(skw_segment) * std::max<size_t>(1, A.seg.size())); memcpy(R.segments, A.seg.data(), sizeof(skw_segment) * A.seg.size());
-        R.tokens = (skw_token*)malloc(sizeof(skw_token) * std::max<size_t>(1, A.tok.size())); memcpy(R.tokens, A.tok.data(), sizeof(skw_token) * A.tok.size());
-        R.text = (char*)malloc(A.text.size() + 1); memcpy(R.text, A.text.data(), A.text.size()); R.text[A.text.size()] = 0;
-        tot_tokens += R.n_tokens;
+        skw_result& res = rq.results[i]; SeqAcc& A = cs.acc[i];
+        res.n_segments = (int)A.seg.size(); res.n_tokens = (int)A.tok.size(); res.text_len = (int)A.text.size();
+        res.segments = (skw_segment*)malloc(sizeof(skw_segment) * std::max<size_t>(1, A.seg.size())); memcpy(res.segments, A.seg.data(), sizeof(skw_segment) * A.seg.size());
+        res.tokens = (skw_token*)malloc(sizeof(skw_token) * std::max<size_t>(1, A.tok.size())); memcpy(res.tokens, A.tok.data(), sizeof(skw_token) * A.tok.size());
+        res.text = (char*)malloc(A.text.size() + 1); memcpy(res.text, A.text.data(), A.text.size()); res.text[A.text.size()] = 0;
+        tot_tokens += res.n_tokens;
     }
     prof_collect(c);
     { float a = 0, t = 0; hipEventElapsedTime(&a, c->ev[0], c->ev[1]); hipEventElapsedTime(&t, c->ev[0], c->ev[5]);
-      c->timing.mel_ms = a; c->timing.encode_ms = enc_ms; c->timing.decode_ms = dec_ms;
-      c->timing.total_ms = t; c->timing.n_windows = tot_windows; c->timing.n_decode_steps = tot_steps;
-      c->timing.n_tokens = tot_tokens; c->timing.n_row_steps = (int32_t)tot_row_steps; c->timing.decode_groups = used_groups; c->timing.decode_group_rows = used_group_rows; }
+      c->timing.mel_ms = a; c->timing.encode_ms = cs.enc_ms; c->timing.decode_ms = cs.dec_ms;
+      c->timing.total_ms = t; c->timing.n_windows = cs.tot_windows; c->timing.n_decode_steps = cs.tot_steps;
+      c->timing.n_tokens = tot_tokens; c->timing.n_row_steps = (int32_t)cs.tot_row_steps; c->timing.decode_groups = cs.used_groups; c->timing.decode_group_rows = cs.used_group_rows; }
     return 0;
 }
+
+static int full_batch_impl(skw_ctx* c, const FullRequest& rq) {
+    char* errbuf = c->errbuf; errbuf[0] = 0;
+    WS_READY(c);
+    if (int rc = validate_request(c, rq)) return rc;
+    HIPCHK(hipSetDevice(c->m->device));
+    if (rq.tracing() && ensure_trace_buffers(c)) return -1;
+    CallState cs(rq.n_clips);
+    if (int rc = load_call(c, rq, cs)) return rc;
+    if (int rc = detect_languages(c, rq, cs)) return rc;
+    cs.lp = rq.mixed() ? mixed_logit_params(c->m) : make_logit_params(c->m, rq.p);
+    while (true) {
+        WindowBatch w;      // (alive until collect_window has synchronised the stream)
+        if (!plan_window(rq, cs, w)) break;
+        if (int rc = stage_window(c, rq, cs, w)) return rc;
+        if (int rc = prompt_pass(c, w)) return rc;
+        if (int rc = step_loop(c, rq, cs, w)) return rc;
+        if (int rc = collect_window(c, rq, cs, w)) return rc;
+    }
+    return finish_call(c, rq, cs);
+}
+
+// the entry points' guard: nothing may unwind across the C ABI
+template <typename F> static int guarded(skw_ctx* c, const char* entry, F&& body) {
+    try { return body(); }
+    catch (const std::exception& e) { snprintf(c->errbuf, 512, "%s: %s", entry, e.what()); return -5; }
+}
+static FullRequest make_request(const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device, skw_result* results) {
+    FullRequest rq; rq.p = p; rq.pcm = pcm; rq.n_samples = n_samples; rq.n_clips = n_clips; rq.pcm_on_device = pcm_on_device; rq.results = results;
+    return rq;
+}
 extern "C" int skw_full_batch(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device, skw_result* results) {
-    try { return full_batch_impl(c, p, pcm, n_samples, n_clips, pcm_on_device, results, nullptr, nullptr, nullptr); }
-    catch (const std::exception& e) { snprintf(c->errbuf, 512, "skw_full_batch: %s", e.what()); return -5; }      // nothing may unwind across the C ABI
+    return guarded(c, "skw_full_batch", [&] { return full_batch_impl(c, make_request(p, pcm, n_samples, n_clips, pcm_on_device, results)); });
 }
 extern "C" void skw_rng_state_init(uint32_t* state) {      // std::mt19937(0), as whisper_init_state leaves decoder 0's generator
     state[0] = 0u; for (int i = 1; i < 624; ++i) state[i] = 1812433253u * (state[i - 1] ^ (state[i - 1] >> 30)) + (uint32_t)i;
@@ -1610,38 +1648,39 @@ extern "C" void skw_rng_state_init(uint32_t* state) {      // std::mt19937(0), a
 }
 extern "C" int skw_full_batch_rng(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                   uint32_t* const* rng_state, skw_result* results) {
-    try { return full_batch_impl(c, p, pcm, n_samples, n_clips, pcm_on_device, results, nullptr, nullptr, nullptr, rng_state); }
-    catch (const std::exception& e) { snprintf(c->errbuf, 512, "skw_full_batch_rng: %s", e.what()); return -5; }
+    return guarded(c, "skw_full_batch_rng", [&] {
+        FullRequest rq = make_request(p, pcm, n_samples, n_clips, pcm_on_device, results); rq.rng_state = rng_state;
+        return full_batch_impl(c, rq); });
 }
 extern "C" int skw_full_batch_mixed(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                     uint32_t* const* rng_state, skw_result* results) {
-    try {
+    return guarded(c, "skw_full_batch_mixed", [&] {
         if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_mixed: params is NULL (one skw_full_params per clip)"); return -1; }
-        return full_batch_impl(c, params, pcm, n_samples, n_clips, pcm_on_device, results, nullptr, nullptr, nullptr, rng_state, params);
-    } catch (const std::exception& e) { snprintf(c->errbuf, 512, "skw_full_batch_mixed: %s", e.what()); return -5; }
+        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state;
+        return full_batch_impl(c, rq); });
 }
 extern "C" int skw_full_batch_context(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                       uint32_t* const* rng_state, int32_t* const* context, skw_result* results) {
-    try {
+    return guarded(c, "skw_full_batch_context", [&] {
         if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_context: params is NULL (one skw_full_params per clip)"); return -1; }
-        return full_batch_impl(c, params, pcm, n_samples, n_clips, pcm_on_device, results, nullptr, nullptr, nullptr, rng_state, params, context);
-    } catch (const std::exception& e) { snprintf(c->errbuf, 512, "skw_full_batch_context: %s", e.what()); return -5; }
+        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state; rq.context = context;
+        return full_batch_impl(c, rq); });
 }
 extern "C" int skw_full_batch_traced_context(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                              const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, int32_t* const* context, skw_result* results) {
     static_assert(sizeof(skw_trace_step) == sizeof(SkwTraceStep), "skw_trace_step is SkwTraceStep");
-    try {
+    return guarded(c, "skw_full_batch_traced", [&] {      // (both traced entry points report under this name)
         if (!traces || (forced_ids && !n_forced)) { snprintf(c->errbuf, 512, "skw_full_batch_traced: bad arguments"); return -1; }
         for (int i = 0; i < n_clips; ++i) { traces[i].n = 0; traces[i].steps = nullptr; }
         std::vector<std::vector<SkwTraceStep>> tr(std::max(0, n_clips));
-        const int rc = full_batch_impl(c, p, pcm, n_samples, n_clips, pcm_on_device, results, forced_ids, n_forced, &tr, nullptr, nullptr, context);
+        FullRequest rq = make_request(p, pcm, n_samples, n_clips, pcm_on_device, results); rq.forced_ids = forced_ids; rq.n_forced = n_forced; rq.traces = &tr; rq.context = context;
+        const int rc = full_batch_impl(c, rq);
         if (rc) return rc;
         for (int i = 0; i < n_clips; ++i) {
             traces[i].n = (int32_t)tr[i].size(); traces[i].steps = (skw_trace_step*)malloc(sizeof(skw_trace_step) * std::max<size_t>(1, tr[i].size()));
             memcpy(traces[i].steps, tr[i].data(), sizeof(skw_trace_step) * tr[i].size());
         }
-        return 0;
-    } catch (const std::exception& e) { snprintf(c->errbuf, 512, "skw_full_batch_traced: %s", e.what()); return -5; }
+        return 0; });
 }
 extern "C" int skw_full_batch_traced(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                      const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, skw_result* results) {
@@ -1661,12 +1700,7 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
     const skw_model* m = c->m; const int NV = m->hp.n_vocab, MT = c->max_tok;
     for (int r = 0; r < n_rows; ++r) if (n_hist[r] < 0 || n_hist[r] >= MT || n_hist[r] > hist_stride) { snprintf(errbuf, 512, "row %d: history of %d tokens (at most %d)", r, n_hist[r], MT - 1);
     return -1; }
-    if (!c->trace_dev) {
-        int* f = nullptr; SkwTraceStep* t = nullptr;
-        if (hipMalloc((void**)&f, sizeof(int) * (size_t)c->max_batch * MT) != hipSuccess || hipMalloc((void**)&t, sizeof(SkwTraceStep) * (size_t)c->max_batch * MT) != hipSuccess) {
-            hipFree(f); snprintf(errbuf, 512, "trace buffers: device allocation failed"); return -1; }
-        c->forced_dev = f; c->trace_dev = t;
-    }
+    if (ensure_trace_buffers(c)) return -1;
     SkwLogitParams lp; std::vector<SkwRowRules> rules;
     if (pv) {
         build_static_mask_pair(c); lp = mixed_logit_params(m);
@@ -1678,17 +1712,17 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
     std::vector<int> forced((size_t)n_rows * MT, -1), zero(n_rows, 0);
     for (int r = 0; r < n_rows; ++r) {
         SkwSeqState& s = c->h_st[r]; memset(&s, 0, sizeof s);
-        s.active = 1; s.seek_delta = 100 * WHISPER_CHUNK_SIZE; s.seek = 0; s.seek_end = 100 * WHISPER_CHUNK_SIZE; s.n_prompt = 1; s.min_margin = INFINITY;
+        s.active = 1; s.seek_delta = SKW_WINDOW_FRAMES; s.seek = 0; s.n_prompt = 1; s.min_margin = INFINITY;
         s.cur_pos = n_hist[r]; s.n_tokens = n_hist[r];
+        // the history's timestamps through the token loop's update (as the parent of this hook, oracle/skwo_debug_process_logits, replays them): how has_ts / seek_delta /
+        // result_len follow them, and the one failure a history can show.  No stop rule can fire: no budget, no loop bound, the audio without end, and <|endoftext|> is no timestamp
+        s.seek_end = INT32_MAX;
         for (int i = 0; i < n_hist[r]; ++i) {
             const int id = hist[(size_t)r * hist_stride + i]; toks[(size_t)r * MT + i].id = id;
-            if (id > m->tok_beg) {
-                const int sd = 2 * (id - m->tok_beg);
-                if (s.has_ts && s.seek_delta > sd && s.result_len < i) { snprintf(errbuf, 512, "row %d: the token loop cannot produce this history (timestamp goes backwards at %d)", r, i);
-                return -1; }
-                s.seek_delta = sd; s.result_len = i + 1; s.has_ts = 1;
-            }
+            if (id > m->tok_beg && skw_token_loop_update(s, id, i, m->tok_beg, m->tok_eot, 0, 0, 0, INT32_MAX)) {
+                snprintf(errbuf, 512, "row %d: the token loop cannot produce this history (timestamp goes backwards at %d)", r, i); return -1; }
         }
+        s.seek_end = SKW_WINDOW_FRAMES;
         c->h_row_live[r] = 1;
     }
     HIPCHK(hipMemcpyAsync(c->st, c->h_st, sizeof(SkwSeqState) * n_rows, hipMemcpyHostToDevice, c->stream));

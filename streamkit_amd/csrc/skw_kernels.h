@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "skw_window_rules.h"
 
 typedef _Float16 half_t;
 
@@ -177,29 +178,8 @@ void skw_dec_cross_attn_vt(const half_t* q, const half_t* ck, const half_t* cvt,
                            //  memory, so a captured step holds no key count; n_ctx and Tpad stay the strides of the buffers
                            const int* nkeys = nullptr);
 
-// per-sequence decoding state kept on the device (whisper_decoder + the bits of whisper_full_with_state's loop that depend on it)
-struct SkwSeqState {
-    int32_t active;        // still decoding
-    int32_t failed, completed;
-    int32_t has_ts, seek_delta, result_len;
-    int32_t n_tokens;      // sampled tokens so far (i)
-    int32_t seek, seek_end;
-    int32_t n_prompt;
-    float no_speech_prob;
-    float min_margin;
-    int32_t cur_token;     // token to feed next
-    int32_t cur_pos;       // its position
-    float temperature;     // 0: argmax; > 0: logits / t, then a std::discrete_distribution draw from the clip's mt19937
-    int32_t pad;
-    int32_t n_keys;        // cross-attention keys of this row (the clip's audio_ctx); 0: the model's n_audio_ctx
-};
-// The prompt pass (skw_engine.hip, prefill): one SkwSeqState per PROMPT TOKEN, so every kernel of the decode step takes it as a row —
-//   active = 1, cur_token / cur_pos = the token and its position, pad = the sequence (window slot) it belongs to, seek = slot * n_text_ctx + position (its K / V cache row).
-// whisper_full_with_state: `const int delta_min = 10` mel frames (100 ms) - shortest input transcribed, the loop's stop rule and the decoder's end-of-audio test
-#define SKW_DELTA_MIN 10
-#define SKW_PROMPT_CAP 240   // [prev] + n_text_ctx/2 past tokens + sot, language, task, notimestamps
+// SkwSeqState (the per-sequence decoding state kept on the device), SkwTokenOut, SKW_DELTA_MIN and SKW_PROMPT_CAP: skw_window_rules.h, with the token loop's update rule
 #define SKW_RNG_WORDS 625   // std::mt19937 state per clip: mt[624] + index
-struct SkwTokenOut { int32_t id, tid; float p, plog, pt, ptsum, margin; };
 // one sampling decision as the trace / teacher-forced mode records it (skw_full_batch_traced): what this precision would have chosen, what it was made to
 // feed instead (forced_id == chosen_id in a free run), the two largest admissible logits with their owners, the (filtered) logit of the fed token and the
 // log-sum-exp of the admissible logits.  Layout == skw_trace_step of include/skw_engine.h.

@@ -8,6 +8,7 @@
 //   k_layernorm        ggml_norm + ggml_mul + ggml_add (K3)
 //   k_attn_encoder     KQ = mul_mat(K,Q); soft_max_ext; mul_mat(V, KQ_soft_max) (K4)
 //   k_dec_*            whisper_decode_internal pieces (K7-K9), whisper_process_logits + greedy (K11)
+#define SKW_WINDOW_RULES_DEVICE_PART      // (skw_window_rules.h without its host rules)
 #include "skw_kernels.h"
 #include <hip/hip_ext.h>
 #include <atomic>
@@ -1713,26 +1714,9 @@ __global__ __launch_bounds__(1024) void k_dec_sample_stream(float* logits_all, c
     if (!sampled && t2 > -INFINITY && t1 - t2 < st->min_margin) st->min_margin = t1 - t2;   // argmax passes only (diagnostic)
     if (i < max_tok) toks[i] = tk;
     st->n_tokens = i + 1;
-    int failed = 0, completed = 0;
-    if (tk.id > p.tok_beg) {
-        const int sd_new = 2 * (tk.id - p.tok_beg);
-        if (st->has_ts && st->seek_delta > sd_new && st->result_len < i) failed = 1;
-        else { st->seek_delta = sd_new; st->result_len = i + 1; st->has_ts = 1; }
-    }
-    if (!failed && (tk.id == p.tok_eot || (p.max_tokens > 0 && i >= p.max_tokens) || (st->has_ts && st->seek + st->seek_delta + SKW_DELTA_MIN >= st->seek_end))) {
-        if (st->result_len == 0 && !p.no_timestamps) {
-            if (st->seek + st->seek_delta + SKW_DELTA_MIN >= st->seek_end) st->result_len = i + 1; else failed = 1;
-        }
-        if (!failed) {
-            if (p.single_segment || p.no_timestamps) { st->result_len = i + 1; st->seek_delta = 100 * 30; }
-            completed = 1;
-        }
-    }
-    if (!failed && !completed && i == p.n_max - 1 && (st->result_len == 0 || st->seek_delta < 100 * 30 / 2)) failed = 1;
-    if (!failed && !completed && i + 1 >= p.n_max) completed = 1;   // loop bound reached (whisper.cpp leaves the for loop)
-    st->failed = failed; st->completed = completed;
+    const int done = skw_token_loop_update(*st, tk.id, i, p.tok_beg, p.tok_eot, p.max_tokens, p.no_timestamps, p.single_segment, p.n_max);
     st->cur_token = tk.id; st->cur_pos = st->n_prompt + i;
-    if (failed || completed) { st->active = 0; n_active[b] = 0; }     // the row's live flag, in host-mapped memory: the host reads it after the stream drains (no copy kernel in the step)
+    if (done) { st->active = 0; n_active[b] = 0; }     // the row's live flag, in host-mapped memory: the host reads it after the stream drains (no copy kernel in the step)
 }
 // Register-resident form: the row's logits (<= 104 per thread) are loaded once, every pass of whisper_process_logits then runs on
 // registers -- the streaming form above re-reads the row from L2 six times with nothing to overlap the latency (90 us per step).
@@ -1975,26 +1959,9 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_sample(float* logits_all, const 
     if (!sampled && t2 > -INFINITY && t1 - t2 < st->min_margin) st->min_margin = t1 - t2;   // argmax passes only (diagnostic)
     if (i < max_tok) toks[i] = tk;
     st->n_tokens = i + 1;
-    int failed = 0, completed = 0;
-    if (tk.id > p.tok_beg) {
-        const int sd_new = 2 * (tk.id - p.tok_beg);
-        if (st->has_ts && st->seek_delta > sd_new && st->result_len < i) failed = 1;
-        else { st->seek_delta = sd_new; st->result_len = i + 1; st->has_ts = 1; }
-    }
-    if (!failed && (tk.id == p.tok_eot || (p.max_tokens > 0 && i >= p.max_tokens) || (st->has_ts && st->seek + st->seek_delta + SKW_DELTA_MIN >= st->seek_end))) {
-        if (st->result_len == 0 && !p.no_timestamps) {
-            if (st->seek + st->seek_delta + SKW_DELTA_MIN >= st->seek_end) st->result_len = i + 1; else failed = 1;
-        }
-        if (!failed) {
-            if (p.single_segment || p.no_timestamps) { st->result_len = i + 1; st->seek_delta = 100 * 30; }
-            completed = 1;
-        }
-    }
-    if (!failed && !completed && i == p.n_max - 1 && (st->result_len == 0 || st->seek_delta < 100 * 30 / 2)) failed = 1;
-    if (!failed && !completed && i + 1 >= p.n_max) completed = 1;   // loop bound reached (whisper.cpp leaves the for loop)
-    st->failed = failed; st->completed = completed;
+    const int done = skw_token_loop_update(*st, tk.id, i, p.tok_beg, p.tok_eot, p.max_tokens, p.no_timestamps, p.single_segment, p.n_max);
     st->cur_token = tk.id; st->cur_pos = st->n_prompt + i;
-    if (failed || completed) { st->active = 0; n_active[b] = 0; }     // the row's live flag, in host-mapped memory: the host reads it after the stream drains (no copy kernel in the step)
+    if (done) { st->active = 0; n_active[b] = 0; }     // the row's live flag, in host-mapped memory: the host reads it after the stream drains (no copy kernel in the step)
 }
 static_assert(SMP_NT == 512, "smp_mask_bytes restates SMP_NT");
 size_t skw_static_mask_bytes(int n_vocab) { return smp_mask_bytes(n_vocab); }
