@@ -490,14 +490,18 @@ static void linear_q8_seg(const float* A, long lda, int rows, const lin_t* L, fl
     free(qa); free(da); free(sa);
 }
 static void linear_q8(const float* A, long lda, int rows, const lin_t* L, float* out, long ldo) { linear_q8_seg(A, lda, rows, L, out, ldo, 1); }
-/* test hook: out [rows][n_out] = ggml's quantised mul_mat of A [rows][n_in] f32 with n_out * n_in / 32 blocks of the given type */
-int skwo_debug_linear_q8(int type, const uint8_t* blocks, int n_out, int n_in, const float* A, int rows, float* out) {
-    const size_t bb = skw_ggml_block_bytes(type); if (!bb || n_in % 32) return -1;
+/* test hooks: out [rows][n_out] = ggml's quantised mul_mat of A [rows][n_in] f32 with n_out * n_in / 32 blocks of the given type; nseg: the block sum as that many contiguous
+ * runs added in ascending order (1: ggml's single sum, 4: the decoder's segmented form; n_in / 32 must divide) */
+int skwo_debug_linear_q8_seg(int type, const uint8_t* blocks, int n_out, int n_in, const float* A, int rows, int nseg, float* out) {
+    const size_t bb = skw_ggml_block_bytes(type); if (!bb || n_in % 32 || nseg < 1 || (n_in / 32) % nseg) return -1;
     lin_t L; memset(&L, 0, sizeof L); L.n_in = n_in; L.n_out = n_out; L.qtype = type; const int nb = n_in / 32;
     L.qw = (int8_t*)malloc((size_t)n_out * n_in); L.qd = xmalloc_f((size_t)n_out * nb); L.qm = xmalloc_f((size_t)n_out * nb);
     for (size_t i = 0; i < (size_t)n_out * nb; ++i) skw_ggml_unpack_block(type, blocks + i * bb, L.qw + i * 32, &L.qd[i], &L.qm[i]);
-    linear_q8(A, n_in, rows, &L, out, n_out);
+    linear_q8_seg(A, n_in, rows, &L, out, n_out, nseg);
     free(L.qw); free(L.qd); free(L.qm); return 0;
+}
+int skwo_debug_linear_q8(int type, const uint8_t* blocks, int n_out, int n_in, const float* A, int rows, float* out) {
+    return skwo_debug_linear_q8_seg(type, blocks, n_out, n_in, A, rows, 1, out);
 }
 static void linear(const float* A, long lda, int rows, const lin_t* L, float* out, long ldo) {
     if (L->qw) linear_q8(A, lda, rows, L, out, ldo);

@@ -97,11 +97,13 @@ static bool is_matmul_weight(const RawT& t) {
     const std::string& n = t.name;
     return t.n_dims == 2 && n.size() > 7 && n.compare(n.size() - 7, 7, ".weight") == 0 && n.find("positional_embedding") == std::string::npos && n.find("ln") == std::string::npos;
 }
-static void host_q(const RawT& w, HostQ* h) {
-    const int K = w.ne[0], n_out = w.ne[1], nb = K / 32; const size_t bb = skw_ggml_block_bytes(w.qtype);
+// blocks: n_out rows of K / 32 blocks of ggml type qtype, as the file holds them
+static void host_q(int qtype, const uint8_t* blocks, int n_out, int K, HostQ* h) {
+    const int nb = K / 32; const size_t bb = skw_ggml_block_bytes(qtype);
     h->n_out = n_out; h->K = K; h->q.resize((size_t)n_out * K); h->d.resize((size_t)n_out * nb); h->m.resize((size_t)n_out * nb);
-    for (size_t i = 0; i < (size_t)n_out * nb; ++i) skw_ggml_unpack_block(w.qtype, w.qblk.data() + i * bb, h->q.data() + i * 32, &h->d[i], &h->m[i]);
+    for (size_t i = 0; i < (size_t)n_out * nb; ++i) skw_ggml_unpack_block(qtype, blocks + i * bb, h->q.data() + i * 32, &h->d[i], &h->m[i]);
 }
+static void host_q(const RawT& w, HostQ* h) { host_q(w.qtype, w.qblk.data(), w.ne[1], w.ne[0], h); }
 // int8 rows as they are; scales and offsets transposed to [block][n_pad] so that a lane's four adjacent features are one 16-byte load
 static bool up_q(skw_model* m, const HostQ& h, int qtype, DevLin* L) {
     const int nb = h.K / 32, n_pad = (h.n_out + 63) & ~63;
@@ -2104,6 +2106,118 @@ extern "C" int skw_debug_attn16(skw_ctx* c, int form, int H, int n_ctx, int n_sl
     cleanup();
     for (int r = 0; r < orows; ++r) for (int n = 0; n < d; ++n)
         out_host[(size_t)r * d + n] = skw_f16_to_f32(o[ofrag ? (size_t)skw_afrag_off(r, skw_kperm(n), d) : (size_t)r * d + skw_kperm(n)]);
+    return 0;
+}
+
+// tests (tests/test_gpu_q8.py): one product of ggml's arithmetic for quantised files on host-supplied operands, through everything the engine itself goes through — the model
+// loader's repack of the file's blocks (host_q / up_q), skw_q8_quantize on the f32 rows A [M][lda], then skw_gemm_q8 (so the dispatch is part of what is tested; *kernel_id is what
+// skw_gemm_q8_kernel — the function the launcher branches on — answers for the launch's arguments).  The output buffers are the caller's: C (c_bytes; ldc elements per row where the
+// epilogue has rows) and, for EPI_DEC_QKV, C2 / C3 (c2_bytes each, ldc2) are uploaded as given — a sentinel pattern with a margin past M and N is the caller's to lay down — and read
+// back after the launch.  res_alias (EPI_F32): the residual is C itself, as the engine calls it, so C's first M x N region holds the residual on entry.  pos (EPI_DEC_QKV): [M], reaches
+// the kernel as the cur_pos fields of a SkwSeqState array.  Every index the epilogue can form is checked against the buffer sizes here, before anything is launched.
+extern "C" int skw_debug_gemm_q8(skw_ctx* c, int type, const uint8_t* blocks_host, int N, int K, const float* A_host, long lda, int M, int segmented, int epi,
+                                 int n_ctx, int H, int Tpad, const float* bias_host, int res_alias, float scale, int has_scale, const int* pos,
+                                 void* C_host, long c_bytes, long ldc, void* C2_host, void* C3_host, long c2_bytes, long ldc2, int* kernel_id) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_gemm_q8: %s", what); return -1; };
+    const int form = skw_ggml_dot_form(type);
+    if (!form || M < 1 || M > 65536 || N < 1 || N > 65536 || K < 32 || K > 8192 || (K & 31) || lda < K || (lda & 3) || !blocks_host || !A_host || !C_host || !kernel_id) return bad("bad geometry");
+    if (segmented && ((K & 127) || M > 4096)) return bad("the segmented form needs K % 128 == 0 and M <= 4096");
+    const long MN_last = (long)(M - 1) * ldc + N;
+    switch (epi) {
+        case EPI_F32: case EPI_GELU_F32: if (ldc < N || MN_last * 4 > c_bytes) return bad("C too small"); break;
+        case EPI_F16_PLAIN: if (ldc < N || MN_last * 2 > c_bytes) return bad("C too small"); break;
+        case EPI_HEADS_F16: case EPI_VT_F16:
+            if (n_ctx < 1 || M % n_ctx || (N & 63) || H != N / 64 || Tpad < n_ctx || (Tpad & 31) || (long)(M / n_ctx) * H * Tpad * 64 * 2 > c_bytes) return bad("heads / V^T geometry");
+            break;
+        case EPI_DEC_QKV:
+            if (N % 3 || n_ctx != N / 3 || !pos || !C2_host || !C3_host || ldc < n_ctx || ((long)(M - 1) * ldc + n_ctx) * 2 > c_bytes) return bad("q|k|v geometry");
+            for (int m = 0; m < M; ++m) if (pos[m] < 0 || ((long)m * ldc2 + (long)(pos[m] + 1) * n_ctx) * 2 > c2_bytes) return bad("a row's cache position lies outside C2 / C3");
+            break;
+        default: return bad("an epilogue skw_gemm_q8 does not take");
+    }
+    if (res_alias && epi != EPI_F32) return bad("res_alias is EPI_F32's");
+    HostQ hq; host_q(type, blocks_host, N, K, &hq);
+    DevLin L; const size_t allocs_before = c->m->allocs.size();
+    const bool up = up_q(c->m, hq, type, &L);
+    const int nb = K / 32;
+    float *dA = nullptr, *dd = nullptr, *ds = nullptr, *dbias = nullptr; int8_t* dq = nullptr; void *dC = nullptr, *dC2 = nullptr, *dC3 = nullptr; SkwSeqState* dst = nullptr;
+    auto cleanup = [&]() {
+        hipFree(dA); hipFree(dd); hipFree(ds); hipFree(dbias); hipFree(dq); hipFree(dC); hipFree(dC2); hipFree(dC3); hipFree(dst);
+        while (c->m->allocs.size() > allocs_before) { hipFree(c->m->allocs.back()); c->m->allocs.pop_back(); }      // the repacked weight is this call's, not the model's
+    };
+    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_gemm_q8: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
+    if (!up) { cleanup(); return bad("device allocation failed for the weight"); }
+    if (!chk(hipMalloc((void**)&dA, (size_t)M * lda * 4)) || !chk(hipMalloc((void**)&dq, (size_t)M * K)) || !chk(hipMalloc((void**)&dd, (size_t)M * nb * 4)) ||
+        !chk(hipMalloc((void**)&ds, (size_t)M * nb * 4)) || !chk(hipMalloc(&dC, (size_t)c_bytes))) return -1;
+    if (!chk(hipMemcpy(dA, A_host, (size_t)M * lda * 4, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dC, C_host, (size_t)c_bytes, hipMemcpyHostToDevice))) return -1;
+    if (bias_host && (!chk(hipMalloc((void**)&dbias, (size_t)N * 4)) || !chk(hipMemcpy(dbias, bias_host, (size_t)N * 4, hipMemcpyHostToDevice)))) return -1;
+    SkwGemmArgs a{}; a.M = M; a.N = N; a.K = K; a.C = dC; a.ldc = ldc; a.epi = epi; a.scale = scale; a.has_scale = has_scale; a.bias = dbias; a.n_ctx = n_ctx; a.H = H; a.Tpad = Tpad;
+    a.gelu_tab = c->m->gelu_tab;
+    if (res_alias) { a.res = (const float*)dC; a.ldres = ldc; }
+    if (epi == EPI_DEC_QKV) {
+        std::vector<SkwSeqState> st(M); memset((void*)st.data(), 0, sizeof(SkwSeqState) * M);
+        for (int m = 0; m < M; ++m) { st[m].active = 1; st[m].cur_pos = pos[m]; }
+        if (!chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * M)) || !chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * M, hipMemcpyHostToDevice))) return -1;
+        if (!chk(hipMalloc(&dC2, (size_t)c2_bytes)) || !chk(hipMalloc(&dC3, (size_t)c2_bytes))) return -1;
+        if (!chk(hipMemcpy(dC2, C2_host, (size_t)c2_bytes, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dC3, C3_host, (size_t)c2_bytes, hipMemcpyHostToDevice))) return -1;
+        a.C2 = dC2; a.C3 = dC3; a.ldc2 = ldc2; a.pos_ptr = &dst[0].cur_pos; a.pos_stride = (int)(sizeof(SkwSeqState) / sizeof(int));
+    }
+    skw_q8_quantize(dA, lda, M, K, dq, dd, ds, c->stream);
+    SkwQ8Args qa{dq, dd, ds, L.qw, L.dwT, L.mwT, L.n_pad, L.qform, segmented ? 1 : 0};
+    *kernel_id = skw_gemm_q8_kernel(a, qa);
+    if (!skw_gemm_q8(a, qa, c->stream)) { cleanup(); return bad("skw_gemm_q8 refused the arguments"); }
+    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(C_host, dC, (size_t)c_bytes, hipMemcpyDeviceToHost))) return -1;
+    if (epi == EPI_DEC_QKV && (!chk(hipMemcpy(C2_host, dC2, (size_t)c2_bytes, hipMemcpyDeviceToHost)) || !chk(hipMemcpy(C3_host, dC3, (size_t)c2_bytes, hipMemcpyDeviceToHost)))) return -1;
+    cleanup();
+    return 0;
+}
+// tests: k_q8_quantize on host rows x [M][ldx] (ldx >= K, a multiple of 4): q int8 [M][K], dT / sT f32 [K/32][M]
+extern "C" int skw_debug_q8_quantize(skw_ctx* c, const float* x_host, long ldx, int M, int K, int8_t* q, float* dT, float* sT) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    if (M < 1 || M > 65536 || K < 32 || K > 8192 || (K & 31) || ldx < K || (ldx & 3) || !x_host || !q || !dT || !sT) { snprintf(errbuf, 512, "skw_debug_q8_quantize: bad geometry"); return -1; }
+    const int nb = K / 32; float *dx = nullptr, *dd = nullptr, *ds = nullptr; int8_t* dq = nullptr;
+    auto cleanup = [&]() { hipFree(dx); hipFree(dd); hipFree(ds); hipFree(dq); };
+    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_q8_quantize: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
+    if (!chk(hipMalloc((void**)&dx, (size_t)M * ldx * 4)) || !chk(hipMalloc((void**)&dq, (size_t)M * K))) return -1;
+    if (!chk(hipMalloc((void**)&dd, (size_t)M * nb * 4)) || !chk(hipMalloc((void**)&ds, (size_t)M * nb * 4))) return -1;
+    if (!chk(hipMemcpy(dx, x_host, (size_t)M * ldx * 4, hipMemcpyHostToDevice))) return -1;
+    skw_q8_quantize(dx, ldx, M, K, dq, dd, ds, c->stream);
+    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError())) return -1;
+    if (!chk(hipMemcpy(q, dq, (size_t)M * K, hipMemcpyDeviceToHost)) || !chk(hipMemcpy(dT, dd, (size_t)M * nb * 4, hipMemcpyDeviceToHost))) return -1;
+    if (!chk(hipMemcpy(sT, ds, (size_t)M * nb * 4, hipMemcpyDeviceToHost))) return -1;
+    cleanup();
+    return 0;
+}
+// tests: the decoder's self attention (the exact form of k_dec_attn) twice on the same operands — once with f32_out = 1 (out_f32 [rows][H*64]), once leaving its rows as q8 blocks
+// (SkwQ8Out: q int8 [rows][H*64], dT / sT f32 [H*2][rows]) — so that the in-kernel quantiser can be held to quantize_rows of the first launch's rows.  Q [rows][H*64], K / V
+// [rows][n_text_ctx][H*64] f16 bit patterns (row b reads the cache of sequence seq[b], or b); pos / active / seq: [rows] (the last two may be null), reaching the kernel as fields of a
+// SkwSeqState array.  All four output buffers are uploaded as the caller filled them (a sentinel), so what an inactive row leaves is visible.
+extern "C" int skw_debug_self_attn_q8(skw_ctx* c, int H, int n_text_ctx, int rows, const uint16_t* Q_host, const uint16_t* K_host, const uint16_t* V_host, const int* pos, const int* active,
+                                      const int* seq, float* out_f32, int8_t* q, float* dT, float* sT) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_self_attn_q8: %s", what); return -1; };
+    if (H < 1 || H > 32 || n_text_ctx < 1 || n_text_ctx > 7 * 64 || rows < 1 || rows > 4096 || !Q_host || !K_host || !V_host || !pos || !out_f32 || !q || !dT || !sT) return bad("bad geometry");
+    for (int b = 0; b < rows; ++b) if (pos[b] < 0 || pos[b] >= n_text_ctx || (seq && (seq[b] < 0 || seq[b] >= rows))) return bad("pos or seq outside the caches");
+    const int d = H * 64; const size_t nQ = (size_t)rows * d, nKV = (size_t)rows * n_text_ctx * d, nS = (size_t)2 * H * rows;
+    std::vector<SkwSeqState> st(rows); memset((void*)st.data(), 0, sizeof(SkwSeqState) * rows);
+    for (int b = 0; b < rows; ++b) { st[b].active = active ? active[b] : 1; st[b].pad = seq ? seq[b] : b; st[b].cur_pos = pos[b]; }
+    half_t *dq16 = nullptr, *dk = nullptr, *dv = nullptr; float *dout = nullptr, *dd = nullptr, *ds = nullptr; int8_t* dq8 = nullptr; SkwSeqState* dst = nullptr;
+    auto cleanup = [&]() { hipFree(dq16); hipFree(dk); hipFree(dv); hipFree(dout); hipFree(dd); hipFree(ds); hipFree(dq8); hipFree(dst); };
+    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_self_attn_q8: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
+    if (!chk(hipMalloc((void**)&dq16, nQ * 2)) || !chk(hipMalloc((void**)&dk, nKV * 2)) || !chk(hipMalloc((void**)&dv, nKV * 2)) || !chk(hipMalloc((void**)&dout, nQ * 4))) return -1;
+    if (!chk(hipMalloc((void**)&dq8, nQ)) || !chk(hipMalloc((void**)&dd, nS * 4)) || !chk(hipMalloc((void**)&ds, nS * 4)) || !chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * rows))) return -1;
+    if (!chk(hipMemcpy(dq16, Q_host, nQ * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dk, K_host, nKV * 2, hipMemcpyHostToDevice))) return -1;
+    if (!chk(hipMemcpy(dv, V_host, nKV * 2, hipMemcpyHostToDevice))) return -1;
+    if (!chk(hipMemcpy(dout, out_f32, nQ * 4, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dq8, q, nQ, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dd, dT, nS * 4, hipMemcpyHostToDevice))) return -1;
+    if (!chk(hipMemcpy(ds, sT, nS * 4, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * rows, hipMemcpyHostToDevice))) return -1;
+    const int* act = active ? &dst[0].active : nullptr; const int* sq = seq ? &dst[0].pad : nullptr;
+    skw_dec_self_attn(dq16, dk, dv, &dst[0].cur_pos, rows, H, d, n_text_ctx, (half_t*)dout, act, c->stream, 1, SkwQ8Out{nullptr, nullptr, nullptr, 0}, sq);
+    skw_dec_self_attn(dq16, dk, dv, &dst[0].cur_pos, rows, H, d, n_text_ctx, nullptr, act, c->stream, 0, SkwQ8Out{dq8, dd, ds, rows}, sq);
+    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError())) return -1;
+    if (!chk(hipMemcpy(out_f32, dout, nQ * 4, hipMemcpyDeviceToHost)) || !chk(hipMemcpy(q, dq8, nQ, hipMemcpyDeviceToHost)) || !chk(hipMemcpy(dT, dd, nS * 4, hipMemcpyDeviceToHost)) ||
+        !chk(hipMemcpy(sT, ds, nS * 4, hipMemcpyDeviceToHost))) return -1;
+    cleanup();
     return 0;
 }
 

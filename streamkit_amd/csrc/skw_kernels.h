@@ -136,6 +136,9 @@ struct SkwQ8Args { const int8_t* qa; const float* dyT; const float* syT;        
                    int segmented; };
 void skw_q8_quantize(const float* x, long ldx, int M, int K, int8_t* q, float* dT, float* sT, hipStream_t s);
 bool skw_gemm_q8(const SkwGemmArgs& a, const SkwQ8Args& qa, hipStream_t s);
+// the kernel skw_gemm_q8 launches for these arguments: k_gemm_q8_small<UB 6 | 8> (segmented), k_gemm_q8<TW 2 | 4>, k_gemm_q8_lds
+enum SkwQ8Kernel : int { SKW_Q8K_SMALL6 = 0, SKW_Q8K_SMALL8, SKW_Q8K_TW2, SKW_Q8K_TW4, SKW_Q8K_LDS };
+int skw_gemm_q8_kernel(const SkwGemmArgs& a, const SkwQ8Args& qa);
 void skw_dec_embed_f32(const float* te32, const float* pe, const int* tok, const int* pos, int B, int d, float* x, hipStream_t s);
 void skw_dec_embed_ln(const half_t* te, const float* pe, const int* tok, const int* pos, int B, int d, float* x, const float* w, const float* b, half_t* y16, hipStream_t s);
 // self attention for one new token per sequence. q: f16 plain [b][d] (already scaled+rounded), kc/vc: f16 plain [b][n_text_ctx][d];

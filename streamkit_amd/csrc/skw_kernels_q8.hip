@@ -261,34 +261,23 @@ __global__ __launch_bounds__(256) void k_gemm_q8_small(SkwGemmArgs a, SkwQ8Args 
         const int n = n0 + 4 * g + r; if (n < a.N) q8_store<EPI>(a, m, n, v);
     }
 }
-template <int EPI, int FORM> static void launch_gemm_q8_small(const SkwGemmArgs& a, const SkwQ8Args& qa, hipStream_t s) {
-    const dim3 gs((a.N + 15) / 16, (a.M + 15) / 16); const int bps = (a.K >> 5) >> 2;
-    if (bps <= 6) hipLaunchKernelGGL((k_gemm_q8_small<EPI, FORM, 6>), gs, dim3(256), 0, s, a, qa);
-    else hipLaunchKernelGGL((k_gemm_q8_small<EPI, FORM, 8>), gs, dim3(256), 0, s, a, qa);
+// which kernel a product runs on: the one place that decides it (launch_gemm_q8 below branches on the answer, and the test entry skw_debug_gemm_q8 reports it)
+int skw_gemm_q8_kernel(const SkwGemmArgs& a, const SkwQ8Args& qa) {
+    if (qa.segmented) return ((a.K >> 5) >> 2) <= 6 ? SKW_Q8K_SMALL6 : SKW_Q8K_SMALL8;                      // the decoder's products
+    if (a.M < 1024) return SKW_Q8K_TW2;
+    return (skw_sw(SW_Q8_LDS) && !(a.N & 127) && !(a.K & 63) && !(a.M & 3)) ? SKW_Q8K_LDS : SKW_Q8K_TW4;
+}
+template <int EPI, int FORM> static void launch_gemm_q8_form(const SkwGemmArgs& a, const SkwQ8Args& qa, hipStream_t s) {
+    switch (skw_gemm_q8_kernel(a, qa)) {
+        case SKW_Q8K_SMALL6: hipLaunchKernelGGL((k_gemm_q8_small<EPI, FORM, 6>), dim3((a.N + 15) / 16, (a.M + 15) / 16), dim3(256), 0, s, a, qa); break;
+        case SKW_Q8K_SMALL8: hipLaunchKernelGGL((k_gemm_q8_small<EPI, FORM, 8>), dim3((a.N + 15) / 16, (a.M + 15) / 16), dim3(256), 0, s, a, qa); break;
+        case SKW_Q8K_LDS: hipLaunchKernelGGL((k_gemm_q8_lds<EPI, FORM>), dim3(a.N / 128, (a.M + 127) / 128), dim3(256), 0, s, a, qa); break;
+        case SKW_Q8K_TW4: hipLaunchKernelGGL((k_gemm_q8<EPI, FORM, 4>), dim3((a.N + 127) / 128, (a.M + 127) / 128), dim3(256), 0, s, a, qa); break;
+        default: hipLaunchKernelGGL((k_gemm_q8<EPI, FORM, 2>), dim3((a.N + 63) / 64, (a.M + 63) / 64), dim3(256), 0, s, a, qa); break;
+    }
 }
 template <int EPI> static void launch_gemm_q8(const SkwGemmArgs& a, const SkwQ8Args& qa, hipStream_t s) {
-    if (qa.segmented) {                     // the decoder's products
-        if (qa.form == 1) launch_gemm_q8_small<EPI, 1>(a, qa, s); else if (qa.form == 2) launch_gemm_q8_small<EPI, 2>(a, qa, s); else launch_gemm_q8_small<EPI, 3>(a, qa, s);
-        return;
-    }
-    if (skw_sw(SW_Q8_LDS) && a.M >= 1024 && !(a.N & 127) && !(a.K & 63) && !(a.M & 3)) {
-        const dim3 grid(a.N / 128, (a.M + 127) / 128);
-        if (qa.form == 1) hipLaunchKernelGGL((k_gemm_q8_lds<EPI, 1>), grid, dim3(256), 0, s, a, qa);
-        else if (qa.form == 2) hipLaunchKernelGGL((k_gemm_q8_lds<EPI, 2>), grid, dim3(256), 0, s, a, qa);
-        else hipLaunchKernelGGL((k_gemm_q8_lds<EPI, 3>), grid, dim3(256), 0, s, a, qa);
-        return;
-    }
-    if (a.M >= 1024) {
-        const dim3 grid((a.N + 127) / 128, (a.M + 127) / 128);
-        if (qa.form == 1) hipLaunchKernelGGL((k_gemm_q8<EPI, 1, 4>), grid, dim3(256), 0, s, a, qa);
-        else if (qa.form == 2) hipLaunchKernelGGL((k_gemm_q8<EPI, 2, 4>), grid, dim3(256), 0, s, a, qa);
-        else hipLaunchKernelGGL((k_gemm_q8<EPI, 3, 4>), grid, dim3(256), 0, s, a, qa);
-        return;
-    }
-    const dim3 grid((a.N + 63) / 64, (a.M + 63) / 64);
-    if (qa.form == 1) hipLaunchKernelGGL((k_gemm_q8<EPI, 1, 2>), grid, dim3(256), 0, s, a, qa);
-    else if (qa.form == 2) hipLaunchKernelGGL((k_gemm_q8<EPI, 2, 2>), grid, dim3(256), 0, s, a, qa);
-    else hipLaunchKernelGGL((k_gemm_q8<EPI, 3, 2>), grid, dim3(256), 0, s, a, qa);
+    if (qa.form == 1) launch_gemm_q8_form<EPI, 1>(a, qa, s); else if (qa.form == 2) launch_gemm_q8_form<EPI, 2>(a, qa, s); else launch_gemm_q8_form<EPI, 3>(a, qa, s);
 }
 bool skw_gemm_q8(const SkwGemmArgs& a, const SkwQ8Args& qa, hipStream_t s) {
     if ((a.K & 31) || qa.form < 1 || qa.form > 3 || (qa.segmented && ((a.K & 127) || a.M > 4096))) return false;

@@ -143,6 +143,10 @@ def lib():
         L.skw_debug_switch_get.argtypes = [C.c_char_p]
         L.skw_debug_switch_set.argtypes = [C.c_char_p, C.c_int]
         L.skw_debug_attn16.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+        L.skw_debug_gemm_q8.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.POINTER(C.c_int)])
+        L.skw_debug_q8_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.skw_debug_self_attn_q8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10
         _LIB = L
     return _LIB
 
@@ -508,6 +512,52 @@ class Context:
                                                 int(k_pad), int(v_pad), None if slot_k is None else slot_k.ctypes.data, row0.size, row0.ctypes.data, nq.ctypes.data, slot.ctypes.data,
                                                 int(sentinel), out.ctypes.data))
         return out
+
+    def gemm_q8(self, qtype, blocks, N, K, A, segmented, epi, C_buf, ldc=0, bias=None, res_alias=False, scale=1.0, has_scale=0, n_ctx=0, H=0, Tpad=0, pos=None,
+                C2_buf=None, C3_buf=None, ldc2=0):
+        """One product of ggml's arithmetic for quantised files on caller-supplied operands (skw_debug_gemm_q8, skw_engine.hip): `blocks` (bytes: N rows of K / 32 blocks of ggml
+        type qtype) go through the model loader's repack, A (f32 [M][lda >= K]: the first K columns are the rows) through skw_q8_quantize, then skw_gemm_q8 — the public
+        launchers, dispatch included.  C_buf (and C2_buf / C3_buf for EPI_DEC_QKV) are flat arrays holding what the output buffers hold BEFORE the launch: the caller's sentinel
+        with its margin (res_alias: the residual in C's M x N region); they are not modified.  -> (kernel id, C, C2, C3): the buffers after the launch."""
+        Ah = np.ascontiguousarray(A, dtype=np.float32); M, lda = Ah.shape
+        blocks = np.frombuffer(blocks, np.uint8)
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+        bias = f32(bias); pos = None if pos is None else np.ascontiguousarray(pos, dtype=np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        Cb = np.ascontiguousarray(C_buf).copy(); C2 = None if C2_buf is None else np.ascontiguousarray(C2_buf).copy(); C3 = None if C3_buf is None else np.ascontiguousarray(C3_buf).copy()
+        assert bias is None or bias.size == N
+        assert (C2 is None) == (C3 is None) and (C2 is None or C2.nbytes == C3.nbytes)
+        kid = C.c_int(-1)
+        self._check(lib().skw_debug_gemm_q8(self.h, int(qtype), blocks.ctypes.data, N, K, Ah.ctypes.data, lda, M, 1 if segmented else 0, int(epi), int(n_ctx), int(H), int(Tpad), ptr(bias),
+                                            1 if res_alias else 0, float(scale), int(has_scale), ptr(pos), Cb.ctypes.data, Cb.nbytes, int(ldc), ptr(C2), ptr(C3),
+                                            0 if C2 is None else C2.nbytes, int(ldc2), C.byref(kid)))
+        return kid.value, Cb, C2, C3
+
+    def q8_quantize(self, x, K):
+        """k_q8_quantize on f32 rows x [M][ldx >= K] (skw_debug_q8_quantize) -> q int8 [M][K], d and s f32 [K/32][M]"""
+        x = np.ascontiguousarray(x, dtype=np.float32); M, ldx = x.shape
+        q = np.empty((M, K), np.int8); dT = np.empty((K // 32, M), np.float32); sT = np.empty((K // 32, M), np.float32)
+        self._check(lib().skw_debug_q8_quantize(self.h, x.ctypes.data, ldx, M, K, q.ctypes.data, dT.ctypes.data, sT.ctypes.data))
+        return q, dT, sT
+
+    def self_attn_q8(self, H, n_text_ctx, Q, K, V, pos, active=None, seq=None, sentinel=0x5A):
+        """The decoder's exact self attention twice on the same operands (skw_debug_self_attn_q8): with f32 output and leaving its rows as q8 blocks.  Q [rows][H*64], K / V
+        [rows][n_text_ctx][H*64] float16; pos / active / seq per row.  Every byte of the four outputs starts as `sentinel`.
+        -> (out f32 [rows][H*64], q int8 [rows][H*64], d, s f32 [2H][rows])"""
+        d = H * 64
+        bits = lambda a: np.ascontiguousarray(a.view(np.uint16) if a.dtype == np.float16 else a, dtype=np.uint16)
+        ints = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        Q = bits(Q); K = bits(K); V = bits(V); rows = Q.shape[0]
+        assert Q.shape == (rows, d) and K.shape == (rows, n_text_ctx, d) and V.shape == K.shape
+        pos, active, seq = ints(pos), ints(active), ints(seq)
+        for a in (pos, active, seq):
+            assert a is None or a.size == rows
+        out = np.full((rows, d), sentinel, np.uint8).repeat(4, axis=1).view(np.float32); q = np.full((rows, d), sentinel, np.uint8).view(np.int8)
+        dT = np.full((2 * H, rows * 4), sentinel, np.uint8).view(np.float32); sT = dT.copy()
+        self._check(lib().skw_debug_self_attn_q8(self.h, H, n_text_ctx, rows, Q.ctypes.data, K.ctypes.data, V.ctypes.data, pos.ctypes.data, ptr(active), ptr(seq),
+                                                 out.ctypes.data, q.ctypes.data, dT.ctypes.data, sT.ctypes.data))
+        return out, q, dT, sT
 
     def math(self, kind, x):
         x = np.ascontiguousarray(x, dtype=np.float32)

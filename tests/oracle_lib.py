@@ -49,6 +49,7 @@ def lib():
         L.skwo_set_quant_mode.argtypes = [C.c_int]
         L.skwo_model_quant.argtypes = [C.c_void_p]
         L.skwo_debug_linear_q8.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.skwo_debug_linear_q8_seg.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.skwo_get_hparams.argtypes = [C.c_void_p, C.POINTER(HParams)]
         L.skwo_token_str.restype = C.c_void_p
         L.skwo_token_str.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]

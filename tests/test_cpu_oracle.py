@@ -10,6 +10,7 @@ import pytest
 
 import oracle_lib
 from ggml_reader import read_ggml
+from q8_ref_lib import np_q8_mul_mat as _np_q8_mul_mat
 from streamkit_amd import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -273,57 +274,6 @@ def test_quantised_ggml_is_read_as_its_dequantised_f16_twin(kind, tmp_path):
     a = oracle_lib.OracleModel(qpath, quant_mode=0).full(pcm)
     b = oracle_lib.OracleModel(twin).full(pcm)
     assert a["tokens"] == b["tokens"] and a["segments"] == b["segments"] and len(a["tokens"]) > 0
-
-
-def _np_q8_mul_mat(kind, blocks, n_out, n_in, A):
-    """ggml's quantised mul_mat restated step by step in numpy float32 scalars (include/skw_ggml_quant.h (a)), independent of the C code."""
-    import struct
-    f1 = np.float32
-    bb = {"q4_0": 18, "q4_1": 20, "q5_0": 22, "q5_1": 24, "q8_0": 34}[kind]
-    nb = n_in // 32
-    raw = np.frombuffer(blocks, np.uint8).reshape(n_out * nb, bb)
-    qw = np.zeros((n_out * nb, 32), np.int32); dw = np.zeros(n_out * nb, np.float32); mw = np.zeros(n_out * nb, np.float32)
-    for i, b in enumerate(raw):
-        o = 0
-        dw[i] = np.frombuffer(b[o:o + 2].tobytes(), np.float16)[0]; o += 2
-        if kind in ("q4_1", "q5_1"):
-            mw[i] = np.frombuffer(b[o:o + 2].tobytes(), np.float16)[0]; o += 2
-        qh = 0
-        if kind in ("q5_0", "q5_1"):
-            qh = struct.unpack("<I", b[o:o + 4].tobytes())[0]; o += 4
-        qs = b[o:]
-        if kind == "q8_0":
-            qw[i] = qs.view(np.int8)
-            continue
-        for j in range(16):
-            x0, x1 = int(qs[j]) & 15, int(qs[j]) >> 4
-            if kind in ("q5_0", "q5_1"):
-                x0 |= ((qh >> j) & 1) << 4; x1 |= ((qh >> (j + 16)) & 1) << 4
-            off = 8 if kind == "q4_0" else 16 if kind == "q5_0" else 0
-            qw[i, j], qw[i, j + 16] = x0 - off, x1 - off
-    rows = A.shape[0]
-    out = np.zeros((rows, n_out), np.float32)
-    for r in range(rows):
-        qa = np.zeros((nb, 32), np.int32); da = np.zeros(nb, np.float32); sa = np.zeros(nb, np.float32)
-        for b in range(nb):
-            x = A[r, b * 32:(b + 1) * 32]
-            amax = f1(np.abs(x).max()); d = f1(amax / f1(127)); idv = f1(f1(1) / d) if d != 0 else f1(0)
-            v = (x * idv).astype(np.float32).astype(np.float64)
-            q = (np.sign(v) * np.floor(np.abs(v) + 0.5)).astype(np.int32)          # roundf: half away from zero (exact in f64)
-            qa[b] = q; da[b] = f1(np.float16(d)); sa[b] = f1(np.float16(f1(f1(int(q.sum())) * d)))
-        for n in range(n_out):
-            sumf = f1(0)
-            for b in range(nb):
-                i = n * nb + b; sumi = int((qw[i] * qa[b]).sum())
-                if kind == "q4_0":
-                    t = f1(f1(f1(sumi) * dw[i]) * da[b])
-                else:
-                    t = f1(f1(dw[i] * da[b]) * f1(sumi))
-                    if kind in ("q4_1", "q5_1"):
-                        t = f1(t + f1(mw[i] * sa[b]))
-                sumf = f1(sumf + t)
-            out[r, n] = sumf
-    return out
 
 
 @pytest.mark.parametrize("kind", ["q4_0", "q4_1", "q5_0", "q5_1", "q8_0"])
