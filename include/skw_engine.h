@@ -172,6 +172,24 @@ int  skw_full_batch_mixed(skw_ctx*, const skw_full_params* params /* [n_clips] *
 int  skw_full_batch_context(skw_ctx*, const skw_full_params* params /* [n_clips] */, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                             uint32_t* const* rng_state /* as skw_full_batch_mixed */, int32_t* const* context /* NULL, or [n_clips] with entries that may be NULL */, skw_result* results);
 
+/* Decoding constraints per clip, applied to the f32 logits row of every sampling decision before the sampler (k_dec_constrain), in this order:
+ *   1. bias                  x[bias_id[k]] += bias[k] for k < n_bias: distinct ids in [0, n_vocab), each bias finite or -inf (-inf: the token is suppressed)
+ *   2. repetition_penalty t  (finite, > 0; 1 = off) for each DISTINCT text token id of the pass so far: x[id] = x[id] < 0 ? x[id] * t : x[id] / t — once, however often it occurred
+ *   3. no_repeat_ngram_size N (>= 0; 0 = off) with T = the pass's text tokens, m of them: for every i in 0 .. m - N with T[i .. i+N-1) == T[m-N+1 .. m), x[T[i+N-1]] = -inf
+ * "the pass so far": the ids sampled in the current temperature pass of the current window that are below <|endoftext|> — timestamps, <|endoftext|> and specials neither count nor
+ * are touched by 2 and 3, and the prompt ([prev] + carried context + sot / language / task) is not part of it.  The sampler then takes the row exactly where it took the decoder's:
+ * no_speech_prob of a window's first decision is computed from the biased row (2 and 3 cannot move it: the history is empty there).  Not applied in the language-detection pass.
+ * skw_full_batch_rules is skw_full_batch_context with one such record per clip: rules == NULL, a NULL entry or a default entry is skw_full_batch_context for that clip, bit for bit,
+ * and a call whose clips are all default is that call launch for launch.  A bad record (t not finite or <= 0, N < 0, n_bias outside 0 .. SKW_BIAS_MAX, an id outside the vocabulary
+ * or given twice, a bias that is +inf or NaN) fails the call before anything runs, naming the clip. */
+#define SKW_BIAS_MAX 256
+typedef struct { float repetition_penalty; int32_t no_repeat_ngram_size; int32_t n_bias; int32_t pad;
+                 int32_t bias_id[SKW_BIAS_MAX]; float bias[SKW_BIAS_MAX]; } skw_decode_rules;
+void skw_decode_rules_default(skw_decode_rules*);            /* 1.0, 0, 0 */
+int  skw_full_batch_rules(skw_ctx*, const skw_full_params* params /* [n_clips] */, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                          uint32_t* const* rng_state, int32_t* const* context, const skw_decode_rules* const* rules /* NULL, or [n_clips] with entries that may be NULL */,
+                          skw_result* results);
+
 /* ---- decision trace / teacher forcing (parity instrumentation of the hot path; the reference has no counterpart) ----
  * skw_full_batch_traced is skw_full_batch that also returns, per clip, one record for EVERY sampling decision it made, in execution order
  * over all windows and temperature passes (discarded tokens included).  With forced_ids[i] == NULL the run is free (forced_id == chosen_id).
@@ -204,7 +222,7 @@ typedef struct { float mel_ms, encode_ms, decode_ms, total_ms; int32_t n_windows
 } skw_timing;
 void skw_ctx_last_timing(const skw_ctx*, skw_timing* out);
 /* per-kernel-class event timing (adds an event pair around every launch; use for roofline accounting, not for the timed run).
- * classes: 0 k_gemm, 1 k_gemm_smallm, 2 k_attn_encoder, 3 k_layernorm, 4 k_mel, 5 k_dec_self_attn, 6 k_dec_sample, 7 other, 8 k_dec_cross_attn */
+ * classes: 0 k_gemm, 1 k_gemm_smallm, 2 k_attn_encoder, 3 k_layernorm, 4 k_mel, 5 k_dec_self_attn, 6 k_dec_sample, 7 other, 8 k_dec_cross_attn, 9 k_dec_constrain */
 void skw_ctx_profile(skw_ctx*, int on);
 int  skw_ctx_profile_get(skw_ctx*, int cls, char* name, size_t name_len, long* count, double* ms, double* algorithmic_flops, double* algorithmic_bytes);
 /* In-kernel launch clock of the decode step's dominant kernel (the f16_mfma cross attention).  HIP events cannot sit between the kernels of a captured step graph, and an eager,

@@ -8,6 +8,7 @@
 #include "../../include/skw_ggml_quant.h"
 #include "skw_kernels.h"
 #include "skw_tokenizer.h"
+#include "skw_decode_rules.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -480,7 +481,8 @@ struct skw_ctx {
     hipStream_t stream = nullptr; hipEvent_t ev[6] = {};
     hipStream_t cur = nullptr;                       // stream the launch helpers enqueue on (== stream outside the decode groups)
     static const int MAX_GROUPS = 8; hipStream_t gstream[MAX_GROUPS] = {}; hipEvent_t gev[MAX_GROUPS] = {}; int n_groups = 1;
-    struct StepGraph { int g, r0, n, precision, ln_stats, kclk, var_k; unsigned sw_epoch; SkwLogitParams lp; int rows; hipGraphExec_t exec; }; std::vector<StepGraph> step_graphs; int use_graphs = 1;
+    struct StepGraph { int g, r0, n, precision, ln_stats, kclk, var_k; unsigned sw_epoch; SkwLogitParams lp; int rows, cons; hipGraphExec_t exec; };
+    std::vector<StepGraph> step_graphs; int use_graphs = 1;
     char errbuf[512] = {0};
     std::vector<void*> allocs;
     // front end
@@ -509,6 +511,7 @@ struct skw_ctx {
     SkwSeqState* st = nullptr; SkwTokenOut* toks = nullptr; uint8_t* static_mask = nullptr; int static_mask_nst = -1;
     // skw_full_batch_mixed: both static masks back to back ([0] without, [1] with the non-speech list; written at the first mixed call) and the rows' own rules, per window
     uint8_t* static_mask_pair = nullptr; int static_mask_pair_built = 0; SkwRowRules* row_rules = nullptr;
+    SkwRowConstraints* row_cons = nullptr;           // skw_full_batch_rules: the rows' decoding constraints, per window (read by k_dec_constrain, which only constrained calls launch)
     SkwSeqState* h_st = nullptr; SkwTokenOut* h_toks = nullptr; // pinned
     int* h_row_live = nullptr; int* d_row_live = nullptr;      // per-row live flags in pinned host memory and their device-side address: k_dec_sample clears a row's flag itself,
                                                                // so a step ends with no 4-byte copy kernel (4.2 us in the chain of every step) — the host reads the flags after the stream drains
@@ -628,6 +631,7 @@ extern "C" skw_ctx* skw_ctx_create(skw_model* m, int max_batch, int max_samples,
     want("static_mask", c->static_mask, skw_static_mask_bytes(hp.n_vocab), true);
     want("static_mask_pair", c->static_mask_pair, 2 * skw_static_mask_bytes(hp.n_vocab), true);
     want("row_rules", c->row_rules, B, true);
+    want("row_cons", c->row_cons, B, true);
     if (m->quant) {      // ggml q8 arithmetic (quantised files, exact precision): unrounded f32 activations and their q8 blocks
         want("y32", c->y32, enc_rows * d, false);
         want("h32", c->h32, enc_rows * 4 * d, false);
@@ -729,8 +733,9 @@ static void tap(skw_ctx* c, const char* name, const void* dev, int rows, int col
 }
 
 // ------------------------------------------------------------------ per-kernel-class profiling (HIP events on the engine stream)
-enum ProfClass { PC_GEMM = 0, PC_GEMM_SMALL, PC_ATTN_ENC, PC_LAYERNORM, PC_MEL, PC_DEC_ATTN, PC_DEC_SAMPLE, PC_OTHER, PC_DEC_XATTN, PC_COUNT };
-static const char* const g_prof_names[PC_COUNT] = {"k_gemm", "k_gemm_smallm", "k_attn_encoder", "k_layernorm", "k_mel", "k_dec_self_attn", "k_dec_sample", "other", "k_dec_cross_attn"};
+enum ProfClass { PC_GEMM = 0, PC_GEMM_SMALL, PC_ATTN_ENC, PC_LAYERNORM, PC_MEL, PC_DEC_ATTN, PC_DEC_SAMPLE, PC_OTHER, PC_DEC_XATTN, PC_DEC_CONSTRAIN, PC_COUNT };
+static const char* const g_prof_names[PC_COUNT] = {"k_gemm", "k_gemm_smallm", "k_attn_encoder", "k_layernorm", "k_mel", "k_dec_self_attn", "k_dec_sample", "other", "k_dec_cross_attn",
+                                                 "k_dec_constrain"};
 struct ProfRec { int cls; double flops, bytes; hipEvent_t a, b; };
 struct ProfState { bool on = false; std::vector<ProfRec> recs;
 std::vector<hipEvent_t> pool; size_t next = 0; double ms[PC_COUNT] = {}, flops[PC_COUNT] = {}, bytes[PC_COUNT] = {}; long count[PC_COUNT] = {}; };
@@ -1109,11 +1114,13 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
 // One generation step of a row group as an executable graph: decoder step (positions and tokens read from the device state),
 // logit filters + sampling, and the read-back of the group's active count.  Captured once per (group, rows, filter params).
 // rows: the per-row form of the sampler (skw_full_batch_mixed) — lp then holds model constants and any_sampled only, so one graph serves every parameter mix of its shape
-static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogitParams& lp, bool rows) {
+// cons: some clip of the call has decoding constraints (skw_full_batch_rules): k_dec_constrain sits between the logits GEMM and the sampler; the rows' records are device memory,
+//  so that graph too serves every mix.  Calls without constraints key cons = 0 and replay the graphs they always did
+static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogitParams& lp, bool rows, bool cons) {
     for (size_t i = 0; i < c->step_graphs.size(); ++i) {
         auto& sg = c->step_graphs[i];
         if (sg.g == g && sg.r0 == r0 && sg.n == n && sg.precision == c->precision && sg.ln_stats == c->ln_stats_on && sg.kclk == c->kclk_on && sg.sw_epoch == skw_sw_epoch() &&
-            sg.var_k == (int)c->var_k && sg.rows == (int)rows && memcmp(&sg.lp, &lp, sizeof lp) == 0) {
+            sg.var_k == (int)c->var_k && sg.rows == (int)rows && sg.cons == (int)cons && memcmp(&sg.lp, &lp, sizeof lp) == 0) {
             if (i + 1 != c->step_graphs.size()) { auto hit = sg; c->step_graphs.erase(c->step_graphs.begin() + i); c->step_graphs.push_back(hit); }   // most recently used last
             return c->step_graphs.back().exec;
         }
@@ -1123,6 +1130,7 @@ static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogi
     c->cur_group = g;
     run_decoder_step(c, r0, n, 0, true, s);
     c->cur_group = 0;
+    if (cons) skw_dec_constrain(c->logits + (size_t)r0 * NV, NV, lp.tok_eot, c->row_cons + r0, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, s);
     if (rows) skw_dec_sample_rows(c->logits + (size_t)r0 * NV, c->static_mask_pair, lp, c->row_rules + r0, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->d_row_live + r0,
         c->probs + (size_t)r0 * skw_probs_row_floats(NV), c->rng, c->clip_idx + r0, c->prompt_buf + (size_t)r0 * SKW_PROMPT_CAP, s);
     else skw_dec_sample(c->logits + (size_t)r0 * NV, c->static_mask, lp, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->d_row_live + r0,
@@ -1134,7 +1142,7 @@ static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogi
         // bounded: a long-lived server with ragged batches would otherwise keep one executable graph per (group, rows, params) forever
         if (c->step_graphs.size() >= 24) { hipGraphExecDestroy(c->step_graphs.front().exec); c->step_graphs.erase(c->step_graphs.begin()); }
         skw_ctx::StepGraph sg; sg.g = g; sg.r0 = r0; sg.n = n; sg.precision = c->precision; sg.ln_stats = c->ln_stats_on; sg.kclk = c->kclk_on; sg.var_k = (int)c->var_k;
-         sg.sw_epoch = skw_sw_epoch(); sg.lp = lp; sg.rows = (int)rows; sg.exec = exec; c->step_graphs.push_back(sg);
+         sg.sw_epoch = skw_sw_epoch(); sg.lp = lp; sg.rows = (int)rows; sg.cons = (int)cons; sg.exec = exec; c->step_graphs.push_back(sg);
     }
     return exec;
 }
@@ -1184,6 +1192,14 @@ static SkwRowRules make_row_rules(const skw_model* m, const skw_full_params* p) 
     SkwRowRules r{}; r.suppress_blank = lp.suppress_blank; r.suppress_nst = lp.suppress_nst; r.no_timestamps = lp.no_timestamps; r.single_segment = lp.single_segment;
     r.max_tokens = lp.max_tokens; r.tid0_initial = lp.tid0_initial;
     return r;
+}
+// skw_decode_rules is SkwRowConstraints, field for field (NULL: the default record)
+static_assert(sizeof(skw_decode_rules) == sizeof(SkwRowConstraints) && offsetof(skw_decode_rules, bias_id) == offsetof(SkwRowConstraints, bias_id) &&
+              offsetof(skw_decode_rules, bias) == offsetof(SkwRowConstraints, bias) && SKW_BIAS_MAX == SKW_CONSTRAIN_BIAS_MAX, "skw_decode_rules is SkwRowConstraints");
+static SkwRowConstraints make_row_constraints(const skw_decode_rules* r) {
+    SkwRowConstraints o; skw_decode_rules d; if (!r) { skw_decode_rules_set_default(&d); r = &d; }
+    memcpy(&o, r, sizeof o); o.pad = 0;
+    return o;
 }
 static SkwLogitParams mixed_logit_params(const skw_model* m) {
     skw_full_params z{};      // (no request: the six fields stay 0 / -1 and the per-row form never reads them)
@@ -1256,6 +1272,7 @@ struct FullRequest {
     const float* const* pcm = nullptr; const int32_t* n_samples = nullptr; int n_clips = 0; int pcm_on_device = 0; skw_result* results = nullptr;
     const int32_t* const* forced_ids = nullptr; const int32_t* n_forced = nullptr; std::vector<std::vector<SkwTraceStep>>* traces = nullptr;      // tracing / teacher forcing
     uint32_t* const* rng_state = nullptr; int32_t* const* context = nullptr;
+    const skw_decode_rules* const* rules = nullptr; bool constrained = false;      // skw_full_batch_rules; constrained: some clip's record is not the default (set by validate_request)
     bool mixed() const { return pv != nullptr; }
     bool tracing() const { return traces != nullptr; }
     const skw_full_params& P(int ci) const { return pv ? pv[ci] : *p; }
@@ -1277,6 +1294,7 @@ struct WindowBatch {
     std::vector<int> act, retry_old;      // the clips of the rows; the slots the first R of them (retries) left their cross K/V in
     int R = 0, Bw = 0, enc_rows = 0, prefill_passes = 0;
     std::vector<int> sk, ks, pbuf, np_row, fbuf; std::vector<SkwRowRules> rules;      // per row: seek, key count, prompt (SKW_PROMPT_CAP ids) and its length, forced tokens, request rules
+    std::vector<SkwRowConstraints> cons;      // per row: decoding constraints (constrained calls only)
 };
 struct RowGroups { int G = 0; int r0[skw_ctx::MAX_GROUPS], n[skw_ctx::MAX_GROUPS]; bool live[skw_ctx::MAX_GROUPS]; };
 }
@@ -1300,13 +1318,19 @@ static int ensure_trace_buffers(skw_ctx* c) {
     return 0;
 }
 
-static int validate_request(skw_ctx* c, const FullRequest& rq) {
+static int validate_request(skw_ctx* c, FullRequest& rq) {
     char* errbuf = c->errbuf; const skw_hparams& hp = c->m->hp;
     if (rq.n_clips < 1 || rq.n_clips > c->max_batch) { snprintf(errbuf, 512, "n_clips %d outside [1, %d]", rq.n_clips, c->max_batch); return -1; }
     for (int i = 0; i < rq.n_clips; ++i) if (rq.P(i).audio_ctx < 0 || rq.P(i).audio_ctx > hp.n_audio_ctx) {
         snprintf(errbuf, 512, "clip %d: audio_ctx %d outside [0, %d] (0 = the model's n_audio_ctx)", i, rq.P(i).audio_ctx, hp.n_audio_ctx); return -3; }
     // contexts handed in (skw_full_batch_context) are checked before anything is launched: a refused call leaves every context, like every generator state, as it was
     if (rq.context) for (int i = 0; i < rq.n_clips; ++i) if (rq.context[i] && !skw_context_check(rq.context[i], SKW_CONTEXT_WORDS - 1, hp.n_vocab, i, errbuf, 512)) return -3;
+    rq.constrained = false;
+    if (rq.rules) for (int i = 0; i < rq.n_clips; ++i) {
+        char who[32]; snprintf(who, sizeof who, "clip %d", i);
+        if (!skw_decode_rules_check(rq.rules[i], hp.n_vocab, who, errbuf, 512)) return -3;
+        if (!skw_decode_rules_is_default(rq.rules[i])) rq.constrained = true;
+    }
     return 0;
 }
 
@@ -1404,6 +1428,10 @@ static int stage_window(skw_ctx* c, const FullRequest& rq, CallState& cs, Window
         w.rules.resize(Bw); for (int j = 0; j < Bw; ++j) w.rules[j] = make_row_rules(m, &rq.P(act[j]));
         HIPCHK(hipMemcpyAsync(c->row_rules, w.rules.data(), sizeof(SkwRowRules) * Bw, hipMemcpyHostToDevice, c->stream));
     }
+    if (rq.constrained) {      // the rows' constraints, like their rules: a clip without a record gets the default, which k_dec_constrain leaves alone
+        w.cons.resize(Bw); for (int j = 0; j < Bw; ++j) w.cons[j] = make_row_constraints(rq.rules[act[j]]);
+        HIPCHK(hipMemcpyAsync(c->row_cons, w.cons.data(), sizeof(SkwRowConstraints) * Bw, hipMemcpyHostToDevice, c->stream));
+    }
     cs.lp.any_sampled = 0; for (int j = 0; j < Bw; ++j) if (cs.temps[act[j]][cs.tidx[act[j]]] > 0.0f) cs.lp.any_sampled = 1;      // (part of the step graph's key: greedy passes run the lean sampler)
     if (rq.tracing()) {      // this pass's forced tokens per row: the clip's sequence from its cursor on (-1 = none: the row feeds its own choices)
         w.fbuf.assign((size_t)Bw * c->max_tok, -1);
@@ -1488,6 +1516,8 @@ static RowGroups cut_row_groups(const skw_ctx* c, int Bw) {
 static void sample_group(skw_ctx* c, const FullRequest& rq, const SkwLogitParams& lp, const RowGroups& rg, int g) {
     const int NV = c->m->hp.n_vocab, r0 = rg.r0[g], n = rg.n[g]; const bool tracing = rq.tracing();
     c->cur = c->gstream[g];
+    if (rq.constrained) { ProfScope p_(c, PC_DEC_CONSTRAIN, 0, 0);
+      skw_dec_constrain(c->logits + (size_t)r0 * NV, NV, lp.tok_eot, c->row_cons + r0, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->gstream[g]); }
     { ProfScope p_(c, PC_DEC_SAMPLE, 0, 4.0 * n * NV);
       if (rq.mixed()) skw_dec_sample_rows(c->logits + (size_t)r0 * NV, c->static_mask_pair, lp, c->row_rules + r0, c->st + r0,
         c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->d_row_live + r0, c->probs + (size_t)r0 * skw_probs_row_floats(NV), c->rng,
@@ -1512,7 +1542,7 @@ static int step_loop(skw_ctx* c, const FullRequest& rq, CallState& cs, const Win
     HIPCHK(hipEventRecord(c->ev[5], c->stream));
     for (int g = 0; g < G; ++g) HIPCHK(hipStreamWaitEvent(c->gstream[g], c->ev[5], 0));
     hipGraphExec_t gexec[skw_ctx::MAX_GROUPS] = {};
-    if (use_graphs && !profiling && !tracing) for (int g = 0; g < G; ++g) gexec[g] = step_graph(c, g, rg.r0[g], rg.n[g], lp, rq.mixed());   // nullptr -> eager launches
+    if (use_graphs && !profiling && !tracing) for (int g = 0; g < G; ++g) gexec[g] = step_graph(c, g, rg.r0[g], rg.n[g], lp, rq.mixed(), rq.constrained);   // nullptr -> eager launches
     // The host learns whether a group still has live rows only by waiting for its stream, and a wait + relaunch per step leaves the
     // GPU idle for the turnaround.  So steps are enqueued `ahead` at a time and the count is read once per block: a step that
     // runs after the last row of its group has finished changes nothing (its attention and sampling kernels return at once for
@@ -1611,7 +1641,7 @@ static int finish_call(skw_ctx* c, const FullRequest& rq, CallState& cs) {
     return 0;
 }
 
-static int full_batch_impl(skw_ctx* c, const FullRequest& rq) {
+static int full_batch_impl(skw_ctx* c, FullRequest rq) {
     char* errbuf = c->errbuf; errbuf[0] = 0;
     WS_READY(c);
     if (int rc = validate_request(c, rq)) return rc;
@@ -1668,6 +1698,14 @@ extern "C" int skw_full_batch_context(skw_ctx* c, const skw_full_params* params,
         FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state; rq.context = context;
         return full_batch_impl(c, rq); });
 }
+extern "C" void skw_decode_rules_default(skw_decode_rules* r) { skw_decode_rules_set_default(r); }
+extern "C" int skw_full_batch_rules(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                                    uint32_t* const* rng_state, int32_t* const* context, const skw_decode_rules* const* rules, skw_result* results) {
+    return guarded(c, "skw_full_batch_rules", [&] {
+        if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_rules: params is NULL (one skw_full_params per clip)"); return -1; }
+        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state; rq.context = context; rq.rules = rules;
+        return full_batch_impl(c, rq); });
+}
 extern "C" int skw_full_batch_traced_context(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                              const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, int32_t* const* context, skw_result* results) {
     static_assert(sizeof(skw_trace_step) == sizeof(SkwTraceStep), "skw_trace_step is SkwTraceStep");
@@ -1693,8 +1731,10 @@ extern "C" int skw_full_batch_traced(skw_ctx* c, const skw_full_params* p, const
 // memory) makes each row's next decision.  has_ts / seek_delta / result_len are replayed from the history by the token loop's update rule, as
 // oracle/skwo_debug_process_logits does.  Outputs per row: the decision (skw_token), its trace record, and (form 1, optional) the filtered logits.
 // pv (skw_debug_sample_rows_mixed): one skw_full_params per row — the launch is the per-row form of the sampler, each row under its own rules and its own static mask.
+// rv (skw_debug_sample_rows_rules): one skw_decode_rules (or NULL) per row — k_dec_constrain runs on the rows' logits ahead of the sampler, as in the decode step.
 static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const skw_full_params* pv, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
-                                  const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out) {
+                                  const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out,
+                                  const skw_decode_rules* const* rv = nullptr) {
     char* errbuf = c->errbuf; errbuf[0] = 0;
     WS_READY(c);
     if (n_rows < 1 || n_rows > c->max_batch) { snprintf(errbuf, 512, "n_rows %d outside [1, %d]", n_rows, c->max_batch); return -1; }
@@ -1703,7 +1743,12 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
     for (int r = 0; r < n_rows; ++r) if (n_hist[r] < 0 || n_hist[r] >= MT || n_hist[r] > hist_stride) { snprintf(errbuf, 512, "row %d: history of %d tokens (at most %d)", r, n_hist[r], MT - 1);
     return -1; }
     if (ensure_trace_buffers(c)) return -1;
-    SkwLogitParams lp; std::vector<SkwRowRules> rules;
+    SkwLogitParams lp; std::vector<SkwRowRules> rules; std::vector<SkwRowConstraints> cons;
+    if (rv) {
+        for (int r = 0; r < n_rows; ++r) { char who[32]; snprintf(who, sizeof who, "row %d", r); if (!skw_decode_rules_check(rv[r], NV, who, errbuf, 512)) return -3; }
+        cons.resize(n_rows); for (int r = 0; r < n_rows; ++r) cons[r] = make_row_constraints(rv[r]);
+        HIPCHK(hipMemcpyAsync(c->row_cons, cons.data(), sizeof(SkwRowConstraints) * n_rows, hipMemcpyHostToDevice, c->stream));
+    }
     if (pv) {
         build_static_mask_pair(c); lp = mixed_logit_params(m);
         rules.resize(n_rows); for (int r = 0; r < n_rows; ++r) rules[r] = make_row_rules(m, &pv[r]);
@@ -1732,6 +1777,7 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
     HIPCHK(hipMemcpyAsync(c->forced_dev, forced.data(), sizeof(int) * forced.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->clip_idx, zero.data(), sizeof(int) * n_rows, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->logits, logits_host, sizeof(float) * (size_t)n_rows * NV, hipMemcpyHostToDevice, c->stream));
+    if (rv) skw_dec_constrain(c->logits, NV, lp.tok_eot, c->row_cons, c->st, c->toks, MT, n_rows, c->stream);
     skw_debug_force_stream_sampler(form == 1);
     if (pv) skw_dec_sample_rows(c->logits, c->static_mask_pair, lp, c->row_rules, c->st, c->toks, MT, n_rows, c->d_row_live, c->probs, c->rng, c->clip_idx, c->prompt_buf, c->stream,
                                 c->forced_dev, c->trace_dev);
@@ -1758,6 +1804,12 @@ extern "C" int skw_debug_sample_rows_mixed(skw_ctx* c, const skw_full_params* pa
                                            const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out) {
     if (!params) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_mixed: params is NULL (one skw_full_params per row)"); return -1; }
     return debug_sample_rows_impl(c, params, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out);
+}
+extern "C" int skw_debug_sample_rows_rules(skw_ctx* c, const skw_full_params* params /* [n_rows] */, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
+                                           const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out,
+                                           const skw_decode_rules* const* rules /* [n_rows], entries may be NULL */) {
+    if (!params || !rules) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_rules: params and rules are one per row (rules entries may be NULL)"); return -1; }
+    return debug_sample_rows_impl(c, params, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out, rules);
 }
 extern "C" void skw_trace_free(skw_trace* t) { if (!t) return; free(t->steps); t->steps = nullptr; t->n = 0; }
 extern "C" void skw_result_free(skw_result* r) { if (!r) return; free(r->segments); free(r->tokens); free(r->text); memset(r, 0, sizeof *r); }

@@ -219,6 +219,13 @@ void skw_dec_sample(float* logits, const uint8_t* static_mask, SkwLogitParams p,
 // (callers leave them zero, so a captured step graph holds no request's values and replays for any parameter mix)
 void skw_dec_sample_rows(float* logits, const uint8_t* static_mask_pair, SkwLogitParams p, const SkwRowRules* rules, SkwSeqState* st, SkwTokenOut* toks, int max_tok, int B, int* n_active,
                          float* probs, uint32_t* rng, const int* clip_idx, const int* prompt_buf, hipStream_t s, const int* forced = nullptr, SkwTraceStep* trace = nullptr);
+// Decoding constraints of one row (skw_full_batch_rules): skw_decode_rules of include/skw_engine.h, field for field, in device memory, written by the host per window like
+// SkwRowRules — and beside it, not inside it: that record's size is pinned above.  A row whose record is the default (1.0, 0, 0) is left alone.
+#define SKW_CONSTRAIN_BIAS_MAX 256
+struct SkwRowConstraints { float penalty; int32_t ngram, n_bias, pad; int32_t bias_id[SKW_CONSTRAIN_BIAS_MAX]; float bias[SKW_CONSTRAIN_BIAS_MAX]; };
+// k_dec_constrain, between the logits GEMM and the sampler: bias, repetition penalty over the distinct text tokens (id < tok_eot) of the row's pass so far (toks[0 .. n_tokens)), then the
+// no-repeat n-gram ban over the same tokens; one workgroup per row, the row's logits edited in place.  Rows that are finished, still feeding their prompt or unconstrained return at once.
+void skw_dec_constrain(float* logits, int n_vocab, int tok_eot, const SkwRowConstraints* cons, const SkwSeqState* st, const SkwTokenOut* toks, int max_tok, int B, hipStream_t s);
 void skw_debug_force_stream_sampler(int on);   // tests: the streaming sampler (filters the logits row in place) even where the register-resident form applies
 void skw_rng_seed(uint32_t* rng, int n_clips, uint32_t seed, hipStream_t s);   // std::mt19937(seed) for every clip
 

@@ -1993,6 +1993,57 @@ void skw_dec_sample_rows(float* logits, const uint8_t* static_mask_pair, SkwLogi
     dec_sample_launch<true>(logits, static_mask_pair, p, st, toks, max_tok, B, n_active, probs, rng, clip_idx, prompt_buf, s, forced, trace, rules);
 }
 
+// ------------------------------------------------------------------ decoding constraints (skw_full_batch_rules): bias, repetition penalty, no-repeat n-gram
+// One workgroup per row, ahead of the sampler and outside it (k_dec_sample's registers are spoken for).  T = the text tokens (id < tok_eot) among the row's sampled tokens of
+// this pass, compacted into LDS in order (a ballot per wave, the waves' counts through LDS); then three phases on the row in global memory, a barrier between them:
+//   bias      one thread per pair; the ids are distinct (host-checked), so no two threads meet
+//   penalty   one thread per element of T, and only the FIRST occurrence of an id acts: it reads what the bias phase left and writes once, so a token seen three times is penalised once
+//   n-gram    one thread per candidate start i: T[i .. i+N-1) against the last N-1 text tokens; a match bans T[i+N-1] (several threads may store the same -inf)
+#define CONSTRAIN_NT 256
+__global__ __launch_bounds__(CONSTRAIN_NT) void k_dec_constrain(float* logits_all, int n_vocab, int tok_eot, const SkwRowConstraints* cons, const SkwSeqState* st_all,
+                                                                const SkwTokenOut* toks_all, int max_tok) {
+    extern __shared__ int s_T[];      // [max_tok]
+    __shared__ int s_cnt[CONSTRAIN_NT / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const SkwSeqState* st = &st_all[b];
+    if (!st->active) return;                        // (all three uniform per block)
+    if (st->cur_pos < st->n_prompt - 1) return;     // still feeding the prompt: the sampler does not sample either
+    const SkwRowConstraints& r = cons[b];
+    const float theta = r.penalty; const int N = r.ngram, n_bias = min(r.n_bias, SKW_CONSTRAIN_BIAS_MAX);
+    if (theta == 1.0f && N == 0 && n_bias <= 0) return;
+    float* lg = logits_all + (long)b * n_vocab;
+    const SkwTokenOut* toks = toks_all + (long)b * max_tok;
+    const int n = min(st->n_tokens, max_tok);
+    int m = 0;
+    for (int c0 = 0; c0 < n; c0 += CONSTRAIN_NT) {      // (one round for every Whisper model: max_tok = n_text_ctx / 2 = 224)
+        const int i = c0 + tid; const int id = i < n ? toks[i].id : 0x7fffffff;
+        const bool text = id >= 0 && id < tok_eot;
+        const unsigned long long bal = __ballot(text);
+        if (lane == 0) s_cnt[w] = __popcll(bal);
+        __syncthreads();
+        int off = m; for (int k = 0; k < w; ++k) off += s_cnt[k];
+        if (text) s_T[off + __popcll(bal & ((1ull << lane) - 1ull))] = id;
+        for (int k = 0; k < CONSTRAIN_NT / 64; ++k) m += s_cnt[k];
+        __syncthreads();
+    }
+    for (int k = tid; k < n_bias; k += CONSTRAIN_NT) { const int id = r.bias_id[k]; if (id >= 0 && id < n_vocab) lg[id] = lg[id] + r.bias[k]; }
+    __syncthreads();
+    if (theta != 1.0f) for (int j = tid; j < m; j += CONSTRAIN_NT) {
+        const int t = s_T[j]; bool first = true;
+        for (int i = 0; i < j; ++i) if (s_T[i] == t) { first = false; break; }
+        if (first) { const float x = lg[t]; lg[t] = x < 0.0f ? x * theta : x / theta; }
+    }
+    __syncthreads();
+    if (N >= 1 && m >= N) for (int i = tid; i <= m - N; i += CONSTRAIN_NT) {
+        bool same = true;
+        for (int k = 0; k < N - 1; ++k) if (s_T[i + k] != s_T[m - N + 1 + k]) { same = false; break; }
+        if (same) lg[s_T[i + N - 1]] = -INFINITY;
+    }
+}
+void skw_dec_constrain(float* logits, int n_vocab, int tok_eot, const SkwRowConstraints* cons, const SkwSeqState* st, const SkwTokenOut* toks, int max_tok, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_dec_constrain, dim3(B), dim3(CONSTRAIN_NT), sizeof(int) * (size_t)max_tok, s, logits, n_vocab, tok_eot, cons, st, toks, max_tok);
+}
+
 // ------------------------------------------------------------------ R1: audio::resampler arithmetic (rubato FastFixedIn, Linear)
 // Restates /root/reference/crates/nodes/src/audio/filters/resampler.rs:231-244, 384-514 (rubato 0.16.2 asynchro_fast.rs):
 // per chunk: idx starts at last_index, `while idx < end_idx { idx += t_ratio; out = (1-frac)*y[floor idx] + frac*y[floor idx + 1] }`,

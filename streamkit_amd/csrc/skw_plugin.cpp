@@ -5,7 +5,8 @@
 // ABI: include/streamkit_native_abi.h.
 //
 // Params beyond the reference's are ADDITIVE (unknown keys are ignored by the reference's serde config, lib.rs:66-104):
-// vad_mode, batch_window_ms, max_batch, mixed_batch, flush_tail, precision, gpu_device: "auto", initial_prompt, carry_context, and input_sample_rate / input_resample_mode (the
+// vad_mode, batch_window_ms, max_batch, mixed_batch, flush_tail, precision, gpu_device: "auto", initial_prompt, carry_context, repetition_penalty,
+// no_repeat_ngram_size, suppress_tokens, logit_bias (decoding constraints per instance, skw_full_batch_rules), and input_sample_rate / input_resample_mode (the
 // audio::resampler node's arithmetic run inside this plugin, skw_resampler_core.h: a 48 kHz Opus source then needs no node in between).
 // One BEHAVIOURAL difference remains and is not additive: with the default vad_mode "auto" the Silero model at `vad_model_path`
 // gates what Whisper sees exactly as in the reference (skw_silero.h) only when that file exists; when it does not, the
@@ -14,6 +15,7 @@
 // reference's hard failure.  INTEGRATION.md section D lists this with the other observable differences.
 #include "../../include/streamkit_native_abi.h"
 #include "../../include/skw_engine.h"
+#include "skw_decode_rules.h"
 #include "skw_segmenter.h"
 #include "../../include/skw_vad_batch.h"
 #include "skw_silero.h"
@@ -82,7 +84,67 @@ struct WhisperConfig {
     std::string initial_prompt;      // whisper_full_params.initial_prompt: tokenised with whisper.cpp's tokenizer (nothing is put in front of it), in front of every segment's context
     bool carry_context = false;      // whisper_full_params.no_context = false: the text of this instance's segment n conditions its segment n + 1
     uint32_t input_sample_rate = 16000; std::string input_resample_mode = "linear";   // linear (the audio::resampler node's rubato arithmetic, bit for bit) | polyphase
+    // Decoding constraints of this instance's segments (skw_full_batch_rules): repetition_penalty, no_repeat_ngram_size, and suppress_tokens (a -inf bias each) + logit_bias as the
+    // record's pairs, at most SKW_BIAS_MAX distinct ids together.  The default record asks for nothing.  max_suppress_id / max_bias_id: the largest id each key named (-1: none),
+    // so that the check against the loaded model's vocabulary can name the key
+    skw_decode_rules rules; int max_suppress_id = -1, max_bias_id = -1;
+    WhisperConfig() { skw_decode_rules_set_default(&rules); }
 };
+
+// repetition_penalty, no_repeat_ngram_size, suppress_tokens, logit_bias -> cfg->rules; every refusal names its key
+bool parse_decode_rules(const skw::JsonValue& v, WhisperConfig* cfg, std::string* err) {
+    skw_decode_rules& r = cfg->rules;
+    auto bad = [&](const std::string& m) { *err = "Invalid config: " + m; return false; };
+    auto whole = [](const skw::JsonValue& x, double lo, double hi) { return x.type == skw::JsonValue::Number && x.num == std::floor(x.num) && x.num >= lo && x.num <= hi; };
+    if (const skw::JsonValue* x = v.get("repetition_penalty")) {
+        if (x->type != skw::JsonValue::Number || !std::isfinite((float)x->num) || !((float)x->num > 0.0f)) return bad("repetition_penalty must be a number > 0 (1.0 = off)");
+        r.repetition_penalty = (float)x->num;
+    }
+    if (const skw::JsonValue* x = v.get("no_repeat_ngram_size")) {
+        if (!whole(*x, 0, 1e6)) return bad("no_repeat_ngram_size must be an integer >= 0 (0 = off)");
+        r.no_repeat_ngram_size = (int32_t)x->num;
+    }
+    // suppression first, then the biases: an id under both keys is suppressed (x + b, then -inf, is -inf)
+    auto add = [&](const char* key, int id, float b) {
+        for (int k = 0; k < r.n_bias; ++k) if (r.bias_id[k] == id) {
+            if (std::isinf(r.bias[k]) && !std::isinf(b)) return true;
+            if (std::isinf(b)) return true;      // (listed twice under suppress_tokens: once is enough)
+            return bad(std::string(key) + ": token id " + std::to_string(id) + " is given twice");
+        }
+        if (r.n_bias >= SKW_BIAS_MAX) return bad("suppress_tokens and logit_bias together allow at most " + std::to_string(SKW_BIAS_MAX) + " distinct token ids");
+        r.bias_id[r.n_bias] = id; r.bias[r.n_bias] = b; ++r.n_bias;
+        return true;
+    };
+    if (const skw::JsonValue* x = v.get("suppress_tokens")) {
+        if (x->type != skw::JsonValue::Array) return bad("suppress_tokens must be an array of token ids");
+        for (const skw::JsonValue& e : x->arr) {
+            if (!whole(e, 0, 1e9)) return bad("suppress_tokens must be an array of token ids (integers >= 0)");
+            if (!add("suppress_tokens", (int)e.num, -INFINITY)) return false;
+            cfg->max_suppress_id = std::max(cfg->max_suppress_id, (int)e.num);
+        }
+    }
+    if (const skw::JsonValue* x = v.get("logit_bias")) {
+        if (x->type != skw::JsonValue::Array) return bad("logit_bias must be an array of [token id, bias] pairs");
+        for (const skw::JsonValue& e : x->arr) {
+            if (e.type != skw::JsonValue::Array || e.arr.size() != 2 || !whole(e.arr[0], 0, 1e9) || e.arr[1].type != skw::JsonValue::Number || !std::isfinite((float)e.arr[1].num))
+                return bad("logit_bias must be an array of [token id, bias] pairs (an integer >= 0 and a finite number; suppress_tokens is the -inf bias)");
+            if (!add("logit_bias", (int)e.arr[0].num, (float)e.arr[1].num)) return false;
+            cfg->max_bias_id = std::max(cfg->max_bias_id, (int)e.arr[0].num);
+        }
+    }
+    return true;
+}
+// the ids against the loaded model's vocabulary (create_instance and update_params, once the engine is known)
+bool check_rule_ids(const WhisperConfig& cfg, int n_vocab, std::string* err) {
+    for (int pass = 0; pass < 2; ++pass) {
+        const int mx = pass ? cfg.max_bias_id : cfg.max_suppress_id;
+        if (mx >= n_vocab) { *err = std::string("Invalid config: ") + (pass ? "logit_bias" : "suppress_tokens") + ": token id " + std::to_string(mx) + " outside the model's vocabulary [0, " +
+                                    std::to_string(n_vocab) + ")"; return false; }
+    }
+    char e[512];
+    if (!skw_decode_rules_check(&cfg.rules, n_vocab, "decoding rules", e, sizeof e)) { *err = std::string("Invalid config: ") + e; return false; }      // (nothing the parser lets through)
+    return true;
+}
 
 bool parse_config(const char* json, WhisperConfig* cfg, std::string* err) {
     if (!json || !*json) return true;
@@ -136,7 +198,7 @@ bool parse_config(const char* json, WhisperConfig* cfg, std::string* err) {
     d = cfg->max_batch; if (!num("max_batch", &d)) return false; cfg->max_batch = std::max(1, (int)d);
     if (!boo("use_gpu", &cfg->use_gpu) || !boo("suppress_blank", &cfg->suppress_blank) || !boo("suppress_non_speech_tokens", &cfg->suppress_non_speech_tokens) ||
         !boo("emit_vad_events", &cfg->emit_vad_events) || !boo("flush_tail", &cfg->flush_tail) || !boo("mixed_batch", &cfg->mixed_batch) || !boo("carry_context", &cfg->carry_context)) return false;
-    return true;
+    return parse_decode_rules(v, cfg, err);
 }
 
 // ------------------------------------------------------------------ shared engine: model cache + batch scheduler
@@ -171,6 +233,8 @@ struct Job {
     // first one back); without it the job takes no part in a context call
     int32_t ctx[SKW_CONTEXT_WORDS] = {0}; bool want_ctx = false;
     int32_t* context() { return want_ctx ? ctx : nullptr; }
+    skw_decode_rules rules; bool constrained = false;      // the owning instance's decoding constraints when the segment was queued; constrained: they are not the default record
+    const skw_decode_rules* decode_rules() const { return constrained ? &rules : nullptr; }
     void set_samples(const std::vector<float>& v) {
         n = v.size(); pinned = PinnedPool::get().acquire(n);
         if (pinned.p) memcpy(pinned.p, v.data(), n * sizeof(float)); else pcm_pageable = v;      // (no page-locked memory to be had: the ordinary copy path)
@@ -179,7 +243,7 @@ struct Job {
     ~Job() { PinnedPool::get().release(pinned); }
 };
 std::atomic<long> g_engine_calls{0}, g_batch_jobs{0}, g_mixed_calls{0};      // skw_whisper_plugin_batch_stats
-std::atomic<long> g_context_calls{0};                                        // skw_whisper_plugin_context_stats: engine calls that carried at least one context
+std::atomic<long> g_context_calls{0}, g_rules_calls{0};                                        // skw_whisper_plugin_context_stats: engine calls that carried at least one context
 struct SharedEngine {
     skw_model* model = nullptr;
     skw_ctx* ctx = nullptr;
@@ -190,6 +254,7 @@ struct SharedEngine {
     bool multilingual = true;   // the model has language tokens (n_vocab >= 51865); set once at load
     int n_audio_ctx = 1500;     // the model's encoder positions (what audio_ctx "auto" is capped at); set once at load
     int n_text_ctx = 448;       // the model's decoder positions (a prompt takes at most half of them); set once at load
+    int n_vocab = 51865;        // the model's vocabulary (what suppress_tokens / logit_bias ids are checked against); set once at load
     bool mixed = true;          // scheduler: jobs join a batch whatever their parameters (mixed_batch of the instance created most recently; under mu)
     int precision = SKW_PRECISION_EXACT;
     static const int kMaxSamples = 16000 * 121;   // schema maximum of max_segment_duration_secs (120 s) + one VAD frame of slack: no segment is longer
@@ -248,7 +313,8 @@ struct SharedEngine {
                 while ((int)queue.size() < batch_limit && !stop) { if (cv.wait_until(l, deadline) == std::cv_status::timeout) break; }
                 while (!queue.empty() && (int)batch.size() < batch_limit) {
                     // arrival order, whatever the jobs' params: every row of skw_full_batch_mixed decodes under its own.  mixed_batch: false cuts at the first job that differs
-                    if (!mixed && !batch.empty() && memcmp(&batch[0]->params, &queue.front()->params, sizeof(skw_full_params)) != 0) break;
+                    if (!mixed && !batch.empty() && (memcmp(&batch[0]->params, &queue.front()->params, sizeof(skw_full_params)) != 0 ||
+                                                     memcmp(&batch[0]->rules, &queue.front()->rules, sizeof(skw_decode_rules)) != 0)) break;      // (and where the rules differ)
                     batch.push_back(queue.front()); queue.pop_front();
                 }
             }
@@ -267,19 +333,27 @@ struct SharedEngine {
                     std::vector<int32_t*> cxs(n); bool any_ctx = false;
                     for (int i = 0; i < n; ++i) { cxs[i] = batch[i]->context(); any_ctx = any_ctx || cxs[i] != nullptr; }
                     // (jobs that all share one parameter block run the uniform call: the same launches as before mixed batches existed)
-                    rc = any_ctx ? skw_full_batch_context(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), cxs.data(), res.data())
+                    // decoding constraints: a batch in which some job has them is ONE rules call (jobs without hand in NULL: their rows are the context call's); otherwise as before
+                    std::vector<const skw_decode_rules*> rls(n); bool any_rules = false, rules_differ = false;
+                    for (int i = 0; i < n; ++i) { rls[i] = batch[i]->decode_rules(); any_rules = any_rules || rls[i] != nullptr;
+                                                  rules_differ = rules_differ || memcmp(&batch[0]->rules, &batch[i]->rules, sizeof(skw_decode_rules)) != 0; }
+                    rc = any_rules ? skw_full_batch_rules(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), any_ctx ? cxs.data() : nullptr, rls.data(), res.data())
+                       : any_ctx ? skw_full_batch_context(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), cxs.data(), res.data())
                        : differ ? skw_full_batch_mixed(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), res.data())
                                 : skw_full_batch_rng(ctx, &pv[0], ptrs.data(), ns.data(), n, 0, rngs.data(), res.data());
                     g_engine_calls.fetch_add(1); g_batch_jobs.fetch_add(n); if (differ) g_mixed_calls.fetch_add(1); if (any_ctx) g_context_calls.fetch_add(1);
+                    if (any_rules) g_rules_calls.fetch_add(1);
                     if (rc == 0) for (int i = 0; i < n; ++i) batch[i]->result = res[i]; else why = skw_ctx_last_error(ctx);
-                    if (rc != 0 && differ) {
+                    if (rc != 0 && (differ || rules_differ)) {
                         // A refusal must stay with the request that earned it: jobs of differently configured instances share this call, and one of them being refused
                         // (the engine fails the whole call and hands no generator state back) is no reason for the others to fail.  Each job again, alone, under its own
                         // parameters; every job gets its own outcome.  (Jobs with equal blocks share their configuration, and shared the call before mixed batches too.)
                         for (int i = 0; i < n; ++i) {
                             skw_result one{}; const float* pp = ptrs[i]; uint32_t* rg = rngs[i];
                             int32_t* cx = cxs[i];      // (the refused call wrote no context back: each job's own, as it was queued)
-                            int r1 = cx ? skw_full_batch_context(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &cx, &one) : skw_full_batch_rng(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &one);
+                            const skw_decode_rules* rl = rls[i];
+                            int r1 = rl ? skw_full_batch_rules(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, cx ? &cx : nullptr, &rl, &one)
+                                   : cx ? skw_full_batch_context(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &cx, &one) : skw_full_batch_rng(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &one);
                             g_engine_calls.fetch_add(1);
                             if (r1 == 0) batch[i]->result = one;
                             else { try { batch[i]->error = skw_ctx_last_error(ctx); } catch (const std::exception&) { r1 = -1; } }      // (a promise is satisfied once)
@@ -403,7 +477,8 @@ std::shared_ptr<SharedEngine> get_engine(const WhisperConfig& cfg, WhisperPlugin
     eng->model = skw_model_load(cfg.model_path.c_str(), cfg.gpu_device, ebuf, sizeof ebuf);
     if (!eng->model) { *err = ebuf[0] ? ebuf : ("Failed to load Whisper model from '" + cfg.model_path + "'"); return nullptr; }
     g_model_loads.fetch_add(1);
-    { skw_hparams hp{}; skw_model_get_hparams(eng->model, &hp); eng->multilingual = hp.n_vocab >= 51865; eng->n_audio_ctx = hp.n_audio_ctx; eng->n_text_ctx = hp.n_text_ctx; }
+    { skw_hparams hp{}; skw_model_get_hparams(eng->model, &hp); eng->multilingual = hp.n_vocab >= 51865; eng->n_audio_ctx = hp.n_audio_ctx; eng->n_text_ctx = hp.n_text_ctx;
+      eng->n_vocab = hp.n_vocab; }
     const auto t1 = std::chrono::steady_clock::now();
     eng->batch_limit = cfg.max_batch;
     eng->window_ms = cfg.batch_window_ms; eng->mixed = cfg.mixed_batch;
@@ -550,6 +625,7 @@ bool transcribe_and_emit(WhisperPlugin* self, const Emit& em, const skw::Segment
     // (additive) the segment's audio context: what its instance is configured for now (update_params takes effect from the next segment); "auto" = the exported rule on its length
     job->params.audio_ctx = self->config.audio_ctx_auto ? skw_audio_ctx_for_samples((int)job->n, self->engine->n_audio_ctx) : self->config.audio_ctx;
     job->rng = self->rng;
+    job->rules = self->config.rules; job->constrained = !skw_decode_rules_is_default(&job->rules);      // (additive) what the instance is configured for now, like audio_ctx
     build_job_context(self, job->ctx); job->want_ctx = self->config.carry_context || job->ctx[0] > 0;
     if ((int)job->n > SharedEngine::kMaxSamples) { *err = "Whisper inference failed: segment longer than the engine workspace"; return false; }
     std::future<int> fut = job->done.get_future();
@@ -624,6 +700,10 @@ const char* const kSchema =
     "\"mixed_batch\":{\"type\":\"boolean\",\"description\":\"(additive) segments of instances with different language / suppress_* settings share one GPU batch; false cuts a batch at the first differing job\",\"default\":true},"
     "\"initial_prompt\":{\"type\":\"string\",\"description\":\"(additive) whisper.cpp's initial_prompt: text (domain vocabulary, spellings) every segment is decoded behind; tokenised with whisper.cpp's tokenizer, which puts nothing in front of it (start it with a space to match openai's reference); at most half the model's text context (224 tokens), longer prompts keep their end\",\"default\":\"\"},"
     "\"carry_context\":{\"type\":\"boolean\",\"description\":\"(additive) whisper.cpp's no_context = false: the text of this instance's previous segment conditions the next one; cleared when model_path, language or initial_prompt change\",\"default\":false},"
+    "\"repetition_penalty\":{\"type\":\"number\",\"description\":\"(additive) repetition penalty on the text tokens the current window has already produced (timestamps and the prompt are exempt): a logit x becomes x / p when positive, x * p when negative, once per distinct token; 1.0 = off. As in faster-whisper / transformers\",\"default\":1.0,\"exclusiveMinimum\":0.0},"
+    "\"no_repeat_ngram_size\":{\"type\":\"integer\",\"description\":\"(additive) no n-gram of this many text tokens occurs twice within a window (timestamps in between are skipped); 0 = off\",\"default\":0,\"minimum\":0},"
+    "\"suppress_tokens\":{\"type\":\"array\",\"items\":{\"type\":\"integer\",\"minimum\":0},\"description\":\"(additive) token ids that are never produced (the id-level form of whisper.cpp's suppress_regex); with logit_bias at most 256 distinct ids, each below the model's vocabulary size\",\"default\":[]},"
+    "\"logit_bias\":{\"type\":\"array\",\"items\":{\"type\":\"array\",\"minItems\":2,\"maxItems\":2},\"description\":\"(additive) [token id, bias] pairs: the bias is added to the token's logit at every sampling decision; an id also under suppress_tokens stays suppressed. Segments with different decoding rules share a batch\",\"default\":[]},"
     "\"flush_tail\":{\"type\":\"boolean\",\"description\":\"(additive) transcribe buffered speech when the input stream ends (the reference drops it)\",\"default\":false},"
     "\"input_sample_rate\":{\"type\":\"integer\",\"description\":\"(additive) sample rate of the mono f32 packets fed to this node; anything but 16000 is resampled to 16 kHz on the GPU with the audio::resampler node's arithmetic (chunk_frames 960) before VAD segmentation\",\"default\":16000,\"minimum\":1000,\"maximum\":768000},"
     "\"input_resample_mode\":{\"type\":\"string\",\"description\":\"(additive) linear (rubato FastFixedIn/Linear, bit for bit what audio::resampler gives) | polyphase (Kaiser-windowed sinc)\",\"default\":\"linear\"}"
@@ -649,6 +729,7 @@ CPluginHandle create_instance_impl(const char* params, CLogCallback log_cb, void
     resolve_auto_device(&p->config);
     p->hold(get_engine(p->config, p.get(), &err));
     if (!p->engine) { p->log(SK_LOG_ERROR, "%s", err.c_str()); return nullptr; }
+    if (!check_rule_ids(p->config, p->engine->n_vocab, &err)) { p->log(SK_LOG_ERROR, "%s", err.c_str()); return nullptr; }
     p->vad = make_vad(p->config, p.get(), &err);
     if (!p->vad) { p->log(SK_LOG_ERROR, "%s", err.c_str()); return nullptr; }
     p->seg.configure(p->config.vad_threshold, p->config.min_silence_duration_ms, p->config.max_segment_duration_secs);
@@ -718,8 +799,9 @@ CResult plugin_update_params(CPluginHandle handle, const char* params) {
         if (nc.model_path != self->config.model_path || nc.precision != self->config.precision || nc.use_gpu != self->config.use_gpu || nc.gpu_device != self->config.gpu_device) {
             auto eng = get_engine(nc, self, &err);
             if (!eng) return err_result("Failed to reload Whisper model: " + err);
+            if (!check_rule_ids(nc, eng->n_vocab, &err)) return err_result(err);      // (before the instance lets go of the engine it has)
             self->hold(eng);
-        }
+        } else if (!check_rule_ids(nc, self->engine->n_vocab, &err)) return err_result(err);
         if (nc.vad_model_path != self->config.vad_model_path || nc.vad_threshold != self->config.vad_threshold || nc.vad_mode != self->config.vad_mode || nc.vad_device != self->config.vad_device ||
             (nc.vad_device == "gpu" && nc.gpu_device != self->config.gpu_device)) {
             auto v = make_vad(nc, self, &err);
@@ -779,6 +861,18 @@ extern "C" void skw_whisper_plugin_batch_stats(long* engine_calls, long* jobs, l
 }
 // additive, for tests: engine calls that carried at least one context (skw_full_batch_context); a process whose instances set neither initial_prompt nor carry_context stays at 0
 extern "C" void skw_whisper_plugin_context_stats(long* context_calls) { if (context_calls) *context_calls = g_context_calls.load(); }
+// additive, for tests: engine calls that carried at least one job with decoding constraints (skw_full_batch_rules); a process whose instances set none of the four keys stays at 0
+extern "C" void skw_whisper_plugin_rules_stats(long* rules_calls) { if (rules_calls) *rules_calls = g_rules_calls.load(); }
+// additive, for tests: the node's own parsing of repetition_penalty / no_repeat_ngram_size / suppress_tokens / logit_bias out of a parameter object, and the check of the ids against
+// a vocabulary of n_vocab entries (what create_instance and update_params apply once the model is known).  0 and the record, or -1 and the message.  No GPU is touched.
+extern "C" int skw_whisper_plugin_parse_rules(const char* params_json, int n_vocab, skw_decode_rules* out, char* err, size_t errlen) {
+    try {
+        WhisperConfig cfg; std::string e;
+        if (!parse_config(params_json, &cfg, &e) || !check_rule_ids(cfg, n_vocab, &e)) { snprintf(err, errlen, "%s", e.c_str()); return -1; }
+        if (out) *out = cfg.rules;
+        return 0;
+    } catch (const std::exception& ex) { snprintf(err, errlen, "%s", ex.what()); return -1; }
+}
 // additive, for tests: cached engines (models resident), how many of them hold a batch workspace right now, and live plugin instances over all of them
 extern "C" void skw_whisper_plugin_workspace_stats(int* engines, int* workspaces, int* instances) {
     EngineCache& cache = engine_cache();

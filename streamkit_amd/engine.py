@@ -26,6 +26,72 @@ class FullParams(C.Structure):
                 ("audio_ctx", C.c_int32)]      # 0 = the model's n_audio_ctx; K: the clip is encoded and attended over K positions (whisper_full_params.audio_ctx)
 
 
+BIAS_MAX = 256      # SKW_BIAS_MAX
+
+
+class DecodeRules(C.Structure):
+    """skw_decode_rules: a clip's decoding constraints, applied to the logits of every sampling decision ahead of the sampler (include/skw_engine.h) —
+    bias (+ suppression as a -inf bias), then the repetition penalty over the pass's distinct text tokens, then the no-repeat n-gram ban.
+    DecodeRules(repetition_penalty=1.1, no_repeat_ngram_size=3, bias={id: b}, suppress=[ids]); no argument: the default record (1.0, 0, no pairs), which asks for nothing."""
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32), ("n_bias", C.c_int32), ("pad", C.c_int32),
+                ("bias_id", C.c_int32 * BIAS_MAX), ("bias", C.c_float * BIAS_MAX)]
+
+    def __init__(self, repetition_penalty=1.0, no_repeat_ngram_size=0, bias=None, suppress=None):
+        super().__init__()
+        self.repetition_penalty = float(repetition_penalty)
+        self.no_repeat_ngram_size = _as_int32(no_repeat_ngram_size, "no_repeat_ngram_size")
+        pairs = [(int(i), float(b)) for i, b in (bias.items() if hasattr(bias, "items") else (bias or ()))]
+        pairs += [(int(i), float("-inf")) for i in (suppress or ())]
+        if len(pairs) > BIAS_MAX:
+            raise ValueError("DecodeRules: %d biased / suppressed ids, at most %d" % (len(pairs), BIAS_MAX))
+        self.n_bias = len(pairs)
+        for k, (i, b) in enumerate(pairs):
+            self.bias_id[k] = _as_int32(i, "bias id")
+            self.bias[k] = b
+
+    def is_default(self):
+        return self.repetition_penalty == 1.0 and self.no_repeat_ngram_size == 0 and self.n_bias == 0
+
+    def check(self, n_vocab, who="rules"):
+        """The engine's own validation (skw_decode_rules_check), restated so that it needs no device: raises ValueError naming `who`"""
+        t = self.repetition_penalty
+        if not (np.isfinite(t) and t > 0.0):
+            raise ValueError("%s: repetition_penalty %r must be finite and > 0 (1 = off)" % (who, t))
+        if self.no_repeat_ngram_size < 0:
+            raise ValueError("%s: no_repeat_ngram_size %d must be >= 0 (0 = off)" % (who, self.no_repeat_ngram_size))
+        if not 0 <= self.n_bias <= BIAS_MAX:
+            raise ValueError("%s: n_bias %d outside [0, %d]" % (who, self.n_bias, BIAS_MAX))
+        seen = set()
+        for k in range(self.n_bias):
+            i, b = self.bias_id[k], self.bias[k]
+            if not 0 <= i < n_vocab:
+                raise ValueError("%s: bias %d: token id %d outside [0, %d)" % (who, k, i, n_vocab))
+            if i in seen:
+                raise ValueError("%s: bias %d: token id %d is given twice" % (who, k, i))
+            seen.add(i)
+            if np.isnan(b) or b == float("inf"):
+                raise ValueError("%s: bias %d (token %d): %r is not finite or -inf" % (who, k, i, b))
+
+
+def _as_int32(v, what):
+    v = int(v)
+    if not -2**31 <= v < 2**31:
+        raise ValueError("DecodeRules: %s %d does not fit an int32" % (what, v))
+    return v
+
+
+def rules_array(rules, n, n_vocab, who):
+    """[DecodeRules | None] * n -> (the checked records kept alive, (c_void_p * n) of their addresses, NULL where None)"""
+    if len(rules) != n:
+        raise ValueError("%d rule records for %d %ss" % (len(rules), n, who))
+    for i, r in enumerate(rules):
+        if r is not None:
+            if not isinstance(r, DecodeRules):
+                raise ValueError("%s %d: rules must be DecodeRules or None" % (who, i))
+            r.check(n_vocab, "%s %d" % (who, i))
+    return list(rules), (C.c_void_p * n)(*[None if r is None else C.addressof(r) for r in rules])
+
+
 class Segment(C.Structure):
     _fields_ = [("t0", C.c_int64), ("t1", C.c_int64), ("tok_begin", C.c_int32), ("tok_end", C.c_int32),
                 ("text_off", C.c_int32), ("text_len", C.c_int32)]
@@ -93,7 +159,12 @@ def lib():
         L.skw_full_batch_mixed.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(Result)]
         L.skw_full_batch_context.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                              C.POINTER(C.c_void_p), C.POINTER(Result)]
-        L.skw_model_tokenize.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int]
+        L.skw_decode_rules_default.argtypes = [C.POINTER(DecodeRules)]
+        L.skw_full_batch_rules.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(Result)]
+        L.skw_debug_sample_rows_rules.argtypes = [C.c_void_p, C.POINTER(FullParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(C.c_void_p)]
+        L.skw_model_tokenize.argtypes =[C.c_void_p, C.c_char_p, C.c_void_p, C.c_int]
         L.skw_debug_set_prompt_pass.argtypes = [C.c_void_p, C.c_int]
         L.skw_debug_set_prompt_xattn_mq.argtypes = [C.c_void_p, C.c_int]
         L.skw_debug_xattn_exact.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
@@ -265,7 +336,7 @@ class Context:
         lib().skw_full_default_params(C.byref(p))
         return p
 
-    def full_batch(self, clips, params=None, device_ptrs=None, n_samples=None, trace=False, forced=None, rng_states=None, contexts=None):
+    def full_batch(self, clips, params=None, device_ptrs=None, n_samples=None, trace=False, forced=None, rng_states=None, contexts=None, rules=None):
         """clips: list of 1-D float32 numpy arrays (host), or device_ptrs + n_samples for HBM-resident PCM.
         trace=True (or forced=[per-clip int32 id sequences]): skw_full_batch_traced — returns (results, traces), traces[i] a structured
         array (TRACE_DT) with one record per sampling decision of clip i; with `forced` the decoder is fed those ids (teacher forcing).
@@ -275,8 +346,16 @@ class Context:
         forcing takes one FullParams and no rng_states: either combination raises ValueError.
         contexts=[int32[513] or None per clip] (context_new()): skw_full_batch_context — each clip decodes behind its owner's carried text (prompt_past: [0] = n, then n ids,
         an initial prompt's tokens in front) and the array is updated in place to what the call leaves, like rng_states.  One FullParams is repeated per clip.  With trace / forced:
-        skw_full_batch_traced_context."""
+        skw_full_batch_traced_context.
+        rules=[DecodeRules or None per clip]: skw_full_batch_rules — each clip's decoding constraints (repetition penalty, no-repeat n-gram, bias / suppression); None or a default
+        record leaves the clip as it is without.  May be combined with per-clip params, rng_states and contexts; with trace / forced it raises ValueError.  The records are checked
+        here as the engine checks them (ValueError naming the clip)."""
         per_clip = isinstance(params, (list, tuple))
+        if rules is not None:
+            if trace or forced is not None:
+                raise ValueError("full_batch: rules cannot be combined with trace / forced (there is no traced entry point with decoding constraints)")
+            n_in = len(device_ptrs) if device_ptrs is not None else len(clips)
+            rules_keep, rules_ptr = rules_array(rules, n_in, self.model.hp.n_vocab, "clip")
         if trace or forced is not None:      # (checked before anything touches the library or the device)
             if per_clip:
                 raise ValueError("full_batch: trace / forced take one FullParams, not a list (tracing with per-clip parameters is not supported)")
@@ -303,7 +382,14 @@ class Context:
                 raise ValueError("full_batch: %d contexts for %d clips" % (len(contexts), n))
             assert all(x is None or (x.dtype == np.int32 and x.size == CONTEXT_WORDS and x.flags["C_CONTIGUOUS"]) for x in contexts)
             cp = (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in contexts])
-        if contexts is not None and not (trace or forced is not None):
+        if rules is not None:
+            sp = None
+            if rng_states is not None:
+                assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
+                sp = (C.c_void_p * n)(*[None if s is None else s.ctypes.data for s in rng_states])
+            pp = p if per_clip else (FullParams * n)(*([p] * n))
+            self._check(lib().skw_full_batch_rules(self.h, pp, ptrs, ns, n, on_dev, sp, cp, rules_ptr, res))
+        elif contexts is not None and not (trace or forced is not None):
             sp = None
             if rng_states is not None:
                 assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
@@ -359,7 +445,7 @@ class Context:
 
     def profile_get(self):
         out = {}
-        for cls in range(9):
+        for cls in range(10):
             name = C.create_string_buffer(64); cnt = C.c_long(); ms = C.c_double(); fl = C.c_double(); by = C.c_double()
             if lib().skw_ctx_profile_get(self.h, cls, name, 64, C.byref(cnt), C.byref(ms), C.byref(fl), C.byref(by)) == 0:
                 out[name.value.decode()] = dict(count=cnt.value, ms=ms.value, flops=fl.value, bytes=by.value)
@@ -437,13 +523,16 @@ class Context:
         self._check(lib().skw_decode_logits(self.h, t.ctypes.data, t.size, out.ctypes.data))
         return out
 
-    def sample_rows(self, hists, logits, params=None, form=0, want_filtered=False):
+    def sample_rows(self, hists, logits, params=None, form=0, want_filtered=False, rules=None):
         """K11 on its own (skw_debug_sample_rows): one sampler launch decides the next token of len(hists) decoders whose sampled tokens so far are
         hists[r], on caller-supplied logits [rows][n_vocab].  form 0: the decode step's sampler; 1: the streaming kernel (leaves the filtered row
         in memory: want_filtered).  -> (tokens structured array, trace records, filtered logits or None)
-        params=[FullParams per row]: the per-row form of the sampler (skw_debug_sample_rows_mixed) — every row under its own rules and its own static mask."""
+        params=[FullParams per row]: the per-row form of the sampler (skw_debug_sample_rows_mixed) — every row under its own rules and its own static mask.
+        rules=[DecodeRules or None per row]: skw_debug_sample_rows_rules — k_dec_constrain on the rows' logits, then the per-row form of the sampler."""
         per_row = isinstance(params, (list, tuple))
         R = len(hists)
+        if rules is not None:
+            rules_keep, rules_ptr = rules_array(rules, R, self.model.hp.n_vocab, "row")
         if per_row and len(params) != R:
             raise ValueError("sample_rows: %d parameter blocks for %d rows" % (len(params), R))
         p = (FullParams * R)(*params) if per_row else (params or self.default_params())
@@ -456,6 +545,10 @@ class Context:
         filt = np.empty_like(lg) if want_filtered else None
         toks = np.zeros(R, dtype=_TOKEN_DT)
         tr = np.zeros(R, dtype=TRACE_DT)
+        if rules is not None:
+            self._check(lib().skw_debug_sample_rows_rules(self.h, p if per_row else (FullParams * R)(*([p] * R)), R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
+                                                          filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data, rules_ptr))
+            return toks, tr, filt
         fn = lib().skw_debug_sample_rows_mixed if per_row else lib().skw_debug_sample_rows
         self._check(fn(self.h, p if per_row else C.byref(p), R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
                        filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data))
