@@ -2224,6 +2224,135 @@ extern "C" int skw_debug_gemm_q8(skw_ctx* c, int type, const uint8_t* blocks_hos
     cleanup();
     return 0;
 }
+// tests (tests/test_gpu_gemm16_epi.py): one product of the f16_mfma precision on host-supplied operands through the public launchers, so that the dispatch is part of what is tested,
+// with EVERY argument of the epilogues in the caller's hands — to be compared bit for bit with tests/gemm16_ref_lib.py.  Modelled on skw_debug_gemm_q8: the output buffers are the
+// caller's (C, and C2 / C3 for EPI_DEC_QKV: uploaded as given — the caller's sentinel with its margins — and read back after the launch), every index the launch can form is checked
+// against the buffer sizes here, BEFORE anything is launched (-1 and a message otherwise), kernel_id is what the launcher itself branches on (SkwGemm16Kernel), and -2 means the
+// launcher refuses the geometry (so a case never silently tests another kernel).
+//   launcher 0 / 1: skw_gemm16 with GEMM16W forced 1 / 0 in-process (k_gemm16w / k_gemm16), restored afterwards; 2: skw_gemm16_small; 3: skw_gemm16_small_lnA
+//   A: f16 bits, a_halves of them (rows at lda, or a_rows_per_batch / a_batch_stride; a_frag: the fragment-order image, pad rows M .. ceil16(M) included); launcher 3: ln_x [M][K],
+//   ln_w, ln_b [K] f32 instead.  W: [N][K] f16 bits in the order the kernel reads k; use_wf: the entry builds the fragment-order image itself (perm as the engine picks it: the
+//   kperm'ed-output epilogues).  res: separate [M][ldres] f32, or res_alias: C itself.  pos [M] (EPI_DEC_QKV) reaches the kernel as SkwSeqState::cur_pos with the real stride.
+//   force_small: probe bit 4 of the launcher — k_gemm16_small where the vocabulary kernel would apply.
+struct skw_gemm16_epi_args {
+    int32_t launcher, M, N, K, epi;
+    const uint16_t* A; int64_t a_halves, lda; int32_t a_rows_per_batch; int64_t a_batch_stride; int32_t a_frag;
+    const float *ln_x, *ln_w, *ln_b;
+    const uint16_t* W; int32_t use_wf;
+    const float* bias; const float* res; int64_t ldres; int32_t res_alias;
+    float scale; int32_t has_scale;
+    const float* pe; int32_t n_ctx, H, Tpad, frag, c_frag;
+    const int32_t* pos; int32_t force_small;
+    void* C; int64_t c_bytes, ldc; void* C2; void* C3; int64_t c2_bytes, ldc2;
+    int32_t kernel_id;      // out
+};
+extern "C" int skw_debug_gemm16_epi(skw_ctx* c, skw_gemm16_epi_args* p) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_gemm16_epi: %s", what); return -1; };
+    if (!p) return bad("no arguments");
+    const int M = p->M, N = p->N, K = p->K, epi = p->epi, L = p->launcher; const long ldc = p->ldc;
+    p->kernel_id = SKW_G16K_NONE;
+    if (L < 0 || L > 3 || M < 1 || M > 65536 || N < 1 || N > 65536 || K < 64 || K > 8192 || !p->W || !p->C || p->c_bytes < 1) return bad("bad geometry");
+    const bool big = L <= 1, lna = L == 3;
+    const bool f32out = epi == EPI_F32 || epi == EPI_CONV2;
+    const bool permo = epi == EPI_F16_KPERM || epi == EPI_GELU_F16_KPERM || epi == EPI_GELU_F16_KPERM_ROWPAD || epi == EPI_HEADS_F16;      // features stored in kperm order
+    const bool per_clip = epi == EPI_HEADS_F16 || epi == EPI_VT_F16 || epi == EPI_GELU_F16_KPERM_ROWPAD || epi == EPI_CONV2 || p->frag;
+    const long esz = f32out ? 4 : 2;
+    // ---- operands
+    if (big) {
+        if ((K & 63) || (N & 15) || (permo && (N & 31))) return bad("the big kernels take K % 64 == 0, N % 16 == 0 (N % 32 == 0 for kperm'ed outputs)");
+        if (p->a_frag || p->c_frag || p->ln_x || p->force_small || epi == EPI_DEC_QKV) return bad("a decode kernels' argument on a big-kernel launch");
+        if (!p->A || p->lda < 8 || (p->lda & 7) || (p->a_rows_per_batch ? (p->a_rows_per_batch < 1 || (p->a_batch_stride & 7) || p->a_batch_stride < 0) : p->lda < K)) return bad("A rows");
+        const long last = p->a_rows_per_batch ? (long)((M - 1) / p->a_rows_per_batch) * p->a_batch_stride + (long)std::min(M - 1, p->a_rows_per_batch - 1) * p->lda : (long)(M - 1) * p->lda;
+        if (last + K > p->a_halves) return bad("A too small for its rows");
+        if (ldc & (f32out ? 3 : 7)) return bad("ldc must keep 16-byte chunks aligned");
+    } else {
+        if ((K & 127)) return bad("the decode kernels take K % 128 == 0");
+        if (p->frag || p->a_rows_per_batch || per_clip) return bad("a big kernels' argument on a decode launch");
+        if (epi != EPI_F32 && epi != EPI_F16_PLAIN && epi != EPI_GELU_F16_KPERM && epi != EPI_DEC_QKV) return bad("an epilogue the decode kernels do not take");
+        if (epi != EPI_F32 && ((N & 15) || (ldc & 3))) return bad("the f16 epilogues store 8-byte groups: N % 16 == 0, ldc % 4 == 0");
+        if (epi == EPI_GELU_F16_KPERM && (N & 31)) return bad("kperm'ed outputs need N % 32 == 0");
+        if (p->c_frag && epi != EPI_GELU_F16_KPERM) return bad("c_frag is EPI_GELU_F16_KPERM's");
+        if (lna) {
+            if (!p->ln_x || !p->ln_w || !p->ln_b || p->a_frag || p->A) return bad("launcher 3 takes ln_x / ln_w / ln_b and no A");
+        } else {
+            if (!p->A || p->ln_x) return bad("launcher 2 takes A");
+            if (p->a_frag ? (long)((M + 15) & ~15) * K > p->a_halves : (p->lda < K || (p->lda & 7) || (long)(M - 1) * p->lda + K > p->a_halves)) return bad("A too small for its rows");
+        }
+    }
+    if (p->use_wf && ((N & 15) || (K & 31)) && big) return bad("a fragment-order image holds whole strips");
+    // ---- outputs: the last element each epilogue can reach
+    if (p->res_alias && (epi != EPI_F32 || p->res)) return bad("res_alias is EPI_F32's, and excludes a separate residual");
+    if (p->res && ((epi != EPI_F32 && !lna) || p->ldres < N || (big && (p->ldres & 3)))) return bad("residual rows");      // (launcher 3 takes none: given one, it must refuse)
+    const long B = (per_clip && p->n_ctx > 0) ? M / p->n_ctx : 0;
+    if (per_clip && (p->n_ctx < 1 || M % p->n_ctx)) return bad("M must be whole clips for this epilogue");
+    if (epi == EPI_HEADS_F16 || epi == EPI_VT_F16 || p->frag) {
+        if ((N & 63) || p->H != N / 64 || p->Tpad < p->n_ctx || (p->Tpad & 31) || B * p->H * p->Tpad * 64 * 2 > p->c_bytes) return bad("heads / V^T / fragment-order geometry");
+        if (p->frag && epi != EPI_F16_PLAIN && epi != EPI_VT_F16) return bad("frag is EPI_F16_PLAIN's and EPI_VT_F16's");
+    } else if (epi == EPI_GELU_F16_KPERM_ROWPAD) {
+        if (ldc < N || ((B * (p->n_ctx + 2) - 2) * ldc + N) * 2 > p->c_bytes) return bad("C too small for the padded rows");
+    } else if (epi == EPI_DEC_QKV) {
+        const int d = p->n_ctx;
+        if (d < 16 || (d & 15) || N != 3 * d || !p->pos || !p->C2 || !p->C3 || ldc < d || ((long)(M - 1) * ldc + d) * 2 > p->c_bytes || (p->ldc2 & 3) || !p->has_scale) return bad("q|k|v geometry");
+        for (int m = 0; m < M; ++m) if (p->pos[m] < 0 || ((long)m * p->ldc2 + (long)(p->pos[m] + 1) * d) * 2 > p->c2_bytes) return bad("a row's cache position lies outside C2 / C3");
+    } else if (p->c_frag) {
+        if ((long)((M + 15) & ~15) * N * 2 > p->c_bytes) return bad("C too small for the fragment-order image");
+    } else {
+        if (epi != EPI_F32 && epi != EPI_CONV2 && epi != EPI_F16_PLAIN && epi != EPI_F16_KPERM && epi != EPI_GELU_F16_KPERM) return bad("an epilogue skw_gemm16 does not take");
+        if (ldc < N || ((long)(M - 1) * ldc + N) * esz > p->c_bytes) return bad("C too small");
+    }
+    if (epi == EPI_CONV2 && (!p->pe || !p->bias)) return bad("EPI_CONV2 needs pe [n_ctx][N] and a bias");
+    if (p->res_alias && (ldc < N)) return bad("res_alias: C rows");
+    // ---- device copies
+    const bool perm = permo;                                  // the image's strip rows in the order of the epilogue that consumes the product, as the model loader picks it
+    half_t *dA = nullptr, *dW = nullptr, *dWf = nullptr; float *dx = nullptr, *dg = nullptr, *db = nullptr, *dbias = nullptr, *dres = nullptr, *dpe = nullptr;
+    void *dC = nullptr, *dC2 = nullptr, *dC3 = nullptr; SkwSeqState* dst = nullptr;
+    auto cleanup = [&]() {
+        hipFree(dA); hipFree(dW); hipFree(dWf); hipFree(dx); hipFree(dg); hipFree(db); hipFree(dbias); hipFree(dres); hipFree(dpe); hipFree(dC); hipFree(dC2); hipFree(dC3); hipFree(dst);
+    };
+    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_gemm16_epi: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
+    auto up = [&](auto** d, const void* h, size_t bytes) { return chk(hipMalloc((void**)d, bytes)) && chk(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice)); };
+    if (p->A && !up(&dA, p->A, (size_t)p->a_halves * 2)) return -1;
+    if (!up(&dW, p->W, (size_t)N * K * 2)) return -1;
+    if (lna && (!up(&dx, p->ln_x, (size_t)M * K * 4) || !up(&dg, p->ln_w, (size_t)K * 4) || !up(&db, p->ln_b, (size_t)K * 4))) return -1;
+    if (p->bias && !up(&dbias, p->bias, (size_t)N * 4)) return -1;
+    if (p->res && !up(&dres, p->res, (size_t)((long)(M - 1) * p->ldres + N) * 4)) return -1;
+    if (p->pe && !up(&dpe, p->pe, (size_t)p->n_ctx * N * 4)) return -1;
+    if (!up(&dC, p->C, (size_t)p->c_bytes)) return -1;
+    SkwGemmArgs a{}; a.A = dA; a.lda = p->lda; a.a_rows_per_batch = p->a_rows_per_batch; a.a_batch_stride = p->a_batch_stride; a.W = dW; a.ldw = K; a.M = M; a.N = N; a.K = K;
+    a.C = dC; a.ldc = ldc; a.bias = dbias; a.scale = p->scale; a.has_scale = p->has_scale; a.gelu_tab = c->m->gelu_tab; a.pe = dpe; a.n_ctx = p->n_ctx; a.H = p->H; a.Tpad = p->Tpad;
+    a.epi = epi; a.c_frag = p->c_frag; a.a_frag = p->a_frag; a.frag = p->frag; a.probe = p->force_small ? 16 : 0; a.ln_x = dx; a.ln_w = dg; a.ln_b = db;
+    if (p->res) { a.res = dres; a.ldres = p->ldres; }
+    if (p->res_alias) { a.res = (const float*)dC; a.ldres = ldc; }
+    if (epi == EPI_DEC_QKV) {
+        std::vector<SkwSeqState> st(M); memset((void*)st.data(), 0, sizeof(SkwSeqState) * M);
+        for (int m = 0; m < M; ++m) { st[m].active = 1; st[m].cur_pos = p->pos[m]; }
+        if (!up(&dst, st.data(), sizeof(SkwSeqState) * M) || !up(&dC2, p->C2, (size_t)p->c2_bytes) || !up(&dC3, p->C3, (size_t)p->c2_bytes)) return -1;
+        a.C2 = dC2; a.C3 = dC3; a.ldc2 = p->ldc2; a.pos_ptr = &dst[0].cur_pos; a.pos_stride = (int)(sizeof(SkwSeqState) / sizeof(int));
+    }
+    if (p->use_wf && !(N & 15)) {
+        if (!chk(hipMalloc((void**)&dWf, (size_t)N * K * 2))) return -1;
+        skw_make_wfrag(dW, K, N, K, perm ? 1 : 0, dWf, c->stream); a.Wf = dWf;
+    } else if (p->use_wf) {      // N % 16 != 0: no image exists for such a weight; a non-null Wf shows the launcher's refusal (the buffer is never read)
+        if (!chk(hipMalloc((void**)&dWf, (size_t)((N + 15) & ~15) * K * 2)) || !chk(hipMemset(dWf, 0, (size_t)((N + 15) & ~15) * K * 2))) return -1;
+        a.Wf = dWf;
+    }
+    (void)skw_sw(0);
+    bool ran = true;
+    if (big) {
+        const int w_was = g_sw_val[SW_GEMM16W];
+        g_sw_val[SW_GEMM16W] = L == 0 ? 1 : 0;
+        if (L == 0 && !skw_gemm16_takes_w(a)) ran = false;
+        else { p->kernel_id = skw_gemm16_kernel(a); skw_gemm16(a, c->stream); }
+        g_sw_val[SW_GEMM16W] = w_was;
+    } else if (L == 2) { p->kernel_id = skw_gemm16_small_kernel(a); ran = skw_gemm16_small(a, c->stream); }
+    else { p->kernel_id = skw_gemm16_small_lnA_kernel(a); ran = skw_gemm16_small_lnA(a, c->stream); }
+    if (!ran) { cleanup(); snprintf(errbuf, 512, "skw_debug_gemm16_epi: the launcher refuses these arguments"); return -2; }
+    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(p->C, dC, (size_t)p->c_bytes, hipMemcpyDeviceToHost))) return -1;
+    if (epi == EPI_DEC_QKV && (!chk(hipMemcpy(p->C2, dC2, (size_t)p->c2_bytes, hipMemcpyDeviceToHost)) || !chk(hipMemcpy(p->C3, dC3, (size_t)p->c2_bytes, hipMemcpyDeviceToHost)))) return -1;
+    cleanup();
+    return 0;
+}
 // tests: k_q8_quantize on host rows x [M][ldx] (ldx >= K, a multiple of 4): q int8 [M][K], dT / sT f32 [K/32][M]
 extern "C" int skw_debug_q8_quantize(skw_ctx* c, const float* x_host, long ldx, int M, int K, int8_t* q, float* dT, float* sT) {
     char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));

@@ -87,6 +87,14 @@ void skw_gemm(const SkwGemmArgs& a, hipStream_t s);
 void skw_gemm16(const SkwGemmArgs& a, hipStream_t s);
 bool skw_gemm16_takes_w(const SkwGemmArgs& a);      // true: skw_gemm16 launches k_gemm16w (weights from the fragment-order image a.Wf) for these arguments, false: k_gemm16
 bool skw_gemm16_small(const SkwGemmArgs& a, hipStream_t s);
+// The kernel each f16 launcher picks for these arguments — the functions the launchers themselves branch on (tests/test_gpu_gemm16_epi.py reports them per case).
+// LDS_256 / LDS_128: k_gemm16's tile; SMALL_16 / SMALL_64: k_gemm16_small's rows per workgroup; LNA_<NKW>_<NT>: k_gemm16_small_lnA's register form;
+// SKW_G16K_VOCAB + 100 MT + RD: k_gemm16_vocab<MT, RD>.  SKW_G16K_NONE: the launcher refuses the arguments (returns false, launches nothing).
+enum SkwGemm16Kernel : int { SKW_G16K_NONE = -1, SKW_G16K_W = 0, SKW_G16K_LDS_256, SKW_G16K_LDS_128, SKW_G16K_SMALL_16 = 10, SKW_G16K_SMALL_64,
+                             SKW_G16K_LNA_6_1 = 20, SKW_G16K_LNA_6_4, SKW_G16K_LNA_12_1, SKW_G16K_LNA_12_2, SKW_G16K_VOCAB = 1000 };
+int skw_gemm16_kernel(const SkwGemmArgs& a);
+int skw_gemm16_small_kernel(const SkwGemmArgs& a);
+int skw_gemm16_small_lnA_kernel(const SkwGemmArgs& a);
 // A = LayerNorm(ln_x [M][K] f32; ln_w, ln_b), statistics and normalisation inside the kernel from the rows it holds in registers; W in NATURAL k order
 bool skw_gemm16_small_lnA(const SkwGemmArgs& a, hipStream_t s);
 // slot_k (per-clip audio context; null: every slot has n_ctx positions): slot b attends over its first slot_k[b] keys with its first slot_k[b] queries; Tpad stays the stride

@@ -645,11 +645,17 @@ static bool gemm16w_ok(const SkwGemmArgs& a) {
     return skw_sw(SW_GEMM16W) && a.Wf && !(a.probe & 1023) && (a.K & 63) == 0 && (a.N & 15) == 0 && a.M >= 128;      // (probe bits 0-9 are k_gemm16's; 10+ this kernel's)
 }
 bool skw_gemm16_takes_w(const SkwGemmArgs& a) { return gemm16w_ok(a); }      // tests: which of the two kernels skw_gemm16 would launch for these arguments
+// k_gemm16's tile for these arguments: 256 x 256 when both extents fill it (V^T: the M axis is walked in virtual rows of Tpad per clip)
+static bool gemm16_big_tile(const SkwGemmArgs& a) {
+    const int Mv = a.epi == EPI_VT_F16 ? (a.M / a.n_ctx) * a.Tpad : a.M;
+    return Mv >= 256 && a.N >= 256 && Mv % 256 == 0 && a.N % 256 == 0;
+}
+int skw_gemm16_kernel(const SkwGemmArgs& a) { return gemm16w_ok(a) ? SKW_G16K_W : gemm16_big_tile(a) ? SKW_G16K_LDS_256 : SKW_G16K_LDS_128; }
 template <int EPI> static void launch_gemm16(const SkwGemmArgs& a_in, hipStream_t s) {
     // tile choice: 256 x 256 (8 waves, one workgroup per CU) when both extents fill it, 128 x 128 (4 waves, two per CU) otherwise;
     // persistent workgroups: one grid slot per resident workgroup (rounded to the 8 XCDs), each walks tile ids slot, slot + grid, ...
     const int Mv = Epi16<EPI>::X_IS_M ? (a_in.M / a_in.n_ctx) * a_in.Tpad : a_in.M;
-    const bool big = Mv >= 256 && a_in.N >= 256 && Mv % 256 == 0 && a_in.N % 256 == 0;
+    const bool big = gemm16_big_tile(a_in);
     const int cus = skw_cu_count() & ~7;
     const SkwGemmArgs& a = a_in;
     if (big && a.probe) { const int nblk = ((Mv + 255) / 256) * ((a.N + 255) / 256);
@@ -1144,20 +1150,32 @@ __global__ __launch_bounds__(256) void k_gemm16_small_lnA(SkwGemmArgs a) {
     for (int s = 1; s < NW; ++s) { const f32x4 o = red[s][w][lane]; v[0] = v[0] + o[0]; v[1] = v[1] + o[1]; v[2] = v[2] + o[2]; v[3] = v[3] + o[3]; }
     gemm16_small_finish<EPI>(a, my0 + ft * 16 + r16, n0 + 16 * fq + 4 * g, v, pre_res, pre_po);
 }
-template <int EPI> static bool launch_gemm16_small_lnA(const SkwGemmArgs& a, hipStream_t s) {
-    // Workgroup shape: its ingest is what bounds these kernels (one CU takes in ~70 GB/s).  x is f32 — twice the bytes of a ready-made f16 row — and every
-    // workgroup of a row block loads and normalises the same rows, so a workgroup takes 16 rows and NT strips: NT MFMAs per normalised fragment.
-    // four strips for the QKV and FC1 products (N >= 2048), one for the cross-attention query (measured: profiles/r03b/r03b_lnfold_v*.txt, r04i)
+// which register form of k_gemm16_small_lnA takes these arguments (SkwGemm16Kernel; SKW_G16K_NONE: none does).  The launcher below branches on this answer and on nothing else.
+// Workgroup shape: its ingest is what bounds these kernels (one CU takes in ~70 GB/s).  x is f32 — twice the bytes of a ready-made f16 row — and every
+// workgroup of a row block loads and normalises the same rows, so a workgroup takes 16 rows and NT strips: NT MFMAs per normalised fragment.
+// four strips for the QKV and FC1 products (N >= 2048), one for the cross-attention query (measured: profiles/r03b/r03b_lnfold_v*.txt, r04i)
+int skw_gemm16_small_lnA_kernel(const SkwGemmArgs& a) {
+    if ((a.K & 127) || !a.ln_x || !a.ln_w || !a.ln_b || a.res) return SKW_G16K_NONE;
+    if (a.Wf && (a.N & 15)) return SKW_G16K_NONE;      // a fragment-order image holds whole 16-feature strips only (skw_make_wfrag)
+    if (a.epi != EPI_F16_PLAIN && a.epi != EPI_GELU_F16_KPERM && a.epi != EPI_DEC_QKV) return SKW_G16K_NONE;
     const int nkw = a.K >> 7, nt = a.N >= 2048 ? 4 : 1;
+    if (nkw <= 6) return nt == 4 ? SKW_G16K_LNA_6_4 : SKW_G16K_LNA_6_1;
+    if (nkw <= 12) return nt == 4 ? SKW_G16K_LNA_12_2 : SKW_G16K_LNA_12_1;
+    return SKW_G16K_NONE;
+}
+template <int EPI> static bool launch_gemm16_small_lnA(const SkwGemmArgs& a, hipStream_t s) {
     const dim3 block(256);
 #define SKW_LNA(NKWV, NTV) do { hipLaunchKernelGGL((k_gemm16_small_lnA<EPI, 1, NKWV, NTV>), dim3((a.N + 16 * NTV - 1) / (16 * NTV), (a.M + 15) / 16), block, 0, s, a); return true; } while (0)
-    if (nkw <= 6) { if (nt == 4) SKW_LNA(6, 4); SKW_LNA(6, 1); }
-    if (nkw <= 12) { if (nt == 4) SKW_LNA(12, 2); SKW_LNA(12, 1); }
+    switch (skw_gemm16_small_lnA_kernel(a)) {
+        case SKW_G16K_LNA_6_4: SKW_LNA(6, 4);
+        case SKW_G16K_LNA_6_1: SKW_LNA(6, 1);
+        case SKW_G16K_LNA_12_2: SKW_LNA(12, 2);
+        case SKW_G16K_LNA_12_1: SKW_LNA(12, 1);
+        default: return false;
+    }
 #undef SKW_LNA
-    return false;
 }
 bool skw_gemm16_small_lnA(const SkwGemmArgs& a, hipStream_t s) {
-    if ((a.K & 127) || !a.ln_x || !a.ln_w || !a.ln_b || a.res) return false;
     switch (a.epi) {
         case EPI_F16_PLAIN: return launch_gemm16_small_lnA<EPI_F16_PLAIN>(a, s);
         case EPI_GELU_F16_KPERM: return launch_gemm16_small_lnA<EPI_GELU_F16_KPERM>(a, s);
@@ -1283,17 +1301,26 @@ template <int MT, int RD> static void launch_gemm16_vocab(const SkwGemmArgs& a, 
     // waves per workgroup: a workgroup walks ~12.7 strips = 6.4 strip pairs at Whisper-small's vocabulary; with four waves some take two pairs and some one
     launch_gemm16_vocab_n<MT, RD, 8>(a, s);      // eight: 21.0 us per launch against 22.5 with four (tools/dec_gemm_probe.py), same arithmetic per output
 }
-// plain f32 output with optional bias, no residual; false when the geometry is outside what it handles
-static bool skw_gemm16_vocab(const SkwGemmArgs& a, hipStream_t s) {
-    if (a.epi != EPI_F32 || a.res || (a.K & 127) || a.K > 2048) return false;
-    if (a.ln_x) return false;
+// The vocabulary kernel's form for these arguments: SKW_G16K_VOCAB + 100 MT + RD, or SKW_G16K_NONE when the geometry is outside what it handles (plain f32 output with
+// optional bias, no residual, ready-made f16 rows: it does not normalise its A operand).
+static int gemm16_vocab_kernel(const SkwGemmArgs& a) {
+    if (a.epi != EPI_F32 || a.res || (a.K & 127) || a.K > 2048 || a.ln_x) return SKW_G16K_NONE;
     const int nk = a.K >> 5;
-    const bool mt4 = 64 * (a.K * 2 + 16) <= 150 * 1024;                          // 64 rows of A in LDS (K <= 1024), else 32
+    const int mt = 64 * (a.K * 2 + 16) <= 150 * 1024 ? 4 : 2;                    // 64 rows of A in LDS (K <= 1024), else 32
+    const int rd = (nk == 24 || nk == 12) ? 12 : (nk == 32 || nk == 16) ? 16 : nk == 40 ? 20 : 4;      // small, tiny | medium, base | large
+    return SKW_G16K_VOCAB + 100 * mt + rd;
+}
+static bool skw_gemm16_vocab(const SkwGemmArgs& a, hipStream_t s) {
+    const int k = gemm16_vocab_kernel(a);
+    if (k == SKW_G16K_NONE) return false;
+    const bool mt4 = (k - SKW_G16K_VOCAB) / 100 == 4;
 #define SKW_VOCAB_RD(RDV) do { if (mt4) launch_gemm16_vocab<4, RDV>(a, s); else launch_gemm16_vocab<2, RDV>(a, s); return true; } while (0)
-    if (nk == 24 || nk == 12) SKW_VOCAB_RD(12);                                  // small, tiny
-    if (nk == 32 || nk == 16) SKW_VOCAB_RD(16);                                  // medium, base
-    if (nk == 40) SKW_VOCAB_RD(20);                                              // large
-    SKW_VOCAB_RD(4);
+    switch ((k - SKW_G16K_VOCAB) % 100) {
+        case 12: SKW_VOCAB_RD(12);
+        case 16: SKW_VOCAB_RD(16);
+        case 20: SKW_VOCAB_RD(20);
+        default: SKW_VOCAB_RD(4);
+    }
 #undef SKW_VOCAB_RD
 }
 
@@ -1305,12 +1332,23 @@ template <int EPI> static void launch_gemm16_small(const SkwGemmArgs& a, hipStre
     if (a.N >= 2048) hipLaunchKernelGGL((k_gemm16_small<EPI, 4, 4>), dim3((a.N + 15) / 16, (a.M + 63) / 64), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_gemm16_small<EPI, 1, 4>), dim3((a.N + 15) / 16, (a.M + 15) / 16), dim3(256), 0, s, a);
 }
+// the kernel skw_gemm16_small launches for these arguments (SkwGemm16Kernel); SKW_G16K_NONE: it refuses them.  skw_gemm16_small branches on this answer.
+int skw_gemm16_small_kernel(const SkwGemmArgs& a) {
+    if (a.K & 127) return SKW_G16K_NONE;
+    if (a.N >= 8192 && !(a.probe & 16)) { const int k = gemm16_vocab_kernel(a); if (k != SKW_G16K_NONE) return k; }
+    if (a.ln_x) return SKW_G16K_NONE;         // neither this kernel nor the vocabulary kernel normalises its A operand: that is skw_gemm16_small_lnA's
+    // a fragment-order image holds whole 16-feature strips only (skw_make_wfrag): the kernels would find the whole last strip of a ragged N out of the image's range.
+    // No weight of the engine has such an image (the model loader makes none when n_out % 16 != 0); refused here, not left to the hardware range check.
+    if (a.Wf && (a.N & 15)) return SKW_G16K_NONE;
+    if (a.epi != EPI_F32 && a.epi != EPI_F16_PLAIN && a.epi != EPI_GELU_F16_KPERM && a.epi != EPI_DEC_QKV) return SKW_G16K_NONE;
+    return a.N >= 2048 ? SKW_G16K_SMALL_64 : SKW_G16K_SMALL_16;
+}
 // f16-MFMA form of skw_gemm_smallm; returns false when the geometry is outside what it handles (K % 128 != 0): the caller then
 // launches the exact kernel, which handles everything.
 bool skw_gemm16_small(const SkwGemmArgs& a, hipStream_t s) {
-    if (a.K & 127) return false;
-    if (a.N >= 8192 && !(a.probe & 16) && skw_gemm16_vocab(a, s)) return true;
-    if (a.ln_x) return false;                 // only the vocabulary kernel (and skw_gemm16_small_lnA) normalise their A operand
+    const int k = skw_gemm16_small_kernel(a);
+    if (k == SKW_G16K_NONE) return false;
+    if (k >= SKW_G16K_VOCAB) return skw_gemm16_vocab(a, s);
     switch (a.epi) {
         case EPI_F32: launch_gemm16_small<EPI_F32>(a, s); return true;
         case EPI_F16_PLAIN: launch_gemm16_small<EPI_F16_PLAIN>(a, s); return true;

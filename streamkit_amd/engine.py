@@ -218,8 +218,22 @@ def lib():
                                          C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.POINTER(C.c_int)])
         L.skw_debug_q8_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.skw_debug_self_attn_q8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10
+        L.skw_debug_gemm16_epi.argtypes = [C.c_void_p, C.POINTER(Gemm16EpiArgs)]
         _LIB = L
     return _LIB
+
+
+class Gemm16EpiArgs(C.Structure):      # struct skw_gemm16_epi_args (skw_engine.hip)
+    _fields_ = [("launcher", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("epi", C.c_int32),
+                ("A", C.c_void_p), ("a_halves", C.c_int64), ("lda", C.c_int64), ("a_rows_per_batch", C.c_int32), ("a_batch_stride", C.c_int64), ("a_frag", C.c_int32),
+                ("ln_x", C.c_void_p), ("ln_w", C.c_void_p), ("ln_b", C.c_void_p),
+                ("W", C.c_void_p), ("use_wf", C.c_int32),
+                ("bias", C.c_void_p), ("res", C.c_void_p), ("ldres", C.c_int64), ("res_alias", C.c_int32),
+                ("scale", C.c_float), ("has_scale", C.c_int32),
+                ("pe", C.c_void_p), ("n_ctx", C.c_int32), ("H", C.c_int32), ("Tpad", C.c_int32), ("frag", C.c_int32), ("c_frag", C.c_int32),
+                ("pos", C.c_void_p), ("force_small", C.c_int32),
+                ("C", C.c_void_p), ("c_bytes", C.c_int64), ("ldc", C.c_int64), ("C2", C.c_void_p), ("C3", C.c_void_p), ("c2_bytes", C.c_int64), ("ldc2", C.c_int64),
+                ("kernel_id", C.c_int32)]
 
 
 _TOKEN_DT = np.dtype([("id", "<i4"), ("tid", "<i4"), ("p", "<f4"), ("plog", "<f4"), ("pt", "<f4"), ("ptsum", "<f4"), ("margin", "<f4")])      # struct Token
@@ -625,6 +639,37 @@ class Context:
                                             1 if res_alias else 0, float(scale), int(has_scale), ptr(pos), Cb.ctypes.data, Cb.nbytes, int(ldc), ptr(C2), ptr(C3),
                                             0 if C2 is None else C2.nbytes, int(ldc2), C.byref(kid)))
         return kid.value, Cb, C2, C3
+
+    def gemm16_epi(self, launcher, N, K, epi, W, C_buf, A=None, lda=0, a_rows_per_batch=0, a_batch_stride=0, a_frag=False, M=None, ln=None, use_wf=False, bias=None, res=None,
+                   res_alias=False, scale=1.0, has_scale=0, pe=None, n_ctx=0, H=0, Tpad=0, frag=False, c_frag=False, pos=None, force_small=False, ldc=0, C2_buf=None, C3_buf=None, ldc2=0):
+        """One f16_mfma product on caller-supplied operands through the public launchers (skw_debug_gemm16_epi, skw_engine.hip).  launcher: 0 skw_gemm16 as k_gemm16w, 1 as k_gemm16,
+        2 skw_gemm16_small, 3 skw_gemm16_small_lnA.  A: flat uint16 array of f16 bits (rows at lda, the batch-strided rows of conv2, or the fragment-order image) or, launcher 3,
+        ln = (x f32 [M][K], gain [K], bias [K]); W uint16 [N][K].  C_buf (C2_buf / C3_buf) hold what the output buffers hold BEFORE the launch — the caller's sentinel with its
+        margins, the residual when res_alias — and are not modified.  -> (rc, kernel id, C, C2, C3): rc 0, or -2 when the launcher refuses the arguments; -1 raises."""
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        W = np.ascontiguousarray(W, dtype=np.uint16); assert W.shape == (N, K)
+        A = None if A is None else np.ascontiguousarray(A, dtype=np.uint16).reshape(-1)
+        lx, lw, lb = (f32(v) for v in ln) if ln is not None else (None, None, None)
+        if M is None:
+            M = lx.shape[0]
+        bias, res, pe = f32(bias), f32(res), f32(pe)
+        pos = None if pos is None else np.ascontiguousarray(pos, dtype=np.int32)
+        assert (bias is None or bias.size == N) and (pos is None or pos.size == M) and (lx is None or (lx.shape == (M, K) and lw.size == K and lb.size == K))
+        assert res is None or res.ndim == 2 and res.shape[0] == M
+        assert pe is None or pe.shape == (n_ctx, N)
+        Cb = np.ascontiguousarray(C_buf).copy(); C2 = None if C2_buf is None else np.ascontiguousarray(C2_buf).copy(); C3 = None if C3_buf is None else np.ascontiguousarray(C3_buf).copy()
+        assert (C2 is None) == (C3 is None) and (C2 is None or C2.nbytes == C3.nbytes)
+        a = Gemm16EpiArgs(launcher=int(launcher), M=int(M), N=int(N), K=int(K), epi=int(epi), A=ptr(A), a_halves=0 if A is None else A.size, lda=int(lda),
+                          a_rows_per_batch=int(a_rows_per_batch), a_batch_stride=int(a_batch_stride), a_frag=1 if a_frag else 0, ln_x=ptr(lx), ln_w=ptr(lw), ln_b=ptr(lb),
+                          W=W.ctypes.data, use_wf=1 if use_wf else 0, bias=ptr(bias), res=ptr(res), ldres=0 if res is None else res.shape[1], res_alias=1 if res_alias else 0,
+                          scale=float(scale), has_scale=int(has_scale), pe=ptr(pe), n_ctx=int(n_ctx), H=int(H), Tpad=int(Tpad), frag=1 if frag else 0, c_frag=1 if c_frag else 0,
+                          pos=ptr(pos), force_small=1 if force_small else 0, C=Cb.ctypes.data, c_bytes=Cb.nbytes, ldc=int(ldc), C2=ptr(C2), C3=ptr(C3),
+                          c2_bytes=0 if C2 is None else C2.nbytes, ldc2=int(ldc2), kernel_id=-1)
+        rc = lib().skw_debug_gemm16_epi(self.h, C.byref(a))
+        if rc not in (0, -2):
+            self._check(rc)
+        return rc, a.kernel_id, Cb, C2, C3
 
     def q8_quantize(self, x, K):
         """k_q8_quantize on f32 rows x [M][ldx >= K] (skw_debug_q8_quantize) -> q int8 [M][K], d and s f32 [K/32][M]"""
