@@ -25,6 +25,7 @@
 #define SKW_ENGINE_H
 #include <stddef.h>
 #include <stdint.h>
+#include "skw_align_params.h"      /* skw_align_params; the arithmetic and its helpers: skw_align.h */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -190,6 +191,24 @@ int  skw_full_batch_rules(skw_ctx*, const skw_full_params* params /* [n_clips] *
                           uint32_t* const* rng_state, int32_t* const* context, const skw_decode_rules* const* rules /* NULL, or [n_clips] with entries that may be NULL */,
                           skw_result* results);
 
+/* Word timestamps: a time per text token from the cross-attention weights of a set of alignment heads, warped against the token axis (openai-whisper word_timestamps,
+ * whisper.cpp dtw_token_timestamps).  include/skw_align.h states the arithmetic, step by step, as one contract the kernels and a CPU evaluator evaluate to the same bits.
+ * skw_full_batch_aligned is skw_full_batch_rules with one skw_align_params per clip: align == NULL, a NULL entry or enabled == 0 is skw_full_batch_rules for that clip, bit for
+ * bit, and a call with no aligned clip is that call launch for launch (nothing is allocated either).  For an aligned clip every window that is accepted, is speech and holds
+ * text is run once more, teacher-forced and without [prev] context, and its text tokens receive their times; tokens, text, segments and log-probabilities are what the
+ * unaligned call returns.  times[i] (release with skw_token_times_free): n = results[i].n_tokens, t0 / t1 per result token in centiseconds from the clip's start, -1 for
+ * timestamp tokens and for clips that did not ask.  t1 of a token is t0 of the window's next text token (the last one's: where <|endoftext|> aligns).
+ * A bad record (empty head mask, a head or layer outside the model, median_width even, below 1 or above SKW_ALIGN_MEDIAN_MAX) fails the call before anything runs, naming the clip.
+ * skw_align_batch is forced alignment of GIVEN text: clip i (at most 30 s: one window) against text_tokens[i][0 .. n_text[i]) (ids below <|endoftext|>, 1 .. n_text_ctx / 2 of
+ * them); nothing is decoded.  times[i].n = n_text[i].  Language and task come from params[i] (lang_id < 0: detected); every align entry must be enabled. */
+typedef struct { int32_t n; int64_t* t0; int64_t* t1; } skw_token_times;
+int  skw_full_batch_aligned(skw_ctx*, const skw_full_params* params /* [n_clips] */, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                            uint32_t* const* rng_state, int32_t* const* context, const skw_decode_rules* const* rules, const skw_align_params* const* align /* as rules */,
+                            skw_token_times* times /* [n_clips] out */, skw_result* results);
+int  skw_align_batch(skw_ctx*, const skw_full_params* params /* [n_clips] */, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                     const int32_t* const* text_tokens, const int32_t* n_text, const skw_align_params* const* align, skw_token_times* times /* [n_clips] out */);
+void skw_token_times_free(skw_token_times*);
+
 /* ---- decision trace / teacher forcing (parity instrumentation of the hot path; the reference has no counterpart) ----
  * skw_full_batch_traced is skw_full_batch that also returns, per clip, one record for EVERY sampling decision it made, in execution order
  * over all windows and temperature passes (discarded tokens included).  With forced_ids[i] == NULL the run is free (forced_id == chosen_id).
@@ -222,7 +241,8 @@ typedef struct { float mel_ms, encode_ms, decode_ms, total_ms; int32_t n_windows
 } skw_timing;
 void skw_ctx_last_timing(const skw_ctx*, skw_timing* out);
 /* per-kernel-class event timing (adds an event pair around every launch; use for roofline accounting, not for the timed run).
- * classes: 0 k_gemm, 1 k_gemm_smallm, 2 k_attn_encoder, 3 k_layernorm, 4 k_mel, 5 k_dec_self_attn, 6 k_dec_sample, 7 other, 8 k_dec_cross_attn, 9 k_dec_constrain */
+ * classes: 0 k_gemm, 1 k_gemm_smallm, 2 k_attn_encoder, 3 k_layernorm, 4 k_mel, 5 k_dec_self_attn, 6 k_dec_sample, 7 other, 8 k_dec_cross_attn, 9 k_dec_constrain,
+ *          10 k_align_qk, 11 k_align_reduce, 12 k_align_dtw (word timestamps) */
 void skw_ctx_profile(skw_ctx*, int on);
 int  skw_ctx_profile_get(skw_ctx*, int cls, char* name, size_t name_len, long* count, double* ms, double* algorithmic_flops, double* algorithmic_bytes);
 /* In-kernel launch clock of the decode step's dominant kernel (the f16_mfma cross attention).  HIP events cannot sit between the kernels of a captured step graph, and an eager,

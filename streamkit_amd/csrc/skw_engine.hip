@@ -529,6 +529,13 @@ struct skw_ctx {
     int* forced_dev = nullptr; SkwTraceStep* trace_dev = nullptr;   // [max_batch][max_tok], allocated by the first skw_full_batch_traced
     skw_timing timing{};
     int last_enc_B = 0;
+    // word timestamps (align_window, include/skw_align.h).  The workspace is allocated by the first call that aligns a clip (ensure_align_ws): P holds ONE layer's capture for a
+    // chunk of al_rows alignment rows — every head, n_audio_ctx keys, f32 — so its size does not depend on the batch; acc / x: the chunk's matrices (f64 sums, f32 result).
+    float* al_P = nullptr; double* al_acc = nullptr; float* al_x = nullptr; SkwAlignSeq* al_seqs = nullptr; int* al_times = nullptr; int al_rows = 0;      // al_times: jump | t0 | t1
+    // the alignment pass in flight (al_on: only inside align_window): what run_decoder_step's hook captures after an alignment layer's cross-query GEMM
+    bool al_on = false; const uint32_t* al_mask = nullptr;
+    const SkwAlignSeq* al_h_seqs = nullptr; int al_tap_base = 0, al_tap_next = 0;      // taps: the chunk's records on the host, the call's sequence numbering
+    int al_width = 7, al_nseq = 0, al_rows_now = 0, al_kw_max = 0, al_n_heads = 0, al_l_first = 0, al_l_last = 0;
     struct WsEntry { const char* name; void** slot; size_t bytes; bool zero; bool is_float; };      // one workspace buffer: the field it fills and its size (skw_ctx_create)
     std::vector<WsEntry> ws_table;
 };
@@ -677,6 +684,7 @@ extern "C" void skw_ctx_free(skw_ctx* c) {
     for (int g = 0; g < skw_ctx::MAX_GROUPS; ++g) { if (c->gstream[g]) { hipStreamSynchronize(c->gstream[g]); hipStreamDestroy(c->gstream[g]); } if (c->gev[g]) hipEventDestroy(c->gev[g]); }
     for (void* p : c->allocs) hipFree(p);
     hipFree(c->stageK); hipFree(c->stageV); hipFree(c->slot_map); hipFree(c->forced_dev); hipFree(c->trace_dev); hipFree(c->kclk);
+    hipFree(c->al_P); hipFree(c->al_acc); hipFree(c->al_x); hipFree(c->al_seqs); hipFree(c->al_times);
     if (c->h_st) hipHostFree(c->h_st); if (c->h_toks) hipHostFree(c->h_toks); if (c->h_row_live) hipHostFree(c->h_row_live);
     for (int i = 0; i < 6; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
     if (c->stream) hipStreamDestroy(c->stream);
@@ -713,13 +721,18 @@ extern "C" void skw_debug_enable(int on) { g_taps_on = on != 0; g_taps.clear(); 
 extern "C" long skw_debug_get(const char* name, float* out, size_t cap) {
     auto it = g_taps.find(name); if (it == g_taps.end()) return -1; if (out && cap >= it->second.size()) memcpy(out, it->second.data(), it->second.size() * 4); return (long)it->second.size();
 }
-enum TapLayout { TAP_F32, TAP_F16_KPERM, TAP_HEADS, TAP_VT };
+enum TapLayout { TAP_F32, TAP_F16_KPERM, TAP_HEADS, TAP_VT, TAP_F16_PLAIN };
 static void tap(skw_ctx* c, const char* name, const void* dev, int rows, int cols, TapLayout lay) {
     if (!g_taps_on) return;
     hipStreamSynchronize(c->stream);
     std::vector<float>& o = g_taps[name]; o.assign((size_t)rows * cols, 0.f);
     const int H = c->m->hp.n_audio_head, Tpad = c->Tpad;
     if (lay == TAP_F32) { hipMemcpy(o.data(), dev, o.size() * 4, hipMemcpyDeviceToHost); return; }
+    if (lay == TAP_F16_PLAIN) {      // f16 rows in natural order; the tap holds the BIT PATTERNS as floats (exact: every value is below 2^16)
+        std::vector<uint16_t> h((size_t)rows * cols); hipMemcpy(h.data(), dev, h.size() * 2, hipMemcpyDeviceToHost);
+        for (size_t i = 0; i < h.size(); ++i) o[i] = (float)h[i];
+        return;
+    }
     if (lay == TAP_F16_KPERM) {
         std::vector<uint16_t> h((size_t)rows * cols); hipMemcpy(h.data(), dev, h.size() * 2, hipMemcpyDeviceToHost);
         for (int r = 0; r < rows; ++r) for (int i = 0; i < cols; ++i) o[(size_t)r * cols + i] = skw_f16_to_f32(h[(size_t)r * cols + skw_kperm(i)]);
@@ -733,9 +746,10 @@ static void tap(skw_ctx* c, const char* name, const void* dev, int rows, int col
 }
 
 // ------------------------------------------------------------------ per-kernel-class profiling (HIP events on the engine stream)
-enum ProfClass { PC_GEMM = 0, PC_GEMM_SMALL, PC_ATTN_ENC, PC_LAYERNORM, PC_MEL, PC_DEC_ATTN, PC_DEC_SAMPLE, PC_OTHER, PC_DEC_XATTN, PC_DEC_CONSTRAIN, PC_COUNT };
+enum ProfClass { PC_GEMM = 0, PC_GEMM_SMALL, PC_ATTN_ENC, PC_LAYERNORM, PC_MEL, PC_DEC_ATTN, PC_DEC_SAMPLE, PC_OTHER, PC_DEC_XATTN, PC_DEC_CONSTRAIN, PC_ALIGN_QK,
+                 PC_ALIGN_REDUCE, PC_ALIGN_DTW, PC_COUNT };
 static const char* const g_prof_names[PC_COUNT] = {"k_gemm", "k_gemm_smallm", "k_attn_encoder", "k_layernorm", "k_mel", "k_dec_self_attn", "k_dec_sample", "other", "k_dec_cross_attn",
-                                                 "k_dec_constrain"};
+                                                 "k_dec_constrain", "k_align_qk", "k_align_reduce", "k_align_dtw"};
 struct ProfRec { int cls; double flops, bytes; hipEvent_t a, b; };
 struct ProfState { bool on = false; std::vector<ProfRec> recs;
 std::vector<hipEvent_t> pool; size_t next = 0; double ms[PC_COUNT] = {}, flops[PC_COUNT] = {}, bytes[PC_COUNT] = {}; long count[PC_COUNT] = {}; };
@@ -982,6 +996,41 @@ __global__ void k_lang_argmax(const float* logits, int n_vocab, int tok_sot, int
     for (int o = 32; o > 0; o >>= 1) { float ov = __shfl_xor(bv, o, 64); int oi = __shfl_xor(bi, o, 64); if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; } }
     if (threadIdx.x == 0) out[blockIdx.x] = bi;
 }
+// The alignment pass's hook (align_window): right after decoder layer l's cross-query GEMM, when l holds alignment heads — dq16 then holds exactly the f16 queries the cross
+// attention is about to read, and ck is the layer's cross K as this context stores it (rows, or the fragment-order image).  Step 1 for the layer's heads into the capture, then
+// steps 2-5 into the chunk's matrices: only one layer's capture is ever live.  Launches nothing outside an alignment pass.
+static void align_hook(skw_ctx* c, int l, const half_t* dq16, const half_t* ck, hipStream_t s) {
+    if (!c->al_on || !c->al_mask[l]) return;
+    const skw_hparams& hp = c->m->hp; const int nh = skw_align_popcount(c->al_mask[l]);
+    // taps, one set per SEQUENCE of the call (s = the sequence's number in the order the call aligns them; "align_seq_s<s>" says which clip and window it is): the sequence's
+    // alignment rows of this layer's queries and its slot's cross K, both as f16 bit patterns in natural order — what the evaluator needs to restate the pass
+    if (g_taps_on) {
+        const int nc = hp.n_audio_ctx, dt = hp.n_text_state; char name[40];
+        std::vector<uint16_t> h; hipStreamSynchronize(s);
+        for (int i = 0; i < c->al_nseq; ++i) {
+            const SkwAlignSeq& a = c->al_h_seqs[i]; const int sn = c->al_tap_base + i;
+            snprintf(name, sizeof name, "align_dq16_l%d_s%d", l, sn); tap(c, name, dq16 + (size_t)a.qrow0 * dt, a.n, dt, TAP_F16_PLAIN);
+            h.resize(c->kclip()); hipMemcpy(h.data(), ck + (size_t)a.slot * c->kclip(), h.size() * 2, hipMemcpyDeviceToHost);
+            snprintf(name, sizeof name, "align_ck_l%d_s%d", l, sn); std::vector<float>& o = g_taps[name]; o.assign((size_t)nc * dt, 0.f);
+            for (int k = 0; k < nc; ++k) for (int f = 0; f < dt; ++f)
+                o[(size_t)k * dt + f] = (float)h[c->kv_frag() ? (size_t)skw_kfrag_off(0, hp.n_text_head, c->Tpad, k, f & ~7) + (f & 7) : (size_t)k * dt + f];
+        }
+    }
+    { ProfScope p_(c, PC_ALIGN_QK, 2.0 * c->al_rows_now * nh * 64.0 * hp.n_audio_ctx, 0);
+      skw_align_qk(dq16, hp.n_text_state, ck, c->al_seqs, c->al_nseq, c->al_rows_now, c->al_mask[l], hp.n_text_head, hp.n_audio_ctx, c->Tpad, c->kv_frag(), c->al_P, c->al_rows_now,
+                   hp.n_audio_ctx, s); }
+    if (g_taps_on) {      // the capture of this layer, per sequence: [head][row][key]
+        const int nc = hp.n_audio_ctx; char name[40]; hipStreamSynchronize(s);
+        for (int i = 0; i < c->al_nseq; ++i) {
+            const SkwAlignSeq& a = c->al_h_seqs[i];
+            snprintf(name, sizeof name, "align_P_l%d_s%d", l, c->al_tap_base + i); std::vector<float>& o = g_taps[name]; o.assign((size_t)nh * a.n * nc, 0.f);
+            for (int hl = 0; hl < nh; ++hl) hipMemcpy(o.data() + (size_t)hl * a.n * nc, c->al_P + ((size_t)hl * c->al_rows_now + a.prow0) * nc, sizeof(float) * a.n * nc, hipMemcpyDeviceToHost);
+        }
+    }
+    { ProfScope p_(c, PC_ALIGN_REDUCE, 0, 0);
+      skw_align_reduce(c->al_P, c->al_rows_now, hp.n_audio_ctx, c->al_seqs, c->al_nseq, c->al_kw_max, nh, c->al_width, l == c->al_l_first, l == c->al_l_last, c->al_n_heads, c->al_acc,
+                       c->al_x, s); }
+}
 // rows [r0, r0 + Bw) of the window batch on stream s: sequences are independent, so groups of rows can run on their own streams
 // prefill: the rows are prompt tokens (c->pf_st, scratch from row 0), several per sequence: the K / V caches are addressed through the row's sequence (pad) and cache row (seek)
 static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logits, hipStream_t s, bool prefill = false) {
@@ -1016,6 +1065,7 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
             { SkwGemmArgs a = q8_args(Bw, dx, dt, EPI_F32); a.res = dx; a.ldres = dt; Q8_GEMM(c, a, L.o, r0, true); }
             Q8_LN(c, dx, Bw, dt, L.cross_ln, r0, dy32);
             { SkwGemmArgs a = q8_args(Bw, dq16, dt, EPI_F16_PLAIN); a.scale = KQscale; a.has_scale = 1; Q8_GEMM(c, a, L.cq, r0, true); }
+            align_hook(c, l, dq16, ck, s);
             { ProfScope p_(c, PC_DEC_XATTN, 4.0 * live * (double)nc * dt, 4.0 * live * (double)nc * dt);
             if (!(xq_mq && skw_xattn_prefill_exact(dq16, ck, cv, (half_t*)datt32, c->pf_nseq, c->pf_nq_max, c->pf_meta, c->pf_meta + c->max_batch, c->pf_meta + 2 * c->max_batch, H, dt, nc,
                                                    c->Tpad, s, 1, c->var_k ? c->slot_k : nullptr)))
@@ -1082,6 +1132,7 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
         { SkwGemmArgs a = gemm_args(datt16, dt, L.o, Bw, dx, dt, EPI_F32); a.res = dx; a.ldres = dt; a.a_frag = sa_frag; gemm_s(a); }
         {
             { SkwGemmArgs a = gemm_args(dy16, dt, L.cq, Bw, dq16, dt, EPI_F16_PLAIN); a.scale = KQscale; a.has_scale = 1; gemm_ln(a, L.cq, L.cross_ln, 3 * l, false); }
+            align_hook(c, l, dq16, ck, s);
             const bool xp_mq = skw_sw(SW_PROMPT_XATTN_MQ) != 0;
             if (prefill && xp_mq && c->precision == SKW_PRECISION_F16_MFMA && c->pf_nseq > 0) {
                 // the prompt pass in the tolerance precision: one read of a sequence's cross K / V^T for up to 128 of its prompt tokens (the encoder attention kernel with the
@@ -1273,6 +1324,11 @@ struct FullRequest {
     const int32_t* const* forced_ids = nullptr; const int32_t* n_forced = nullptr; std::vector<std::vector<SkwTraceStep>>* traces = nullptr;      // tracing / teacher forcing
     uint32_t* const* rng_state = nullptr; int32_t* const* context = nullptr;
     const skw_decode_rules* const* rules = nullptr; bool constrained = false;      // skw_full_batch_rules; constrained: some clip's record is not the default (set by validate_request)
+    // skw_full_batch_aligned: a clip's record (NULL / not enabled: the clip is not aligned) and where its token times go; aligned: some clip asked (set by validate_request)
+    const skw_align_params* const* align = nullptr; skw_token_times* times = nullptr; bool aligned = false;
+    // skw_align_batch: no decoding — text[i][0 .. n_text[i]) is aligned to clip i's first window
+    const int32_t* const* text = nullptr; const int32_t* n_text = nullptr;
+    bool wants_align(int ci) const { return align && align[ci] && align[ci]->enabled; }
     bool mixed() const { return pv != nullptr; }
     bool tracing() const { return traces != nullptr; }
     const skw_full_params& P(int ci) const { return pv ? pv[ci] : *p; }
@@ -1280,12 +1336,15 @@ struct FullRequest {
 };
 // The call's host state, per clip unless said otherwise
 struct CallState {
-    explicit CallState(int n) : seek(n, 0), acc(n), temps(n), tidx(n, 0), retry_slot(n, -1), prompt_past(n), last_take(n, 0), lang(n), f_cursor(n, 0) {}
+    explicit CallState(int n) : seek(n, 0), acc(n), temps(n), tidx(n, 0), retry_slot(n, -1), prompt_past(n), last_take(n, 0), lang(n), f_cursor(n, 0), tt0(n), tt1(n) {}
     std::vector<int> n_len, n_len_org, seek; std::vector<SeqAcc> acc;
     std::vector<std::vector<float>> temps; std::vector<int> tidx;      // the clip's temperature ladder and the index its current window is decoded at
     std::vector<int> retry_slot;                                      // the window slot whose cross K/V a retrying clip left behind (-1: not retrying)
     std::vector<std::vector<int>> prompt_past; std::vector<int> last_take;      // text already produced conditions the next window of the same clip; what the last prompt took of it
     std::vector<int> lang, f_cursor;                                  // f_cursor (tracing): decisions of the clip made so far (= its position in forced_ids[i])
+    // word timestamps: per clip the times of its result tokens (parallel to acc.tok; -1: none), and the windows collect_window accepted for alignment in this round
+    struct AlignJob { int ci, slot, seek, n_keys; std::vector<int> text, idx; };      // text: the window's text tokens; idx: where each one's times go in tt0 / tt1
+    std::vector<std::vector<int64_t>> tt0, tt1; std::vector<AlignJob> align_jobs;
     SkwLogitParams lp;
     float enc_ms = 0.f, dec_ms = 0.f; int tot_windows = 0, tot_steps = 0; long tot_row_steps = 0; int used_groups = 1, used_group_rows = 0;
 };
@@ -1330,6 +1389,19 @@ static int validate_request(skw_ctx* c, FullRequest& rq) {
         char who[32]; snprintf(who, sizeof who, "clip %d", i);
         if (!skw_decode_rules_check(rq.rules[i], hp.n_vocab, who, errbuf, 512)) return -3;
         if (!skw_decode_rules_is_default(rq.rules[i])) rq.constrained = true;
+    }
+    rq.aligned = false;
+    if (rq.align) for (int i = 0; i < rq.n_clips; ++i) {
+        if (!skw_align_check_params(rq.align[i], hp.n_text_layer, hp.n_text_head, i, errbuf, 512)) return -3;
+        if (rq.wants_align(i)) rq.aligned = true;
+    }
+    if (rq.aligned && !rq.times) { snprintf(errbuf, 512, "alignment asked for without a place for the token times"); return -3; }
+    if (rq.text) for (int i = 0; i < rq.n_clips; ++i) {
+        if (!rq.wants_align(i)) { snprintf(errbuf, 512, "clip %d: skw_align_batch needs an enabled alignment record", i); return -3; }
+        if (rq.n_text[i] < 1 || rq.n_text[i] > hp.n_text_ctx / 2) { snprintf(errbuf, 512, "clip %d: %d text tokens outside [1, %d]", i, rq.n_text[i], hp.n_text_ctx / 2); return -3; }
+        for (int k = 0; k < rq.n_text[i]; ++k) if (rq.text[i][k] < 0 || rq.text[i][k] >= c->m->tok_eot) {
+            snprintf(errbuf, 512, "clip %d: text token %d (id %d) is not a text token", i, k, rq.text[i][k]); return -3; }
+        if (rq.n_samples[i] > WHISPER_SAMPLE_RATE * 30) { snprintf(errbuf, 512, "clip %d: skw_align_batch aligns one window (at most 30 s of audio)", i); return -3; }
     }
     return 0;
 }
@@ -1610,8 +1682,110 @@ static int collect_window(skw_ctx* c, const FullRequest& rq, CallState& cs, cons
         }
         cs.tidx[ci] = 0;
         skw_prompt_past_update(cs.prompt_past[ci], cs.last_take[ci], tk, s.result_len, v.no_speech);
+        const int tok0 = (int)cs.acc[ci].tok.size(), seek0 = cs.seek[ci];
         cs.seek[ci] += skw_window_output(tk, v.n_tok, cs.seek[ci], s.seek_delta, cs.n_len_org[ci], m->tok_beg, m->tok_eot, q.single_segment, v.no_speech, m->tok_str.data(),
                                          cs.acc[ci]);
+        if (rq.wants_align(ci)) {      // an accepted window that is speech: its text tokens (what the output step kept, below <|endoftext|>) are aligned by align_window
+            CallState::AlignJob job{ci, j, seek0, w.ks[j], {}, {}};
+            for (int k = tok0; k < (int)cs.acc[ci].tok.size(); ++k) if (cs.acc[ci].tok[k].id < m->tok_eot) { job.text.push_back(cs.acc[ci].tok[k].id); job.idx.push_back(k); }
+            if (!job.text.empty()) cs.align_jobs.push_back(job);
+        }
+    }
+    return 0;
+}
+
+// ---- word timestamps: the phase after collect_window (include/skw_align.h is the arithmetic; DESIGN.md section 3 "Word timestamps")
+// The capture of one layer for one chunk: al_rows alignment rows x every head x n_audio_ctx keys, f32, cut to SKW_ALIGN_P_BYTES — but never below one sequence
+// (SKW_ALIGN_MAX_ROWS rows) — whatever the batch size.  With it: f64 sums and f32 matrix per cell of the chunk, the sequences' records, jump / t0 / t1 per row.
+#define SKW_ALIGN_P_BYTES ((size_t)128 << 20)
+static int ensure_align_ws(skw_ctx* c) {
+    if (c->al_P) return 0;
+    char* errbuf = c->errbuf; const skw_hparams& hp = c->m->hp;
+    const size_t per_row = (size_t)hp.n_text_head * hp.n_audio_ctx * sizeof(float);
+    const int rows = (int)std::min<size_t>((size_t)c->rows_cap, std::max<size_t>(SKW_ALIGN_MAX_ROWS, SKW_ALIGN_P_BYTES / per_row));
+    float* P = nullptr; double* acc = nullptr; float* x = nullptr; SkwAlignSeq* sq = nullptr; int* tm = nullptr;
+    if (hipMalloc((void**)&P, per_row * rows) != hipSuccess || hipMalloc((void**)&acc, sizeof(double) * rows * hp.n_audio_ctx) != hipSuccess ||
+        hipMalloc((void**)&x, sizeof(float) * rows * hp.n_audio_ctx) != hipSuccess || hipMalloc((void**)&sq, sizeof(SkwAlignSeq) * c->max_batch) != hipSuccess ||
+        hipMalloc((void**)&tm, sizeof(int) * 3 * rows) != hipSuccess) {
+        hipFree(P); hipFree(acc); hipFree(x); hipFree(sq); hipFree(tm); snprintf(errbuf, 512, "alignment workspace: device allocation failed"); return -1; }
+    poison_floats(P, per_row * rows); poison_floats(acc, sizeof(double) * rows * hp.n_audio_ctx); poison_floats(x, sizeof(float) * rows * hp.n_audio_ctx);
+    c->al_P = P; c->al_acc = acc; c->al_x = x; c->al_seqs = sq; c->al_times = tm; c->al_rows = rows;
+    return 0;
+}
+// The windows collect_window accepted (cs.align_jobs: not retried, not no-speech, at least one text token, clip asked) get their token times: the teacher-forced sequence
+// S = sot (, language, task), notimestamps, text — no [prev] context, from position 0 — runs as ONE prefill pass per chunk of whole sequences, exactly as prompt_pass chunks
+// (whatever SKW_PROMPT_PASS says, no logits); the hook in run_decoder_step captures and reduces every alignment layer on the way; then the DTW.  The pass overwrites the
+// slots' self-attention caches and the step's scratch, which the next window pass rebuilds from position 0 anyway; it only reads the slots' cross K.
+// Jobs whose records differ (head mask, median width) run in passes of their own.
+static int align_window(skw_ctx* c, const FullRequest& rq, CallState& cs) {
+    char* errbuf = c->errbuf; skw_model* m = c->m; const skw_hparams& hp = m->hp; const int ntc = hp.n_text_ctx;
+    std::vector<CallState::AlignJob> jobs; jobs.swap(cs.align_jobs);
+    if (jobs.empty()) return 0;
+    if (ensure_align_ws(c)) return -1;
+    std::vector<bool> done(jobs.size(), false);
+    for (size_t g0 = 0; g0 < jobs.size(); ++g0) {
+        if (done[g0]) continue;
+        const skw_align_params& ap = *rq.align[jobs[g0].ci];
+        std::vector<size_t> grp;      // the jobs under the same record as job g0, in order
+        for (size_t k = g0; k < jobs.size(); ++k) if (!done[k]) { const skw_align_params& bp = *rq.align[jobs[k].ci];
+            if (bp.median_width == ap.median_width && memcmp(bp.head_mask, ap.head_mask, sizeof ap.head_mask) == 0) { grp.push_back(k); done[k] = true; } }
+        int l_first = -1, l_last = -1; for (int l = 0; l < hp.n_text_layer; ++l) if (ap.head_mask[l]) { if (l_first < 0) l_first = l; l_last = l; }
+        size_t at = 0;
+        while (at < grp.size()) {
+            // one chunk: whole sequences while the pass's rows fit the step's scratch, the alignment rows the capture, the sequences the records
+            std::vector<SkwSeqState> pf; std::vector<SkwAlignSeq> sq; std::vector<int> meta((size_t)3 * c->max_batch, 0);
+            int arows = 0, nq_max = 0, kw_max = 0, n_max = 0; long cells = 0; size_t hi = at;
+            for (; hi < grp.size() && (int)sq.size() < c->max_batch; ++hi) {
+                const CallState::AlignJob& jb = jobs[grp[hi]];
+                int32_t S[8 + SKW_ALIGN_MAX_ROWS]; skw_full_params q = rq.P(jb.ci); q.no_timestamps = 1;
+                int np = prompt_tail(m, q, cs.lang[jb.ci], S);
+                const int T = (int)jb.text.size(), N = T + 1, rows = np + T;
+                if (N > SKW_ALIGN_MAX_ROWS || rows > ntc || rows > c->rows_cap || N > c->al_rows) {
+                    snprintf(errbuf, 512, "clip %d: a window of %d text tokens cannot be aligned", jb.ci, T); return -1; }
+                if (hi > at && ((int)pf.size() + rows > c->rows_cap || arows + N > c->al_rows)) break;
+                for (int k = 0; k < T; ++k) S[np + k] = jb.text[k];
+                SkwAlignSeq a; memset(&a, 0, sizeof a);
+                a.qrow0 = (int)pf.size() + np - 1; a.n = N; a.slot = jb.slot; a.n_keys = jb.n_keys; a.kw = skw_align_kw(cs.n_len_org[jb.ci], jb.seek, jb.n_keys); a.prow0 = arows;
+                a.seek_cs = jb.seek; a.xoff = cells;
+                meta[sq.size()] = (int)pf.size(); meta[c->max_batch + sq.size()] = rows; meta[2 * c->max_batch + sq.size()] = jb.slot;
+                for (int k = 0; k < rows; ++k) { SkwSeqState t; memset(&t, 0, sizeof t);
+                    t.active = 1; t.cur_token = S[k]; t.cur_pos = k; t.pad = jb.slot; t.seek = jb.slot * ntc + k; t.n_keys = jb.n_keys; pf.push_back(t); }
+                sq.push_back(a); arows += N; cells += (long)N * a.kw; nq_max = std::max(nq_max, rows); kw_max = std::max(kw_max, a.kw); n_max = std::max(n_max, N);
+            }
+            const int n = (int)pf.size(), ns = (int)sq.size();
+            HIPCHK(hipMemcpyAsync(c->pf_st, pf.data(), sizeof(SkwSeqState) * n, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->pf_meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->al_seqs, sq.data(), sizeof(SkwAlignSeq) * ns, hipMemcpyHostToDevice, c->stream));
+            c->pf_nseq = ns; c->pf_nq_max = nq_max;
+            c->al_on = true; c->al_mask = ap.head_mask; c->al_width = ap.median_width; c->al_nseq = ns; c->al_h_seqs = sq.data(); c->al_tap_base = c->al_tap_next;
+             c->al_rows_now = arows; c->al_kw_max = kw_max;
+            c->al_n_heads = skw_align_n_heads(ap.head_mask); c->al_l_first = l_first; c->al_l_last = l_last;
+            run_decoder_step(c, 0, n, 0, false, c->stream, true);
+            c->al_on = false; c->al_mask = nullptr; c->pf_nseq = 0;
+            if (g_taps_on) {      // per sequence: its matrix, which clip and window it is, and which of the clip's result tokens its rows time
+                char name[40];
+                for (int i = 0; i < ns; ++i) { const CallState::AlignJob& jb = jobs[grp[at + i]]; const int sn = c->al_tap_base + i;
+                    snprintf(name, sizeof name, "align_x_s%d", sn); tap(c, name, c->al_x + sq[i].xoff, sq[i].n, sq[i].kw, TAP_F32);
+                    snprintf(name, sizeof name, "align_seq_s%d", sn);
+                    g_taps[name] = {(float)jb.ci, (float)jb.seek, (float)jb.n_keys, (float)sq[i].kw, (float)sq[i].n, (float)jb.slot, (float)cs.n_len_org[jb.ci]};
+                    snprintf(name, sizeof name, "align_idx_s%d", sn); std::vector<float>& o = g_taps[name]; o.clear(); for (int ix : jb.idx) o.push_back((float)ix); }
+                g_taps["align_n"] = {(float)(c->al_tap_base + ns)};
+            }
+            c->al_tap_next += ns; c->al_h_seqs = nullptr;
+            int *jump = c->al_times, *t0 = c->al_times + c->al_rows, *t1 = c->al_times + 2 * c->al_rows;
+            { ProfScope p_(c, PC_ALIGN_DTW, 0, 0);
+              if (!skw_align_dtw(c->al_x, c->al_seqs, ns, n_max, kw_max, jump, t0, t1, c->stream)) { snprintf(errbuf, 512, "alignment: the DTW launcher refused %d rows x %d keys", n_max, kw_max);
+                                                                                                   return -1; } }
+            std::vector<int> h0(arows), h1(arows);
+            HIPCHK(hipMemcpyAsync(h0.data(), t0, sizeof(int) * arows, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(h1.data(), t1, sizeof(int) * arows, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));      // (the chunk's host vectors are sources of the copies above, and pf_st / al_seqs are reused by the next chunk)
+            for (int i = 0; i < ns; ++i) { const CallState::AlignJob& jb = jobs[grp[at + i]];
+                std::vector<int64_t>& a0 = cs.tt0[jb.ci]; std::vector<int64_t>& a1 = cs.tt1[jb.ci];
+                for (size_t k = 0; k < jb.idx.size(); ++k) { const size_t ix = (size_t)jb.idx[k]; if (a0.size() <= ix) { a0.resize(ix + 1, -1); a1.resize(ix + 1, -1); }
+                    a0[ix] = h0[sq[i].prow0 + k]; a1[ix] = h1[sq[i].prow0 + k]; } }
+            at = hi;
+        }
     }
     return 0;
 }
@@ -1633,6 +1807,13 @@ static int finish_call(skw_ctx* c, const FullRequest& rq, CallState& cs) {
         res.text = (char*)malloc(A.text.size() + 1); memcpy(res.text, A.text.data(), A.text.size()); res.text[A.text.size()] = 0;
         tot_tokens += res.n_tokens;
     }
+    if (rq.times) for (int i = 0; i < n_clips; ++i) {      // per result token (skw_align_batch: per given text token); -1 where no time was computed
+        const size_t nt = rq.text ? (size_t)rq.n_text[i] : cs.acc[i].tok.size();
+        cs.tt0[i].resize(nt, -1); cs.tt1[i].resize(nt, -1);
+        skw_token_times& tt = rq.times[i]; tt.n = (int32_t)nt;
+        tt.t0 = (int64_t*)malloc(sizeof(int64_t) * std::max<size_t>(1, nt)); tt.t1 = (int64_t*)malloc(sizeof(int64_t) * std::max<size_t>(1, nt));
+        memcpy(tt.t0, cs.tt0[i].data(), sizeof(int64_t) * nt); memcpy(tt.t1, cs.tt1[i].data(), sizeof(int64_t) * nt);
+    }
     prof_collect(c);
     { float a = 0, t = 0; hipEventElapsedTime(&a, c->ev[0], c->ev[1]); hipEventElapsedTime(&t, c->ev[0], c->ev[5]);
       c->timing.mel_ms = a; c->timing.encode_ms = cs.enc_ms; c->timing.decode_ms = cs.dec_ms;
@@ -1647,7 +1828,7 @@ static int full_batch_impl(skw_ctx* c, FullRequest rq) {
     if (int rc = validate_request(c, rq)) return rc;
     HIPCHK(hipSetDevice(c->m->device));
     if (rq.tracing() && ensure_trace_buffers(c)) return -1;
-    CallState cs(rq.n_clips);
+    CallState cs(rq.n_clips); c->al_tap_next = 0;
     if (int rc = load_call(c, rq, cs)) return rc;
     if (int rc = detect_languages(c, rq, cs)) return rc;
     cs.lp = rq.mixed() ? mixed_logit_params(c->m) : make_logit_params(c->m, rq.p);
@@ -1655,9 +1836,18 @@ static int full_batch_impl(skw_ctx* c, FullRequest rq) {
         WindowBatch w;      // (alive until collect_window has synchronised the stream)
         if (!plan_window(rq, cs, w)) break;
         if (int rc = stage_window(c, rq, cs, w)) return rc;
+        if (rq.text) {      // skw_align_batch: the encoder has run on the clips' one window; the given text stands where a decoded window's would
+            HIPCHK(hipStreamSynchronize(c->stream));
+            for (int j = 0; j < w.Bw; ++j) { const int ci = w.act[j]; CallState::AlignJob job{ci, j, 0, w.ks[j], {}, {}};
+                for (int k = 0; k < rq.n_text[ci]; ++k) { job.text.push_back(rq.text[ci][k]); job.idx.push_back(k); }
+                cs.align_jobs.push_back(job); }
+            if (int rc = align_window(c, rq, cs)) return rc;
+            break;
+        }
         if (int rc = prompt_pass(c, w)) return rc;
         if (int rc = step_loop(c, rq, cs, w)) return rc;
         if (int rc = collect_window(c, rq, cs, w)) return rc;
+        if (rq.aligned) if (int rc = align_window(c, rq, cs)) return rc;
     }
     return finish_call(c, rq, cs);
 }
@@ -1706,6 +1896,30 @@ extern "C" int skw_full_batch_rules(skw_ctx* c, const skw_full_params* params, c
         FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state; rq.context = context; rq.rules = rules;
         return full_batch_impl(c, rq); });
 }
+extern "C" int skw_full_batch_aligned(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                                      uint32_t* const* rng_state, int32_t* const* context, const skw_decode_rules* const* rules, const skw_align_params* const* align,
+                                      skw_token_times* times, skw_result* results) {
+    return guarded(c, "skw_full_batch_aligned", [&] {
+        if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_aligned: params is NULL (one skw_full_params per clip)"); return -1; }
+        if (times) for (int i = 0; i < n_clips; ++i) { times[i].n = 0; times[i].t0 = times[i].t1 = nullptr; }
+        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state; rq.context = context; rq.rules = rules;
+        rq.align = align; rq.times = times;
+        return full_batch_impl(c, rq); });
+}
+extern "C" int skw_align_batch(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                               const int32_t* const* text_tokens, const int32_t* n_text, const skw_align_params* const* align, skw_token_times* times) {
+    return guarded(c, "skw_align_batch", [&] {
+        if (!params || !text_tokens || !n_text || !align || !times) { snprintf(c->errbuf, 512, "skw_align_batch: params, text_tokens, n_text, align and times must all be given"); return -1; }
+        for (int i = 0; i < n_clips; ++i) { times[i].n = 0; times[i].t0 = times[i].t1 = nullptr; }
+        for (int i = 0; i < n_clips; ++i) if (!text_tokens[i]) { snprintf(c->errbuf, 512, "clip %d: no text tokens", i); return -3; }
+        std::vector<skw_result> res(std::max(1, n_clips)); memset((void*)res.data(), 0, sizeof(skw_result) * res.size());
+        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, res.data()); rq.pv = params; rq.align = align; rq.times = times;
+        rq.text = text_tokens; rq.n_text = n_text;
+        const int rc = full_batch_impl(c, rq);
+        for (int i = 0; i < n_clips; ++i) skw_result_free(&res[i]);
+        return rc; });
+}
+extern "C" void skw_token_times_free(skw_token_times* t) { if (!t) return; free(t->t0); free(t->t1); t->t0 = t->t1 = nullptr; t->n = 0; }
 extern "C" int skw_full_batch_traced_context(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                              const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, int32_t* const* context, skw_result* results) {
     static_assert(sizeof(skw_trace_step) == sizeof(SkwTraceStep), "skw_trace_step is SkwTraceStep");
@@ -2447,6 +2661,105 @@ extern "C" int skw_debug_xattn_exact(skw_ctx* c, int mq, int H, int n_ctx, int n
     if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(out_host, dout, nO * 2, hipMemcpyDeviceToHost))) return -1;
     cleanup();
     return 0;
+}
+
+// Test hooks (tests/test_gpu_align_kernels.py): the three word-timestamp kernels on caller-supplied arrays, each held by its test to the evaluator of include/skw_align.h.
+// Sequences are described by parallel arrays and laid out back to back: sequence i's rows are prow0 = n[0] + .. + n[i-1] onwards, its matrix starts at cell sum of n[j] * kw[j].
+struct AlignHookBufs {
+    std::vector<void*> dev; char* errbuf; const char* who;
+    bool ok(hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "%s: %s", who, hipGetErrorString(e)); return false; } return true; }
+    template <typename T> T* up(const T* host, size_t n) {      // a device copy of host[0 .. n); null on failure
+        void* p = nullptr; if (!ok(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)))) return nullptr;
+        dev.push_back(p);
+        if (n && !ok(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice))) return nullptr;
+        return (T*)p;
+    }
+    ~AlignHookBufs() { for (void* p : dev) hipFree(p); }
+};
+static bool align_hook_seqs(std::vector<SkwAlignSeq>& sq, int n_seq, const int* n, const int* kw, long* rows_total, long* cells) {
+    long r = 0, x = 0;
+    for (int i = 0; i < n_seq; ++i) {
+        if (n[i] < 1 || n[i] > SKW_ALIGN_MAX_ROWS || kw[i] < 1) return false;
+        sq[i].n = n[i]; sq[i].kw = kw[i]; sq[i].prow0 = (int)r; sq[i].xoff = x;
+        r += n[i]; x += (long)n[i] * kw[i];
+    }
+    *rows_total = r; *cells = x;
+    return true;
+}
+// step 1.  Q [q_rows][H*64], K [n_slots][n_ctx][H*64] f16 bit patterns, natural order (frag: the hook lays K out as the fragment-order image, Tpad rows, pad keys k_pad).
+// Sequence i: alignment rows qrow0[i] .. + n[i] of Q, slot[i], n_keys[i] (0: n_ctx).  P: [heads of head_mask][rows_total][n_ctx] f32, uploaded as the caller filled it
+// (a sentinel), so what the kernel leaves alone — keys past n_keys — is visible.
+extern "C" int skw_debug_align_qk(skw_ctx* c, int H, int n_ctx, int n_slots, int q_rows, int frag, const uint16_t* Q_host, const uint16_t* K_host, int k_pad, unsigned head_mask,
+                                  int n_seq, const int* qrow0, const int* n, const int* slot, const int* n_keys, float* P_host) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_align_qk: %s", what); return -1; };
+    if (H < 1 || H > 32 || n_ctx < 1 || n_ctx > SKW_XATTN_MQ_MAX_CTX || n_slots < 1 || n_slots > 64 || q_rows < 1 || n_seq < 1 || n_seq > 4096 || !head_mask) return bad("bad geometry");
+    const int d = H * 64, Tpad = (n_ctx + 31) & ~31, nh = skw_align_popcount(head_mask);
+    std::vector<SkwAlignSeq> sq(n_seq); memset((void*)sq.data(), 0, sizeof(SkwAlignSeq) * n_seq);
+    std::vector<int> kw(n_seq, 1); long rows_total = 0, cells = 0;
+    if (!align_hook_seqs(sq, n_seq, n, kw.data(), &rows_total, &cells)) return bad("a sequence's row count lies outside [1, 256]");
+    for (int i = 0; i < n_seq; ++i) {
+        if (qrow0[i] < 0 || qrow0[i] + n[i] > q_rows || slot[i] < 0 || slot[i] >= n_slots || n_keys[i] < 0 || n_keys[i] > n_ctx) return bad("a sequence's rows, slot or keys lie outside the buffers");
+        sq[i].qrow0 = qrow0[i]; sq[i].slot = slot[i]; sq[i].n_keys = n_keys[i];
+    }
+    const size_t nK = (size_t)n_slots * (frag ? Tpad : n_ctx) * d, nP = (size_t)nh * rows_total * n_ctx;
+    std::vector<uint16_t> k(nK, (uint16_t)k_pad);
+    for (int s = 0; s < n_slots; ++s) for (int i = 0; i < n_ctx; ++i) for (int f = 0; f < d; ++f)
+        k[frag ? (size_t)skw_kfrag_off(s, H, Tpad, i, f & ~7) + (f & 7) : ((size_t)s * n_ctx + i) * d + f] = K_host[((size_t)s * n_ctx + i) * d + f];
+    AlignHookBufs b{{}, errbuf, "skw_debug_align_qk"};
+    const half_t* dq = (const half_t*)b.up(Q_host, (size_t)q_rows * d); const half_t* dk = (const half_t*)b.up(k.data(), nK);
+    SkwAlignSeq* dsq = b.up(sq.data(), (size_t)n_seq); float* dP = b.up(P_host, nP);
+    if (!dq || !dk || !dsq || !dP) return -1;
+    if (!skw_align_qk(dq, d, dk, dsq, n_seq, (int)rows_total, head_mask, H, n_ctx, Tpad, frag, dP, rows_total, n_ctx, c->stream)) return bad("the launcher refused the geometry");
+    if (!b.ok(hipStreamSynchronize(c->stream)) || !b.ok(hipGetLastError()) || !b.ok(hipMemcpy(P_host, dP, nP * 4, hipMemcpyDeviceToHost))) return -1;
+    return 0;
+}
+// steps 2-5.  P_host: the layers' captures back to back, layer l = [nh[l]][rows_total][p_stride] f32; one launch per layer in ascending order, the first starting and the last
+// finishing the sums.  x_host: [cells] f32, uploaded as the caller filled it.
+extern "C" int skw_debug_align_reduce(skw_ctx* c, int n_layers, const int* nh, const float* P_host, int p_stride, int width, int n_seq, const int* n, const int* kw, float* x_host) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_align_reduce: %s", what); return -1; };
+    if (n_layers < 1 || n_layers > SKW_ALIGN_MAX_LAYERS || p_stride < 1 || n_seq < 1 || n_seq > 4096) return bad("bad geometry");
+    std::vector<SkwAlignSeq> sq(n_seq); memset((void*)sq.data(), 0, sizeof(SkwAlignSeq) * n_seq);
+    long rows_total = 0, cells = 0; int kw_max = 0, n_heads = 0;
+    if (!align_hook_seqs(sq, n_seq, n, kw, &rows_total, &cells)) return bad("a sequence's row count lies outside [1, 256], or its crop below 1");
+    for (int i = 0; i < n_seq; ++i) { if (kw[i] > p_stride) return bad("a crop beyond the capture's keys"); kw_max = std::max(kw_max, kw[i]); }
+    for (int l = 0; l < n_layers; ++l) { if (nh[l] < 1 || nh[l] > 32) return bad("a layer without heads"); n_heads += nh[l]; }
+    AlignHookBufs b{{}, errbuf, "skw_debug_align_reduce"};
+    const float* dP = b.up(P_host, (size_t)n_heads * rows_total * p_stride); SkwAlignSeq* dsq = b.up(sq.data(), (size_t)n_seq); float* dx = b.up(x_host, (size_t)cells);
+    double* dacc = nullptr; { std::vector<double> nanfill((size_t)cells, (double)NAN); dacc = b.up(nanfill.data(), (size_t)cells); }      // (no launch may read a sum it did not start)
+    if (!dP || !dsq || !dx || !dacc) return -1;
+    size_t off = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        const bool launched = skw_align_reduce(dP + off, rows_total, p_stride, dsq, n_seq, kw_max, nh[l], width, l == 0, l == n_layers - 1, n_heads, dacc, dx, c->stream);
+        if (!launched) return bad("the launcher refused the geometry");
+        off += (size_t)nh[l] * rows_total * p_stride;
+    }
+    if (!b.ok(hipStreamSynchronize(c->stream)) || !b.ok(hipGetLastError()) || !b.ok(hipMemcpy(x_host, dx, (size_t)cells * 4, hipMemcpyDeviceToHost))) return -1;
+    return 0;
+}
+// steps 6-7, one launch for all n_seq problems.  x_host: the matrices back to back; jump / t0 / t1: [rows_total] int32, uploaded as the caller filled them.
+extern "C" int skw_debug_align_dtw(skw_ctx* c, int n_seq, const int* n, const int* kw, const int* seek_cs, const float* x_host, int32_t* jump, int32_t* t0, int32_t* t1) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_align_dtw: %s", what); return -1; };
+    if (n_seq < 1 || n_seq > 4096) return bad("bad geometry");
+    std::vector<SkwAlignSeq> sq(n_seq); memset((void*)sq.data(), 0, sizeof(SkwAlignSeq) * n_seq);
+    long rows_total = 0, cells = 0; int kw_max = 0, n_max = 0;
+    if (!align_hook_seqs(sq, n_seq, n, kw, &rows_total, &cells)) return bad("a sequence's row count lies outside [1, 256], or its crop below 1");
+    for (int i = 0; i < n_seq; ++i) { sq[i].seek_cs = seek_cs[i]; kw_max = std::max(kw_max, kw[i]); n_max = std::max(n_max, n[i]); }
+    AlignHookBufs b{{}, errbuf, "skw_debug_align_dtw"};
+    const float* dx = b.up(x_host, (size_t)cells); SkwAlignSeq* dsq = b.up(sq.data(), (size_t)n_seq);
+    int *dj = b.up(jump, (size_t)rows_total), *d0 = b.up(t0, (size_t)rows_total), *d1 = b.up(t1, (size_t)rows_total);
+    if (!dx || !dsq || !dj || !d0 || !d1) return -1;
+    if (!skw_align_dtw(dx, dsq, n_seq, n_max, kw_max, dj, d0, d1, c->stream)) return bad("the launcher refused the geometry");
+    if (!b.ok(hipStreamSynchronize(c->stream)) || !b.ok(hipGetLastError())) return -1;
+    if (!b.ok(hipMemcpy(jump, dj, (size_t)rows_total * 4, hipMemcpyDeviceToHost)) || !b.ok(hipMemcpy(t0, d0, (size_t)rows_total * 4, hipMemcpyDeviceToHost)) ||
+        !b.ok(hipMemcpy(t1, d1, (size_t)rows_total * 4, hipMemcpyDeviceToHost))) return -1;
+    return 0;
+}
+// a clip's alignment record checked the way the entry points will check it (include/skw_align.h): 0 good; -1 bad, skw_ctx_last_error names the clip.  Needs no device.
+extern "C" int skw_align_params_check(skw_ctx* c, const skw_align_params* p, int clip) {
+    return skw_align_check_params(p, c->m->hp.n_text_layer, c->m->hp.n_text_head, clip, c->errbuf, 512) ? 0 : -1;
 }
 
 // the launch clock's records (SkwKClk, skw_kernels.h): one clock per (row group, decoder layer) graph node

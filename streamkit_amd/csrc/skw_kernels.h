@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "skw_window_rules.h"
+#include "../../include/skw_align.h"
 
 typedef _Float16 half_t;
 
@@ -236,6 +237,23 @@ struct SkwRowConstraints { float penalty; int32_t ngram, n_bias, pad; int32_t bi
 void skw_dec_constrain(float* logits, int n_vocab, int tok_eot, const SkwRowConstraints* cons, const SkwSeqState* st, const SkwTokenOut* toks, int max_tok, int B, hipStream_t s);
 void skw_debug_force_stream_sampler(int on);   // tests: the streaming sampler (filters the logits row in place) even where the register-resident form applies
 void skw_rng_seed(uint32_t* rng, int n_clips, uint32_t seed, hipStream_t s);   // std::mt19937(seed) for every clip
+
+// ---------------- word timestamps (include/skw_align.h: the contract these three evaluate bit for bit; skw_kernels_align.hip) ----------------
+// One sequence of an alignment pass, in device memory (ragged: every sequence has its own N and Kw).  qrow0: row of `q` holding the sequence's first alignment row (the
+// no_timestamps input position); n: rows N = text tokens + 1; slot: window slot of its cross K; n_keys: its key count (0: n_ctx); kw: the crop (skw_align_kw); prow0: its first row
+// in the capture P and in jump / t0 / t1 (sequences are laid out back to back, ascending); seek_cs: the window's start; xoff: first cell of its N x kw matrix in acc / x.
+struct SkwAlignSeq { int qrow0, n, slot, n_keys, kw, prow0, seek_cs, pad; long xoff; };
+// step 1 for the heads of one layer (head_mask: bit h; hl-th set bit -> P plane hl): P [heads][p_rows][p_stride] f32, keys [0, n_keys) of every row written.  q: [rows][ldq] f16
+// plain (scaled); ck: the layer's cross K as rows [slot][n_ctx][H * 64] or, frag, the fragment-order image (skw_kfrag_off, Tpad).  False (nothing launched): n_ctx above
+// SKW_XATTN_MQ_MAX_CTX, a head outside the model, P too small.
+bool skw_align_qk(const half_t* q, long ldq, const half_t* ck, const SkwAlignSeq* seqs, int n_seq, int rows_total, unsigned head_mask, int H, int n_ctx, int Tpad, int frag,
+                  float* P, long p_rows, long p_stride, hipStream_t s);
+// steps 2-5 for the nh heads P holds, added into acc (f64 [cells]; first: this launch starts the sums); last: x (f32 [cells]) = -(float)(acc / n_heads_total).  Launch the
+// layers in ascending order on one stream.  kw_max: the largest kw among the sequences.
+bool skw_align_reduce(const float* P, long p_rows, long p_stride, const SkwAlignSeq* seqs, int n_seq, int kw_max, int nh, int width, int first, int last, int n_heads_total,
+                      double* acc, float* x, hipStream_t s);
+// steps 6-7: jump / t0 / t1 [rows] at prow0 + r.  False (nothing launched): more than SKW_ALIGN_MAX_ROWS rows, a trace beyond 150 KiB of LDS, or a device that refuses that much LDS.
+bool skw_align_dtw(const float* x, const SkwAlignSeq* seqs, int n_seq, int n_max, int kw_max, int* jump, int* t0, int* t1, hipStream_t s);
 
 // ---------------- resampler (R1) ----------------
 // start / count / offset: [n_chunks + 1] scratch for the per-chunk proposal; flag: 1 int (set when the proposal had to be redone sequentially)

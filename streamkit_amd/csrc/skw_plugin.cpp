@@ -15,7 +15,9 @@
 // reference's hard failure.  INTEGRATION.md section D lists this with the other observable differences.
 #include "../../include/streamkit_native_abi.h"
 #include "../../include/skw_engine.h"
+#include "../../include/skw_align.h"
 #include "skw_decode_rules.h"
+#include "skw_words.h"
 #include "skw_segmenter.h"
 #include "../../include/skw_vad_batch.h"
 #include "skw_silero.h"
@@ -88,7 +90,10 @@ struct WhisperConfig {
     // record's pairs, at most SKW_BIAS_MAX distinct ids together.  The default record asks for nothing.  max_suppress_id / max_bias_id: the largest id each key named (-1: none),
     // so that the check against the loaded model's vocabulary can name the key
     skw_decode_rules rules; int max_suppress_id = -1, max_bias_id = -1;
-    WhisperConfig() { skw_decode_rules_set_default(&rules); }
+    // (additive) timestamp_granularity: "segment" (the reference's output, byte for byte) | "word" (one segment per word: skw_words.h on the token times of skw_full_batch_aligned).
+    // alignment_heads: "top:N" (every head of the top N decoder layers; N = 0: half of them, the default) or explicit [layer, head] pairs in align.head_mask
+    bool word_timestamps = false; int align_top = 0; bool align_explicit = false; skw_align_params align;
+    WhisperConfig() { skw_decode_rules_set_default(&rules); memset(&align, 0, sizeof align); align.median_width = 7; }
 };
 
 // repetition_penalty, no_repeat_ngram_size, suppress_tokens, logit_bias -> cfg->rules; every refusal names its key
@@ -198,6 +203,27 @@ bool parse_config(const char* json, WhisperConfig* cfg, std::string* err) {
     d = cfg->max_batch; if (!num("max_batch", &d)) return false; cfg->max_batch = std::max(1, (int)d);
     if (!boo("use_gpu", &cfg->use_gpu) || !boo("suppress_blank", &cfg->suppress_blank) || !boo("suppress_non_speech_tokens", &cfg->suppress_non_speech_tokens) ||
         !boo("emit_vad_events", &cfg->emit_vad_events) || !boo("flush_tail", &cfg->flush_tail) || !boo("mixed_batch", &cfg->mixed_batch) || !boo("carry_context", &cfg->carry_context)) return false;
+    if (const skw::JsonValue* x = v.get("timestamp_granularity")) {
+        if (x->type != skw::JsonValue::String || (x->str != "segment" && x->str != "word")) { *err = "Invalid config: timestamp_granularity must be \"segment\" or \"word\""; return false; }
+        cfg->word_timestamps = x->str == "word";
+    }
+    if (const skw::JsonValue* x = v.get("alignment_heads")) {
+        const char* msg = "Invalid config: alignment_heads must be \"top:N\" (N >= 1) or an array of [layer, head] pairs (layer 0 .. 31, head 0 .. 31)";
+        memset(cfg->align.head_mask, 0, sizeof cfg->align.head_mask); cfg->align_explicit = false; cfg->align_top = 0;
+        if (x->type == skw::JsonValue::String) {
+            char* end = nullptr; const long n = x->str.compare(0, 4, "top:") == 0 ? strtol(x->str.c_str() + 4, &end, 10) : 0;
+            if (n < 1 || n > 32 || !end || *end) { *err = msg; return false; }
+            cfg->align_top = (int)n;
+        } else if (x->type == skw::JsonValue::Array && !x->arr.empty()) {
+            for (const skw::JsonValue& pr : x->arr) {
+                if (pr.type != skw::JsonValue::Array || pr.arr.size() != 2 || pr.arr[0].type != skw::JsonValue::Number || pr.arr[1].type != skw::JsonValue::Number) { *err = msg; return false; }
+                const double l = pr.arr[0].num, h = pr.arr[1].num;
+                if (l != std::floor(l) || h != std::floor(h) || l < 0 || l > 31 || h < 0 || h > 31) { *err = msg; return false; }
+                cfg->align.head_mask[(int)l] |= 1u << (int)h;
+            }
+            cfg->align_explicit = true;
+        } else { *err = msg; return false; }
+    }
     return parse_decode_rules(v, cfg, err);
 }
 
@@ -235,14 +261,17 @@ struct Job {
     int32_t* context() { return want_ctx ? ctx : nullptr; }
     skw_decode_rules rules; bool constrained = false;      // the owning instance's decoding constraints when the segment was queued; constrained: they are not the default record
     const skw_decode_rules* decode_rules() const { return constrained ? &rules : nullptr; }
+    skw_align_params align; bool want_align = false; skw_token_times times{0, nullptr, nullptr};      // timestamp_granularity "word": the instance's alignment record, the token times
+    const skw_align_params* align_params() const { return want_align ? &align : nullptr; }
     void set_samples(const std::vector<float>& v) {
         n = v.size(); pinned = PinnedPool::get().acquire(n);
         if (pinned.p) memcpy(pinned.p, v.data(), n * sizeof(float)); else pcm_pageable = v;      // (no page-locked memory to be had: the ordinary copy path)
     }
     const float* data() const { return pinned.p ? pinned.p : pcm_pageable.data(); }
-    ~Job() { PinnedPool::get().release(pinned); }
+    ~Job() { PinnedPool::get().release(pinned); skw_token_times_free(&times); }
 };
 std::atomic<long> g_engine_calls{0}, g_batch_jobs{0}, g_mixed_calls{0};      // skw_whisper_plugin_batch_stats
+std::atomic<long> g_align_calls{0};      // engine calls that aligned at least one job (skw_full_batch_aligned)
 std::atomic<long> g_context_calls{0}, g_rules_calls{0};                                        // skw_whisper_plugin_context_stats: engine calls that carried at least one context
 struct SharedEngine {
     skw_model* model = nullptr;
@@ -254,6 +283,7 @@ struct SharedEngine {
     bool multilingual = true;   // the model has language tokens (n_vocab >= 51865); set once at load
     int n_audio_ctx = 1500;     // the model's encoder positions (what audio_ctx "auto" is capped at); set once at load
     int n_text_ctx = 448;       // the model's decoder positions (a prompt takes at most half of them); set once at load
+    int n_text_layer = 4, n_text_head = 6;      // the model's decoder geometry (what alignment_heads is resolved against); set once at load
     int n_vocab = 51865;        // the model's vocabulary (what suppress_tokens / logit_bias ids are checked against); set once at load
     bool mixed = true;          // scheduler: jobs join a batch whatever their parameters (mixed_batch of the instance created most recently; under mu)
     int precision = SKW_PRECISION_EXACT;
@@ -337,14 +367,20 @@ struct SharedEngine {
                     std::vector<const skw_decode_rules*> rls(n); bool any_rules = false, rules_differ = false;
                     for (int i = 0; i < n; ++i) { rls[i] = batch[i]->decode_rules(); any_rules = any_rules || rls[i] != nullptr;
                                                   rules_differ = rules_differ || memcmp(&batch[0]->rules, &batch[i]->rules, sizeof(skw_decode_rules)) != 0; }
-                    rc = any_rules ? skw_full_batch_rules(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), any_ctx ? cxs.data() : nullptr, rls.data(), res.data())
+                    // word timestamps: a batch in which some job asks is ONE aligned call (jobs that do not ask hand in NULL: their rows are the rules call's); otherwise as before
+                    std::vector<const skw_align_params*> als(n); std::vector<skw_token_times> tms(n, skw_token_times{0, nullptr, nullptr}); bool any_align = false;
+                    for (int i = 0; i < n; ++i) { als[i] = batch[i]->align_params(); any_align = any_align || als[i] != nullptr; }
+                    rc = any_align ? skw_full_batch_aligned(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), any_ctx ? cxs.data() : nullptr, any_rules ? rls.data() : nullptr,
+                                                            als.data(), tms.data(), res.data())
+                       : any_rules ? skw_full_batch_rules(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), any_ctx ? cxs.data() : nullptr, rls.data(), res.data())
                        : any_ctx ? skw_full_batch_context(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), cxs.data(), res.data())
                        : differ ? skw_full_batch_mixed(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), res.data())
                                 : skw_full_batch_rng(ctx, &pv[0], ptrs.data(), ns.data(), n, 0, rngs.data(), res.data());
                     g_engine_calls.fetch_add(1); g_batch_jobs.fetch_add(n); if (differ) g_mixed_calls.fetch_add(1); if (any_ctx) g_context_calls.fetch_add(1);
                     if (any_rules) g_rules_calls.fetch_add(1);
-                    if (rc == 0) for (int i = 0; i < n; ++i) batch[i]->result = res[i]; else why = skw_ctx_last_error(ctx);
-                    if (rc != 0 && (differ || rules_differ)) {
+                    if (any_align) g_align_calls.fetch_add(1);
+                    if (rc == 0) for (int i = 0; i < n; ++i) { batch[i]->result = res[i]; batch[i]->times = tms[i]; } else why = skw_ctx_last_error(ctx);
+                    if (rc != 0 && (differ || rules_differ || (any_align && n > 1))) {
                         // A refusal must stay with the request that earned it: jobs of differently configured instances share this call, and one of them being refused
                         // (the engine fails the whole call and hands no generator state back) is no reason for the others to fail.  Each job again, alone, under its own
                         // parameters; every job gets its own outcome.  (Jobs with equal blocks share their configuration, and shared the call before mixed batches too.)
@@ -352,10 +388,12 @@ struct SharedEngine {
                             skw_result one{}; const float* pp = ptrs[i]; uint32_t* rg = rngs[i];
                             int32_t* cx = cxs[i];      // (the refused call wrote no context back: each job's own, as it was queued)
                             const skw_decode_rules* rl = rls[i];
-                            int r1 = rl ? skw_full_batch_rules(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, cx ? &cx : nullptr, &rl, &one)
+                            const skw_align_params* al = als[i]; skw_token_times tm{0, nullptr, nullptr};
+                            int r1 = al ? skw_full_batch_aligned(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, cx ? &cx : nullptr, rl ? &rl : nullptr, &al, &tm, &one)
+                                   : rl ? skw_full_batch_rules(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, cx ? &cx : nullptr, &rl, &one)
                                    : cx ? skw_full_batch_context(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &cx, &one) : skw_full_batch_rng(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &one);
                             g_engine_calls.fetch_add(1);
-                            if (r1 == 0) batch[i]->result = one;
+                            if (r1 == 0) { batch[i]->result = one; batch[i]->times = tm; }
                             else { try { batch[i]->error = skw_ctx_last_error(ctx); } catch (const std::exception&) { r1 = -1; } }      // (a promise is satisfied once)
                             batch[i]->done.set_value(r1);
                         }
@@ -478,6 +516,7 @@ std::shared_ptr<SharedEngine> get_engine(const WhisperConfig& cfg, WhisperPlugin
     if (!eng->model) { *err = ebuf[0] ? ebuf : ("Failed to load Whisper model from '" + cfg.model_path + "'"); return nullptr; }
     g_model_loads.fetch_add(1);
     { skw_hparams hp{}; skw_model_get_hparams(eng->model, &hp); eng->multilingual = hp.n_vocab >= 51865; eng->n_audio_ctx = hp.n_audio_ctx; eng->n_text_ctx = hp.n_text_ctx;
+      eng->n_text_layer = hp.n_text_layer; eng->n_text_head = hp.n_text_head;
       eng->n_vocab = hp.n_vocab; }
     const auto t1 = std::chrono::steady_clock::now();
     eng->batch_limit = cfg.max_batch;
@@ -626,6 +665,11 @@ bool transcribe_and_emit(WhisperPlugin* self, const Emit& em, const skw::Segment
     job->params.audio_ctx = self->config.audio_ctx_auto ? skw_audio_ctx_for_samples((int)job->n, self->engine->n_audio_ctx) : self->config.audio_ctx;
     job->rng = self->rng;
     job->rules = self->config.rules; job->constrained = !skw_decode_rules_is_default(&job->rules);      // (additive) what the instance is configured for now, like audio_ctx
+    if (self->config.word_timestamps) {      // (additive) the instance's alignment record as it is configured now; "top:N" is resolved against the loaded model
+        job->align = self->config.align; job->align.enabled = 1; job->want_align = true;
+        if (!self->config.align_explicit) { const int L = self->engine->n_text_layer;
+            skw_align_heads_top(L, self->engine->n_text_head, self->config.align_top > 0 ? self->config.align_top : std::max(1, L / 2), job->align.head_mask); }
+    }
     build_job_context(self, job->ctx); job->want_ctx = self->config.carry_context || job->ctx[0] > 0;
     if ((int)job->n > SharedEngine::kMaxSamples) { *err = "Whisper inference failed: segment longer than the engine workspace"; return false; }
     std::future<int> fut = job->done.get_future();
@@ -639,6 +683,24 @@ bool transcribe_and_emit(WhisperPlugin* self, const Emit& em, const skw::Segment
     struct Seg { std::string text; uint64_t t0, t1; };
     std::vector<Seg> segs;
     const skw_result& R = job->result;
+    std::vector<Seg> words;      // timestamp_granularity "word": one segment per word (skw_words.h) — a host deserialising TranscriptionSegment would drop any extra key
+    const bool words_ok = job->want_align && job->times.n == R.n_tokens;
+    if (job->want_align && !words_ok) self->log(SK_LOG_WARN, "Word timestamps: %d token times for %d tokens; emitting segments", (int)job->times.n, (int)R.n_tokens);
+    if (words_ok) {
+        std::vector<SkwWordTok> wt; std::vector<std::string> keep; keep.reserve((size_t)R.n_tokens);
+        bool after_ts = true;
+        for (int k = 0; k < R.n_tokens; ++k) {
+            if (job->times.t0[k] < 0) { after_ts = true; continue; }      // (a timestamp token, or a token of a window that was not aligned: the next text token starts a word)
+            int len = 0; const char* tx = skw_model_token_text(self->engine->model, R.tokens[k].id, &len);
+            keep.emplace_back(tx ? tx : "", tx ? (size_t)len : 0);
+            wt.push_back(SkwWordTok{keep.back().data(), (int)keep.back().size(), job->times.t0[k], job->times.t1[k], after_ts});
+            after_ts = false;
+        }
+        for (const SkwWord& w : skw_words_cut(wt.data(), (int)wt.size())) {
+            if (!skw::utf8_valid(w.text)) continue;
+            words.push_back(Seg{w.text, cut.start_time_ms + (uint64_t)(w.start * 10), cut.start_time_ms + (uint64_t)(w.end * 10)});
+        }
+    }
     for (int i = 0; i < R.n_segments; ++i) {
         std::string text(R.text + R.segments[i].text_off, (size_t)R.segments[i].text_len);
         if (!skw::utf8_valid(text)) { self->log(SK_LOG_WARN, "Failed to get segment text: invalid UTF-8"); continue; }
@@ -652,6 +714,7 @@ bool transcribe_and_emit(WhisperPlugin* self, const Emit& em, const skw::Segment
         std::string full; for (size_t i = 0; i < segs.size(); ++i) { if (i) full += " "; full += segs[i].text; }
         // serde_json::to_vec(TranscriptionData) (crates/core/src/types.rs:150-175): field order of the structs
         std::string j = "{\"text\":" + skw::json_quote(full) + ",\"segments\":[";
+        if (words_ok) segs.swap(words);      // (text stays the full text of the segments)
         for (size_t i = 0; i < segs.size(); ++i) {
             if (i) j += ",";
             j += "{\"text\":" + skw::json_quote(segs[i].text) + ",\"start_time_ms\":" + std::to_string(segs[i].t0) + ",\"end_time_ms\":" + std::to_string(segs[i].t1) + ",\"confidence\":null}";
@@ -700,6 +763,8 @@ const char* const kSchema =
     "\"mixed_batch\":{\"type\":\"boolean\",\"description\":\"(additive) segments of instances with different language / suppress_* settings share one GPU batch; false cuts a batch at the first differing job\",\"default\":true},"
     "\"initial_prompt\":{\"type\":\"string\",\"description\":\"(additive) whisper.cpp's initial_prompt: text (domain vocabulary, spellings) every segment is decoded behind; tokenised with whisper.cpp's tokenizer, which puts nothing in front of it (start it with a space to match openai's reference); at most half the model's text context (224 tokens), longer prompts keep their end\",\"default\":\"\"},"
     "\"carry_context\":{\"type\":\"boolean\",\"description\":\"(additive) whisper.cpp's no_context = false: the text of this instance's previous segment conditions the next one; cleared when model_path, language or initial_prompt change\",\"default\":false},"
+    "\"timestamp_granularity\":{\"type\":\"string\",\"description\":\"(additive) segment: the reference's output; word: one segment per word, timed by cross-attention DTW (whisper.cpp dtw_token_timestamps, openai word_timestamps); text stays the full text\",\"default\":\"segment\",\"enum\":[\"segment\",\"word\"]},"
+    "\"alignment_heads\":{\"description\":\"(additive) the cross-attention heads word timestamps are read from: top:N (every head of the top N decoder layers; default: half the layers) or an array of [layer, head] pairs\",\"default\":\"top:half\"},"
     "\"repetition_penalty\":{\"type\":\"number\",\"description\":\"(additive) repetition penalty on the text tokens the current window has already produced (timestamps and the prompt are exempt): a logit x becomes x / p when positive, x * p when negative, once per distinct token; 1.0 = off. As in faster-whisper / transformers\",\"default\":1.0,\"exclusiveMinimum\":0.0},"
     "\"no_repeat_ngram_size\":{\"type\":\"integer\",\"description\":\"(additive) no n-gram of this many text tokens occurs twice within a window (timestamps in between are skipped); 0 = off\",\"default\":0,\"minimum\":0},"
     "\"suppress_tokens\":{\"type\":\"array\",\"items\":{\"type\":\"integer\",\"minimum\":0},\"description\":\"(additive) token ids that are never produced (the id-level form of whisper.cpp's suppress_regex); with logit_bias at most 256 distinct ids, each below the model's vocabulary size\",\"default\":[]},"
@@ -863,6 +928,8 @@ extern "C" void skw_whisper_plugin_batch_stats(long* engine_calls, long* jobs, l
 extern "C" void skw_whisper_plugin_context_stats(long* context_calls) { if (context_calls) *context_calls = g_context_calls.load(); }
 // additive, for tests: engine calls that carried at least one job with decoding constraints (skw_full_batch_rules); a process whose instances set none of the four keys stays at 0
 extern "C" void skw_whisper_plugin_rules_stats(long* rules_calls) { if (rules_calls) *rules_calls = g_rules_calls.load(); }
+// additive, for tests: engine calls that aligned at least one job (skw_full_batch_aligned); a process whose instances all keep timestamp_granularity "segment" stays at 0
+extern "C" void skw_whisper_plugin_align_stats(long* align_calls) { if (align_calls) *align_calls = g_align_calls.load(); }
 // additive, for tests: the node's own parsing of repetition_penalty / no_repeat_ngram_size / suppress_tokens / logit_bias out of a parameter object, and the check of the ids against
 // a vocabulary of n_vocab entries (what create_instance and update_params apply once the model is known).  0 and the record, or -1 and the message.  No GPU is touched.
 extern "C" int skw_whisper_plugin_parse_rules(const char* params_json, int n_vocab, skw_decode_rules* out, char* err, size_t errlen) {

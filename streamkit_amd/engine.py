@@ -219,8 +219,46 @@ def lib():
         L.skw_debug_q8_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.skw_debug_self_attn_q8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10
         L.skw_debug_gemm16_epi.argtypes = [C.c_void_p, C.POINTER(Gemm16EpiArgs)]
+        L.skw_debug_align_qk.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_int] + [C.c_void_p] * 5
+        L.skw_debug_align_reduce.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.skw_debug_align_dtw.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        L.skw_align_params_check.argtypes = [C.c_void_p, C.POINTER(AlignParams), C.c_int]
+        L.skw_full_batch_aligned.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(TokenTimes), C.POINTER(Result)]
+        L.skw_align_batch.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_void_p), C.POINTER(TokenTimes)]
+        L.skw_token_times_free.argtypes = [C.POINTER(TokenTimes)]
         _LIB = L
     return _LIB
+
+
+class AlignParams(C.Structure):        # skw_align_params (include/skw_align.h)
+    _fields_ = [("enabled", C.c_int32), ("median_width", C.c_int32), ("head_mask", C.c_uint32 * 32)]
+
+
+class TokenTimes(C.Structure):         # skw_token_times
+    _fields_ = [("n", C.c_int32), ("t0", C.POINTER(C.c_int64)), ("t1", C.POINTER(C.c_int64))]
+
+
+def align_params(head_mask=None, median_width=7, top=None, hp=None):
+    """An enabled skw_align_params.  head_mask: one uint32 per decoder layer (bit h = head h), or [(layer, head), ...]; or top=N with hp: every head of the top N decoder layers
+    (whisper.cpp's N_TOP_MOST; N = n_text_layer // 2 is openai's default for a model that names no heads)."""
+    p = AlignParams(enabled=1, median_width=int(median_width))
+    if top is not None:
+        head_mask = [((1 << hp.n_text_head) - 1 if hp.n_text_layer - min(top, hp.n_text_layer) <= l < hp.n_text_layer else 0) for l in range(hp.n_text_layer)]
+    if head_mask and isinstance(head_mask[0], (tuple, list)):
+        for l, h in head_mask:
+            p.head_mask[l] |= 1 << h
+    else:
+        for l, w in enumerate(head_mask or []):
+            p.head_mask[l] = int(w)
+    return p
+
+
+def _times_out(tt):
+    out = [(int(tt.t0[k]), int(tt.t1[k])) for k in range(tt.n)]
+    lib().skw_token_times_free(C.byref(tt))
+    return out
 
 
 class Gemm16EpiArgs(C.Structure):      # struct skw_gemm16_epi_args (skw_engine.hip)
@@ -350,7 +388,7 @@ class Context:
         lib().skw_full_default_params(C.byref(p))
         return p
 
-    def full_batch(self, clips, params=None, device_ptrs=None, n_samples=None, trace=False, forced=None, rng_states=None, contexts=None, rules=None):
+    def full_batch(self, clips, params=None, device_ptrs=None, n_samples=None, trace=False, forced=None, rng_states=None, contexts=None, rules=None, align=None):
         """clips: list of 1-D float32 numpy arrays (host), or device_ptrs + n_samples for HBM-resident PCM.
         trace=True (or forced=[per-clip int32 id sequences]): skw_full_batch_traced — returns (results, traces), traces[i] a structured
         array (TRACE_DT) with one record per sampling decision of clip i; with `forced` the decoder is fed those ids (teacher forcing).
@@ -363,8 +401,13 @@ class Context:
         skw_full_batch_traced_context.
         rules=[DecodeRules or None per clip]: skw_full_batch_rules — each clip's decoding constraints (repetition penalty, no-repeat n-gram, bias / suppression); None or a default
         record leaves the clip as it is without.  May be combined with per-clip params, rng_states and contexts; with trace / forced it raises ValueError.  The records are checked
-        here as the engine checks them (ValueError naming the clip)."""
+        here as the engine checks them (ValueError naming the clip).
+        align=[AlignParams or None per clip] (align_params()): skw_full_batch_aligned — the clips that ask get word timestamps: each result gains "token_times", one (t0, t1) in
+        centiseconds per token of "tokens", (-1, -1) for timestamp tokens and for clips that did not ask.  May be combined with per-clip params, rng_states, contexts and rules; not
+        with trace / forced."""
         per_clip = isinstance(params, (list, tuple))
+        if align is not None and (trace or forced is not None):
+            raise ValueError("full_batch: align cannot be combined with trace / forced")
         if rules is not None:
             if trace or forced is not None:
                 raise ValueError("full_batch: rules cannot be combined with trace / forced (there is no traced entry point with decoding constraints)")
@@ -396,7 +439,19 @@ class Context:
                 raise ValueError("full_batch: %d contexts for %d clips" % (len(contexts), n))
             assert all(x is None or (x.dtype == np.int32 and x.size == CONTEXT_WORDS and x.flags["C_CONTIGUOUS"]) for x in contexts)
             cp = (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in contexts])
-        if rules is not None:
+        times = None
+        if align is not None:
+            if len(align) != n:
+                raise ValueError("full_batch: %d alignment records for %d clips" % (len(align), n))
+            sp = None
+            if rng_states is not None:
+                assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
+                sp = (C.c_void_p * n)(*[None if s is None else s.ctypes.data for s in rng_states])
+            pp = p if per_clip else (FullParams * n)(*([p] * n))
+            ap = (C.c_void_p * n)(*[None if a is None else C.addressof(a) for a in align])
+            times = (TokenTimes * n)()
+            self._check(lib().skw_full_batch_aligned(self.h, pp, ptrs, ns, n, on_dev, sp, cp, rules_ptr if rules is not None else None, ap, times, res))
+        elif rules is not None:
             sp = None
             if rng_states is not None:
                 assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
@@ -437,9 +492,27 @@ class Context:
         out = [_result_to_dict(res[i]) for i in range(n)]
         for i in range(n):
             lib().skw_result_free(C.byref(res[i]))
+        if times is not None:
+            for i in range(n):
+                out[i]["token_times"] = _times_out(times[i])
         if trace or forced is not None:
             return out, traces
         return out
+
+    def align_batch(self, clips, texts, align, params=None):
+        """skw_align_batch: forced alignment of given text — clips[i] (at most 30 s) against the text token ids texts[i]; nothing is decoded.
+        -> per clip a list of (t0, t1) in centiseconds, one per given token."""
+        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        n = len(clips)
+        per_clip = isinstance(params, (list, tuple))
+        p = (FullParams * n)(*params) if per_clip else (FullParams * n)(*([params or self.default_params()] * n))
+        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips]); ns = (C.c_int32 * n)(*[c.size for c in clips])
+        keep = [np.ascontiguousarray(t, dtype=np.int32) for t in texts]
+        tp = (C.c_void_p * n)(*[k.ctypes.data for k in keep]); tn = (C.c_int32 * n)(*[k.size for k in keep])
+        ap = (C.c_void_p * n)(*[None if a is None else C.addressof(a) for a in align])
+        times = (TokenTimes * n)()
+        self._check(lib().skw_align_batch(self.h, p, ptrs, ns, n, 0, tp, tn, ap, times))
+        return [_times_out(times[i]) for i in range(n)]
 
     def set_prompt_pass(self, on):
         """test hook (skw_debug_set_prompt_pass): 0 = the prompt is stepped token by token instead of evaluated in one pass"""
@@ -459,7 +532,7 @@ class Context:
 
     def profile_get(self):
         out = {}
-        for cls in range(10):
+        for cls in range(13):
             name = C.create_string_buffer(64); cnt = C.c_long(); ms = C.c_double(); fl = C.c_double(); by = C.c_double()
             if lib().skw_ctx_profile_get(self.h, cls, name, 64, C.byref(cnt), C.byref(ms), C.byref(fl), C.byref(by)) == 0:
                 out[name.value.decode()] = dict(count=cnt.value, ms=ms.value, flops=fl.value, bytes=by.value)
@@ -696,6 +769,50 @@ class Context:
         self._check(lib().skw_debug_self_attn_q8(self.h, H, n_text_ctx, rows, Q.ctypes.data, K.ctypes.data, V.ctypes.data, pos.ctypes.data, ptr(active), ptr(seq),
                                                  out.ctypes.data, q.ctypes.data, dT.ctypes.data, sT.ctypes.data))
         return out, q, dT, sT
+
+    # ---- word timestamps: the three kernels of skw_kernels_align.hip on caller-supplied arrays (include/skw_align.h is what they evaluate)
+    def align_qk(self, H, n_ctx, Q, K, head_mask, qrow0, n, slot, n_keys, frag=False, k_pad=0x7E00, sentinel=np.float32(-7.0)):
+        """k_align_qk (skw_debug_align_qk).  Q [rows][H*64], K [slots][n_ctx][H*64] float16, natural order; head_mask: the layer's alignment heads (bit h); sequence i: rows
+        qrow0[i] .. + n[i] of Q, cross K of slot[i], n_keys[i] keys (0: n_ctx).  -> P f32 [heads][sum n][n_ctx], `sentinel` where nothing was written."""
+        d = H * 64
+        bits = lambda a: np.ascontiguousarray(a.view(np.uint16) if a.dtype == np.float16 else a, dtype=np.uint16)
+        Q = bits(Q); K = bits(K)
+        qrow0, n, slot, n_keys = (np.ascontiguousarray(a, dtype=np.int32) for a in (qrow0, n, slot, n_keys))
+        assert K.shape[1:] == (n_ctx, d) and Q.shape[1] == d and qrow0.size == n.size == slot.size == n_keys.size
+        P = np.full((bin(head_mask).count("1"), int(n.sum()), n_ctx), sentinel, np.float32)
+        self._check(lib().skw_debug_align_qk(self.h, H, n_ctx, K.shape[0], Q.shape[0], 1 if frag else 0, Q.ctypes.data, K.ctypes.data, int(k_pad), int(head_mask), n.size,
+                                             qrow0.ctypes.data, n.ctypes.data, slot.ctypes.data, n_keys.ctypes.data, P.ctypes.data))
+        return P
+
+    def align_reduce(self, P_layers, n, kw, width=7, sentinel=np.float32(-7.0)):
+        """k_align_reduce (skw_debug_align_reduce), one launch per layer.  P_layers: per layer f32 [heads][sum n][keys]; sequences of n[i] rows cropped to kw[i] keys.
+        -> the sequences' N x Kw matrices back to back, flat f32."""
+        P_layers = [np.ascontiguousarray(P, dtype=np.float32) for P in P_layers]
+        n, kw = np.ascontiguousarray(n, dtype=np.int32), np.ascontiguousarray(kw, dtype=np.int32)
+        rows, stride = P_layers[0].shape[1:]
+        assert all(P.shape[1:] == (rows, stride) for P in P_layers) and rows == int(n.sum()) and n.size == kw.size
+        nh = np.array([P.shape[0] for P in P_layers], np.int32)
+        Pall = np.concatenate([P.reshape(-1) for P in P_layers])
+        x = np.full(int((n.astype(np.int64) * kw).sum()), sentinel, np.float32)
+        self._check(lib().skw_debug_align_reduce(self.h, len(P_layers), nh.ctypes.data, Pall.ctypes.data, stride, int(width), n.size, n.ctypes.data, kw.ctypes.data, x.ctypes.data))
+        return x
+
+    def align_dtw(self, xs, seek_cs=None, sentinel=-77):
+        """k_align_dtw (skw_debug_align_dtw): one launch over the f32 matrices xs (each [N][Kw]).  -> (jump, t0, t1), int32 [sum N]"""
+        xs = [np.ascontiguousarray(x, dtype=np.float32) for x in xs]
+        n = np.array([x.shape[0] for x in xs], np.int32); kw = np.array([x.shape[1] for x in xs], np.int32)
+        seek = np.zeros(len(xs), np.int32) if seek_cs is None else np.ascontiguousarray(seek_cs, dtype=np.int32)
+        flat = np.concatenate([x.reshape(-1) for x in xs])
+        jump, t0, t1 = (np.full(int(n.sum()), sentinel, np.int32) for _ in range(3))
+        self._check(lib().skw_debug_align_dtw(self.h, len(xs), n.ctypes.data, kw.ctypes.data, seek.ctypes.data, flat.ctypes.data, jump.ctypes.data, t0.ctypes.data, t1.ctypes.data))
+        return jump, t0, t1
+
+    def align_params_check(self, enabled, median_width, head_mask, clip=0):
+        """a clip's alignment record against this context's model (skw_align_params_check): None when good, else the message"""
+        p = AlignParams(enabled=int(enabled), median_width=int(median_width))
+        for l, w in enumerate(head_mask):
+            p.head_mask[l] = int(w)
+        return None if lib().skw_align_params_check(self.h, C.byref(p), int(clip)) == 0 else lib().skw_ctx_last_error(self.h).decode()
 
     def math(self, kind, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
