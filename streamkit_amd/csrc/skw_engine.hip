@@ -2286,6 +2286,28 @@ extern "C" int skw_debug_gemm16_out(skw_ctx* c, int kernel, int M, int N, int K,
     return 0;
 }
 
+// The packing the attention hooks below share: natural-order f16 bit patterns -> what a kernel reads.  Q [n_slots][n_ctx][H*64] into per-head rows of stride Tpad (qheads; a plain
+// Q is copied as it stands, q.size() halves), K / V [n_slots][n_ctx][H*64] into per-head rows (kheads), the fragment-order images (kfrag / vfrag), plain rows (K otherwise; vrows) or
+// V^T per head in kperm key order (V otherwise).  q / k / v arrive sized and filled with the caller's pad patterns; only keys below fill_from[slot] are written.
+struct AttnHookLayout { int qheads, kheads, kfrag, vrows, vfrag; };
+static void attn_hook_pack(const AttnHookLayout& L, int H, int n_ctx, int n_slots, const uint16_t* Q_host, const uint16_t* K_host, const uint16_t* V_host, const int* fill_from,
+                           std::vector<uint16_t>& q, std::vector<uint16_t>& k, std::vector<uint16_t>& v) {
+    const int d = H * 64, Tpad = (n_ctx + 31) & ~31;
+    if (L.qheads) { for (int s = 0; s < n_slots; ++s) for (int i = 0; i < n_ctx; ++i) for (int n = 0; n < d; ++n)
+                        q[(((size_t)s * H + (n >> 6)) * Tpad + i) * 64 + skw_kperm(n & 63)] = Q_host[((size_t)s * n_ctx + i) * d + n]; }
+    else memcpy(q.data(), Q_host, q.size() * 2);
+    for (int s = 0; s < n_slots; ++s) for (int i = 0; i < fill_from[s]; ++i) for (int n = 0; n < d; ++n) {
+        const uint16_t kv = K_host[((size_t)s * n_ctx + i) * d + n], vv = V_host[((size_t)s * n_ctx + i) * d + n];
+        const int p = skw_kperm(i);
+        if (L.kheads) k[(((size_t)s * H + (n >> 6)) * Tpad + i) * 64 + skw_kperm(n & 63)] = kv;
+        else if (L.kfrag) k[skw_kfrag_off(s, H, Tpad, i, n & ~7) + (n & 7)] = kv;
+        else k[((size_t)s * n_ctx + i) * d + n] = kv;
+        if (L.vrows) v[((size_t)s * n_ctx + i) * d + n] = vv;
+        else if (L.vfrag) v[skw_vtfrag_off(s, H, Tpad, n, p & ~7) + (p & 7)] = vv;
+        else v[((size_t)s * d + n) * Tpad + p] = vv;
+    }
+}
+
 // tests (tests/test_gpu_attn16.py): one f16_mfma attention launcher on host-supplied operands, to be held to a float64 softmax(Q K^T) V kernel by kernel.  Q [rows][H*64], K / V
 // [slot][n_ctx][H*64] arrive as f16 bit patterns in NATURAL order; this packs them into what the kernel reads (per-head rows of stride Tpad, V^T, the fragment-order images), launches
 // through the public launcher (the template dispatch is part of what is tested) and returns the output un-permuted as f32 [rows][H*64].
@@ -2332,19 +2354,7 @@ extern "C" int skw_debug_attn16(skw_ctx* c, int form, int H, int n_ctx, int n_sl
     const size_t nQ = form == 0 ? (size_t)n_slots * Tpad * d : (size_t)rows * d, nK = (size_t)n_slots * kkeys * d, nV = (size_t)n_slots * vkeys * d;
     const size_t nO = (size_t)(ofrag ? (orows + 15) & ~15 : orows) * d;
     std::vector<uint16_t> q(nQ, (uint16_t)k_pad), k(nK, (uint16_t)k_pad), v(nV, (uint16_t)v_pad), o(nO, (uint16_t)sentinel);
-    if (form == 0) { for (int s = 0; s < n_slots; ++s) for (int i = 0; i < n_ctx; ++i) for (int n = 0; n < d; ++n)
-                         q[(((size_t)s * H + (n >> 6)) * Tpad + i) * 64 + skw_kperm(n & 63)] = Q_host[((size_t)s * n_ctx + i) * d + n]; }
-    else memcpy(q.data(), Q_host, nQ * 2);
-    for (int s = 0; s < n_slots; ++s) for (int i = 0; i < fill_from[s]; ++i) for (int n = 0; n < d; ++n) {
-        const uint16_t kv = K_host[((size_t)s * n_ctx + i) * d + n], vv = V_host[((size_t)s * n_ctx + i) * d + n];
-        const int p = skw_kperm(i);
-        if (kheads) k[(((size_t)s * H + (n >> 6)) * Tpad + i) * 64 + skw_kperm(n & 63)] = kv;
-        else if (kfrag) k[skw_kfrag_off(s, H, Tpad, i, n & ~7) + (n & 7)] = kv;
-        else k[((size_t)s * n_ctx + i) * d + n] = kv;
-        if (vrows) v[((size_t)s * n_ctx + i) * d + n] = vv;
-        else if (vfrag) v[skw_vtfrag_off(s, H, Tpad, n, p & ~7) + (p & 7)] = vv;
-        else v[((size_t)s * d + n) * Tpad + p] = vv;
-    }
+    attn_hook_pack(AttnHookLayout{form == 0, kheads, kfrag, vrows, vfrag}, H, n_ctx, n_slots, Q_host, K_host, V_host, fill_from, q, k, v);
     std::vector<SkwSeqState> st(rows); memset((void*)st.data(), 0, sizeof(SkwSeqState) * rows);
     if (form >= 2) for (int b = 0; b < rows; ++b) {
         st[b].active = active ? active[b] : 1; st[b].pad = seq ? seq[b] : b; st[b].cur_pos = form == 4 ? count[b] : 0; st[b].n_keys = (form != 4 && count) ? count[b] : 0;
@@ -2372,6 +2382,65 @@ extern "C" int skw_debug_attn16(skw_ctx* c, int form, int H, int n_ctx, int n_sl
     cleanup();
     for (int r = 0; r < orows; ++r) for (int n = 0; n < d; ++n)
         out_host[(size_t)r * d + n] = skw_f16_to_f32(o[ofrag ? (size_t)skw_afrag_off(r, skw_kperm(n), d) : (size_t)r * d + skw_kperm(n)]);
+    return 0;
+}
+
+// tests (tests/test_gpu_attn_exact.py): the two exact-precision attention launchers that skw_debug_xattn_exact does not reach, on host-supplied operands, to be held bit for bit to
+// the numpy restatement of the contract (tests/attn_exact_ref_lib.py).  Operands, fill_from, k_pad / v_pad and the sentinel are skw_debug_attn16's (whose packing this shares).
+//   form 0  skw_attn_encoder — the launcher, so its choice between k_attn_encoder and k_attn_encoder_v3 is part of what is tested; *kernel_id is what skw_attn_encoder_kernel, the
+//           function the launcher branches on, answers for the launch.  Q is [slot][n_ctx][H*64]; slot_k null: out rows = n_slots * n_ctx; given ([n_slots], each in 1 .. n_ctx):
+//           n_slots * out_rows (out_rows 0: n_ctx)
+//   form 1  skw_dec_self_attn, fastv = 0, no q8 output (k_dec_attn<7>): Q [rows][H*64], K / V the caches [slot][n_ctx = n_text_ctx][H*64]; pos [rows] (required), active / seq
+//           [rows] or null, reaching the kernel as fields of a SkwSeqState array; *kernel_id = -1
+// out: orows x H*64 elements of 2 bytes (f16 bits), or 4 (f32_out: the kernel's unrounded f32 rows).  raw: the f16 rows as the kernel leaves them (kperm order); otherwise un-permuted.
+extern "C" int skw_debug_attn_exact(skw_ctx* c, int form, int H, int n_ctx, int n_slots, int rows, int f32_out, int raw, int out_rows, const uint16_t* Q_host, const uint16_t* K_host,
+                                    const uint16_t* V_host, const int* fill_from, int k_pad, int v_pad, const int* slot_k, const int* active, const int* seq, const int* pos, int sentinel,
+                                    void* out_host, int* kernel_id) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_attn_exact: %s", what); return -1; };
+    if (form < 0 || form > 1 || H < 1 || H > 32 || n_ctx < 1 || n_ctx > 4096 || n_slots < 1 || n_slots > 64 || rows < 1 || rows > 4096 || !fill_from || !Q_host || !K_host || !V_host ||
+        !out_host || !kernel_id) return bad("bad geometry");
+    const int d = H * 64, Tpad = (n_ctx + 31) & ~31, esz = f32_out ? 2 : 1;      // (output element size in halves)
+    for (int s = 0; s < n_slots; ++s) if (fill_from[s] < 0 || fill_from[s] > n_ctx) return bad("fill_from outside [0, n_ctx]");
+    int orows = rows;
+    if (form == 0) {
+        if (slot_k) for (int s = 0; s < n_slots; ++s) if (slot_k[s] < 1 || slot_k[s] > n_ctx || (out_rows && out_rows < slot_k[s])) return bad("slot_k outside [1, n_ctx] or above out_rows");
+        if (!slot_k && out_rows && out_rows != n_ctx) return bad("out_rows needs slot_k");
+        if (out_rows < 0 || out_rows > 4096) return bad("out_rows outside [0, 4096]");
+        orows = n_slots * (out_rows ? out_rows : n_ctx);
+    } else {
+        if (n_ctx > 7 * 64 || !pos) return bad("the self-attention form needs pos and n_text_ctx <= 448");
+        for (int b = 0; b < rows; ++b) {
+            const int s = seq ? seq[b] : b;
+            if (s < 0 || s >= n_slots || pos[b] < 0 || pos[b] >= n_ctx) return bad("a row's sequence or pos lies outside the caches");
+        }
+    }
+    const size_t nQ = form == 0 ? (size_t)n_slots * Tpad * d : (size_t)rows * d, nK = (size_t)n_slots * (form == 0 ? Tpad : n_ctx) * d, nV = nK, nO = (size_t)orows * d * esz;
+    std::vector<uint16_t> q(nQ, (uint16_t)k_pad), k(nK, (uint16_t)k_pad), v(nV, (uint16_t)v_pad), o(nO, (uint16_t)sentinel);
+    attn_hook_pack(AttnHookLayout{form == 0, form == 0, 0, form == 1, 0}, H, n_ctx, n_slots, Q_host, K_host, V_host, fill_from, q, k, v);
+    std::vector<SkwSeqState> st(rows); memset((void*)st.data(), 0, sizeof(SkwSeqState) * rows);
+    if (form == 1) for (int b = 0; b < rows; ++b) { st[b].active = active ? active[b] : 1; st[b].pad = seq ? seq[b] : b; st[b].cur_pos = pos[b]; }
+    half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr; SkwSeqState* dst = nullptr; int* dmeta = nullptr;
+    auto cleanup = [&]() { hipFree(dq); hipFree(dk); hipFree(dv); hipFree(dout); hipFree(dst); hipFree(dmeta); };
+    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_attn_exact: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
+    if (!chk(hipMalloc((void**)&dq, nQ * 2)) || !chk(hipMalloc((void**)&dk, nK * 2)) || !chk(hipMalloc((void**)&dv, nV * 2)) || !chk(hipMalloc((void**)&dout, nO * 2))) return -1;
+    if (!chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * rows)) || !chk(hipMalloc((void**)&dmeta, sizeof(int) * 64))) return -1;
+    if (!chk(hipMemcpy(dq, q.data(), nQ * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dk, k.data(), nK * 2, hipMemcpyHostToDevice))) return -1;
+    if (!chk(hipMemcpy(dv, v.data(), nV * 2, hipMemcpyHostToDevice))) return -1;
+    if (!chk(hipMemcpy(dout, o.data(), nO * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * rows, hipMemcpyHostToDevice))) return -1;
+    int meta[64] = {0};
+    if (slot_k) for (int s = 0; s < n_slots; ++s) meta[s] = slot_k[s];
+    if (!chk(hipMemcpy(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice))) return -1;
+    *kernel_id = -1;
+    if (form == 0) {
+        *kernel_id = skw_attn_encoder_kernel(n_ctx, Tpad, false, slot_k != nullptr);
+        skw_attn_encoder(dq, dk, dv, dout, d, n_slots, H, n_ctx, Tpad, c->stream, nullptr, nullptr, f32_out ? 1 : 0, slot_k ? dmeta : nullptr, out_rows);
+    } else skw_dec_self_attn(dq, dk, dv, &dst[0].cur_pos, rows, H, d, n_ctx, dout, active ? &dst[0].active : nullptr, c->stream, f32_out ? 1 : 0, SkwQ8Out{nullptr, nullptr, nullptr, 0},
+                             seq ? &dst[0].pad : nullptr, 0, 0);
+    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(o.data(), dout, nO * 2, hipMemcpyDeviceToHost))) return -1;
+    cleanup();
+    if (f32_out || raw) memcpy(out_host, o.data(), nO * 2);
+    else for (int r = 0; r < orows; ++r) for (int n = 0; n < d; ++n) ((uint16_t*)out_host)[(size_t)r * d + n] = o[(size_t)r * d + skw_kperm(n)];
     return 0;
 }
 

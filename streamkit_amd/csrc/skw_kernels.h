@@ -120,6 +120,9 @@ void skw_layernorm(const float* x, int rows, int d, const float* w, const float*
 // f32_out: `out` is a float [B*n_ctx][ld_out] buffer, natural order, unrounded
 void skw_attn_encoder(const half_t* Qh, const half_t* Kh, const half_t* Vt, half_t* out, long ld_out, int B, int H, int n_ctx, int Tpad, hipStream_t s,
     float* dbg = nullptr, float* dbg2 = nullptr, int f32_out = 0, const int* slot_k = nullptr /* as skw_attn_encoder16 */, int out_rows = 0);
+// the kernel skw_attn_encoder launches for these arguments: k_attn_encoder (three passes; any context length, the stage taps, the per-clip key counts) or k_attn_encoder_v3<94, 72>
+enum SkwAttnEncKernel : int { SKW_ATTN_ENC_3PASS = 0, SKW_ATTN_ENC_V3 };
+int skw_attn_encoder_kernel(int n_ctx, int Tpad, bool taps, bool slot_k);
 
 // log-mel front end
 struct SkwMelTables { const float* hann; const float* sin_t; const float* cos_t; const float* filters; int n_mel; int n_fft_bins;

@@ -620,11 +620,14 @@ __global__ __launch_bounds__(256, 1) void k_attn_encoder_v3(const half_t* Qh, co
         }
 }
 
+int skw_attn_encoder_kernel(int n_ctx, int Tpad, bool taps, bool slot_k) {
+    // Whisper's 1500-frame context; k_attn_encoder is the form that carries the stage taps (layer 0 of a tapped run) and any other context length
+    return (Tpad == 1504 && Tpad - n_ctx < 16 && !taps && !slot_k) ? SKW_ATTN_ENC_V3 : SKW_ATTN_ENC_3PASS;
+}
 void skw_attn_encoder(const half_t* Qh, const half_t* Kh, const half_t* Vt, half_t* out, long ld_out, int B, int H, int n_ctx, int Tpad, hipStream_t s, float* dbg, float* dbg2, int f32_out,
                       const int* slot_k, int out_rows) {
-    // Whisper's 1500-frame context; k_attn_encoder below is the form that carries the stage taps (layer 0 of a tapped run) and any other context length
     if (!out_rows) out_rows = n_ctx;
-    if (Tpad == 1504 && Tpad - n_ctx < 16 && !dbg && !slot_k) {
+    if (skw_attn_encoder_kernel(n_ctx, Tpad, dbg != nullptr, slot_k != nullptr) == SKW_ATTN_ENC_V3) {
         const int qtiles = (n_ctx + 63) / 64;
         constexpr int RT3 = 72;
         hipLaunchKernelGGL((k_attn_encoder_v3<94, RT3>), dim3(qtiles * H * B), dim3(256), (size_t)4 * (94 - RT3) * 64 * 16, s, Qh, Kh, Vt, out, ld_out, H, n_ctx, Tpad,

@@ -214,6 +214,7 @@ def lib():
         L.skw_debug_switch_get.argtypes = [C.c_char_p]
         L.skw_debug_switch_set.argtypes = [C.c_char_p, C.c_int]
         L.skw_debug_attn16.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+        L.skw_debug_attn_exact.argtypes = [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.POINTER(C.c_int)]
         L.skw_debug_gemm_q8.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.POINTER(C.c_int)])
         L.skw_debug_q8_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -692,6 +693,39 @@ class Context:
                                                 int(k_pad), int(v_pad), None if slot_k is None else slot_k.ctypes.data, row0.size, row0.ctypes.data, nq.ctypes.data, slot.ctypes.data,
                                                 int(sentinel), out.ctypes.data))
         return out
+
+    ATTN_EXACT_FORMS = {"encoder": 0, "self": 1}
+    ATTN_ENC_KERNELS = {0: "k_attn_encoder", 1: "k_attn_encoder_v3"}
+
+    def attn_exact(self, form, H, n_ctx, Q, K, V, fill_from, f32_out=False, raw=False, k_pad=0x7E00, v_pad=0x7E00, slot_k=None, out_rows=0, active=None, seq=None, pos=None,
+                   sentinel=0x5A5A):
+        """The exact precision's encoder attention or decoder self attention on caller-supplied operands (skw_debug_attn_exact, skw_engine.hip), through the public launcher.
+        Operands, fill_from, the pads and the sentinel as attn16.  form "encoder": Q [slots][n_ctx][H*64] (slot_k, out_rows); "self": Q [rows][H*64], K / V the caches
+        [slots][n_text_ctx][H*64], pos per row (active, seq).  -> (out, kernel): out uint16 [rows][H*64] (f16 bits; kperm order when raw, else natural) or, f32_out, uint32
+        [rows][H*64] (the f32 rows' bits); kernel: the encoder kernel the launcher chose (ATTN_ENC_KERNELS), None for "self"."""
+        d = H * 64
+        bits = lambda a: np.ascontiguousarray(a.view(np.uint16) if a.dtype == np.float16 else a, dtype=np.uint16)
+        ints = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        Q = bits(Q); K = bits(K); V = bits(V)
+        n_slots = K.shape[0]
+        assert K.shape == (n_slots, n_ctx, d) and V.shape == K.shape and Q.shape[-1] == d
+        f = self.ATTN_EXACT_FORMS[form]
+        fill_from, slot_k, active, seq, pos = (ints(a) for a in (fill_from, slot_k, active, seq, pos))
+        assert fill_from.size == n_slots and (slot_k is None or slot_k.size == n_slots)
+        if f == 0:
+            assert Q.shape == K.shape and active is None and seq is None and pos is None
+            rows = 1; orows = n_slots * (int(out_rows) if out_rows else n_ctx)
+        else:
+            rows = orows = Q.shape[0]
+            assert Q.shape == (rows, d) and pos is not None and slot_k is None and not out_rows
+            for a in (active, seq, pos):
+                assert a is None or a.size == rows
+        out = np.empty((orows, d), dtype=np.uint32 if f32_out else np.uint16)
+        kid = C.c_int(-1)
+        self._check(lib().skw_debug_attn_exact(self.h, f, H, n_ctx, n_slots, rows, 1 if f32_out else 0, 1 if raw else 0, int(out_rows), Q.ctypes.data, K.ctypes.data, V.ctypes.data,
+                                               fill_from.ctypes.data, int(k_pad), int(v_pad), ptr(slot_k), ptr(active), ptr(seq), ptr(pos), int(sentinel), out.ctypes.data, C.byref(kid)))
+        return out, (self.ATTN_ENC_KERNELS[kid.value] if f == 0 else None)
 
     def gemm_q8(self, qtype, blocks, N, K, A, segmented, epi, C_buf, ldc=0, bias=None, res_alias=False, scale=1.0, has_scale=0, n_ctx=0, H=0, Tpad=0, pos=None,
                 C2_buf=None, C3_buf=None, ldc2=0):

@@ -4,7 +4,7 @@ cases tell a wrong per-block form, a scale from the neighbouring block, a droppe
 
 What runs, through the engine's own path (skw_debug_gemm_q8: the model loader's repack, skw_q8_quantize, skw_gemm_q8 with its dispatch): k_gemm_q8_small<UB 6 | 8>,
 k_gemm_q8<TW 2 | 4> and k_gemm_q8_lds, each in all three per-block forms, at the shapes of q8_ref_lib.cases(); the six epilogues at one shape per class; k_q8_quantize and the
-in-kernel quantiser of k_dec_attn against quantize_rows.  The launch reports the kernel the dispatcher picked (the function the launcher itself branches on), every output buffer
+in-kernel quantiser of k_dec_attn against quantize_rows (and that launch's f32 rows against the attention contract's restatement).  The launch reports the kernel the dispatcher picked (the function the launcher itself branches on), every output buffer
 starts as a sentinel with a margin past M and N that must come back untouched, and the closing test asserts that every kernel ran in every form."""
 import os
 import sys
@@ -14,6 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import q8_ref_lib as q8  # noqa: E402
+import attn_exact_ref_lib as ax  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 CASES = q8.cases()
@@ -178,7 +179,8 @@ def test_row_quantiser_equals_quantize_rows(ctx, M, K, variant, pad):
 
 @pytest.mark.parametrize("H", [4, 6])
 def test_attention_q8_output_equals_quantize_rows_of_its_f32_output(ctx, H):
-    """k_dec_attn's in-kernel quantiser (q8_half_wave_block: wave shuffles, fmaxf) against quantize_rows applied to what the same launch leaves with f32_out"""
+    """k_dec_attn's in-kernel quantiser (q8_half_wave_block: wave shuffles, fmaxf) against quantize_rows applied to what the same launch leaves with f32_out — and those f32 rows
+    against the contract's restatement (tests/attn_exact_ref_lib.py), bit for bit"""
     d = H * 64; n_text_ctx = 448
     pos = np.array([0, 1, 63, 64, 447, 30, 100], np.int32); rows = pos.size
     active = np.array([1, 1, 1, 1, 1, 0, 1], np.int32)                     # row 5 is finished: its outputs stay as they were
@@ -199,6 +201,12 @@ def test_attention_q8_output_equals_quantize_rows_of_its_f32_output(ctx, H):
         pytest.exit("skw_dec_self_attn H = %d: %s" % (H, e), returncode=3)
     live = np.flatnonzero(active); dead = np.flatnonzero(active == 0)
     assert np.isfinite(out[live]).all() and np.abs(out[live]).max() > 0.01
+    for b in live:
+        for h in range(H):
+            sl = slice(h * 64, h * 64 + 64)
+            r = ax.attend(Q[b:b + 1, sl], K[seq[b], :pos[b] + 1, sl], V[seq[b], :pos[b] + 1, sl])
+            assert not ax.order_dependent_rows(r["e"])                         # (a condition on the seeded operands: the row has one expectation)
+            assert np.array_equal(out[b:b + 1, sl].view(np.uint32), r["out32"].view(np.uint32)), "row %d head %d: k_dec_attn's f32 output is not the contract's" % (b, h)
     wq, wd, ws = q8.quantize_rows(out[live])
     assert np.array_equal(q[live], wq.reshape(live.size, d).astype(np.int8))
     assert np.array_equal(dT[:, live].T.copy().view(np.uint32), wd.view(np.uint32)) and np.array_equal(sT[:, live].T.copy().view(np.uint32), ws.view(np.uint32))
