@@ -131,6 +131,19 @@ const char* skw_ctx_last_error(const skw_ctx*);
 int skw_ctx_set_precision(skw_ctx*, int precision);   /* 0 on success; takes effect from the next call on this context */
 int skw_ctx_get_precision(const skw_ctx*);
 
+/* How a context stores the cross K / V its decode steps stream (additive; llama.cpp's --cache-type-k / --cache-type-v q8_0).  Not a third precision: a flag beside it.
+ *   SKW_CROSS_KV_F16   (default) the f16 images; every launch is the one it was before this knob existed;
+ *   SKW_CROSS_KV_Q8_0  the encoder pass also leaves cross K and V^T as ggml q8_0 blocks of 32 (include/skw_kv8.h: format, byte order, the bit-exact score chain), and every launch
+ *                      of the single-query cross attention — decode steps, the language-detection step, prompt rows that take the single-query kernel — streams those, 1.0625 bytes
+ *                      per element instead of 2.  The multi-query prompt pass and the word-timestamp capture keep reading the f16 images, which stay.  Costs another 1.0625 bytes
+ *                      per element of memory (2.45 MB per slot and layer at Whisper-small), allocated when the flag is q8_0 AND the precision is f16_mfma for the first time
+ *                      (whichever of the two setters completes the pair; a context that stays exact never allocates it).
+ * Effective only while the context runs SKW_PRECISION_F16_MFMA with its fragment-order images: the exact precision owes the oracle its bits and ignores the flag (no bit changes). */
+#define SKW_CROSS_KV_F16  0
+#define SKW_CROSS_KV_Q8_0 1
+int skw_ctx_set_cross_kv(skw_ctx*, int type);   /* 0 on success; from the next call on this context */
+int skw_ctx_get_cross_kv(const skw_ctx*);
+
 void skw_full_default_params(skw_full_params*);
 /* The "auto" rule for skw_full_params.audio_ctx, stated once: clips of at least 480 000 samples (30 s) get n_audio_ctx; shorter ones
  * min(n_audio_ctx, 32 * ceil((ceil(n_samples / 320) + 25) / 32)) — the 20 ms positions the audio covers, half a second of margin, whole 32-key blocks.  Needs no device. */

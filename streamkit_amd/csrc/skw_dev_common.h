@@ -24,6 +24,15 @@ __device__ __forceinline__ float gelu_dev(float x, const uint16_t* tab) {
     return h2f(__builtin_bit_cast(half_t, o));
 }
 
+// attention outputs: f16 in kperm order for the f16-weight path; f32 in natural order (the same buffer pointer, viewed as float) when the
+// projection that follows multiplies by block-quantised weights and ggml quantises the UNROUNDED f32 row (skw_kernels_q8.hip)
+__device__ __forceinline__ void att_store(half_t* out, long row_off, int col, float v, int f32_out) {
+    if (f32_out) ((float*)out)[row_off + col] = v; else out[row_off + skw_kperm(col)] = f2h(v);
+}
+// the decode step's attention outputs when the projection that follows reads a fragment-order A image (SkwGemmArgs::a_frag, skw_afrag_off): fk = its K (0: rows)
+__device__ __forceinline__ void att_store_m(half_t* out, int m, long ldo, int col, float v, int f32_out, int fk) {
+    if (fk && !f32_out) out[skw_afrag_off(m, skw_kperm(col), fk)] = f2h(v); else att_store(out, (long)m * ldo, col, v, f32_out);
+}
 union H8 { uint4 u; half_t h[8]; };
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 union H8v { u32x4 v; half_t h[8]; };

@@ -475,13 +475,20 @@ struct skw_ctx {
     int precision = SKW_PRECISION_EXACT;             // SKW_PRECISION_*: which form of the contractions runs (skw_ctx_set_precision)
     int kv_frag_on = 1;                              // f16_mfma: cross K / V^T as fragment-order images (skw_kernels.h, skw_kfrag_off); SKW_XATTN_FRAG=0 keeps the row layouts
     bool kv_frag() const { return kv_frag_on && precision == SKW_PRECISION_F16_MFMA; }
+    // cross_kv = q8_0 (skw_ctx_set_cross_kv; include/skw_kv8.h): the single-query cross attention of the f16_mfma precision reads the q8 image the encoder pass leaves beside the
+    // f16 fragment-order images.  Effective only with those images (kv8()): the exact precision owes the oracle its bits and ignores the flag.  kv8_fresh: the image holds the
+    // slots of the last encoder pass (false after a pass that ran without the flag) — what the decode step asks, so a flag flipped between an encode and a step changes nothing.
+    int cross_kv = SKW_CROSS_KV_F16; uint8_t* crossKV8 = nullptr; bool kv8_fresh = false;
+    bool kv8() const { return cross_kv == SKW_CROSS_KV_Q8_0 && kv_frag() && crossKV8; }
+    bool kv8_step() const { return kv8() && kv8_fresh; }
+    size_t kv8_slot() const { return (size_t)skw_kv8_slot_bytes(m->hp.n_text_head, Tpad); }
     size_t kclip() const { return (size_t)(kv_frag() ? Tpad : m->hp.n_audio_ctx) * m->hp.n_text_state; }      // cross-K elements per window slot (the buffer is sized for the larger: Tpad rows)
     ProfState* prof = nullptr;                       // per-kernel-class event timing (skw_ctx_profile); per context: contexts run on different host threads
     skw_model* m = nullptr; int max_batch = 0, max_samples = 0, n_len_max = 0, Tpad = 0;
     hipStream_t stream = nullptr; hipEvent_t ev[6] = {};
     hipStream_t cur = nullptr;                       // stream the launch helpers enqueue on (== stream outside the decode groups)
     static const int MAX_GROUPS = 8; hipStream_t gstream[MAX_GROUPS] = {}; hipEvent_t gev[MAX_GROUPS] = {}; int n_groups = 1;
-    struct StepGraph { int g, r0, n, precision, ln_stats, kclk, var_k; unsigned sw_epoch; SkwLogitParams lp; int rows, cons; hipGraphExec_t exec; };
+    struct StepGraph { int g, r0, n, precision, ln_stats, kclk, var_k, kv8; unsigned sw_epoch; SkwLogitParams lp; int rows, cons; hipGraphExec_t exec; };
     std::vector<StepGraph> step_graphs; int use_graphs = 1;
     char errbuf[512] = {0};
     std::vector<void*> allocs;
@@ -551,11 +558,30 @@ static const char* ws_first_null(const skw_ctx* c) {
 // every entry point that launches kernels starts here: a context whose table holds a null buffer never reaches a launch
 #define WS_READY(c) do { if (const char* nb_ = ws_first_null(c)) { snprintf((c)->errbuf, 512, "workspace buffer '%s' is not allocated", nb_); return -1; } } while (0)
 extern "C" const char* skw_ctx_last_error(const skw_ctx* c) { return c->errbuf; }
+// The q8 image of cross_kv = q8_0 (1.0625 bytes per element of cross K and V^T, every layer and slot) is allocated when it can first be used: the flag asks for q8_0 AND the
+// context runs f16_mfma — a context that stays in the exact precision, which ignores the flag, never pays for it.  Entered in the workspace table by name.
+static int kv8_ensure(skw_ctx* c, int precision, int cross_kv) {
+    if (cross_kv != SKW_CROSS_KV_Q8_0 || precision != SKW_PRECISION_F16_MFMA || c->crossKV8) return 0;
+    const size_t bytes = (size_t)c->m->hp.n_text_layer * c->max_batch * c->kv8_slot(); void* p = nullptr;
+    if (hipSetDevice(c->m->device) != hipSuccess || hipMalloc(&p, bytes) != hipSuccess || !p) {
+        snprintf(c->errbuf, 512, "workspace buffer 'crossKV8' could not be allocated (%zu bytes, max_batch %d)", bytes, c->max_batch); return -1;
+    }
+    c->crossKV8 = (uint8_t*)p; c->allocs.push_back(p);
+    c->ws_table.push_back(skw_ctx::WsEntry{"crossKV8", (void**)&c->crossKV8, bytes, false, false});
+    return 0;
+}
 extern "C" int skw_ctx_set_precision(skw_ctx* c, int precision) {
     if (precision != SKW_PRECISION_EXACT && precision != SKW_PRECISION_F16_MFMA) { snprintf(c->errbuf, 512, "unknown precision %d", precision); return -1; }
+    if (kv8_ensure(c, precision, c->cross_kv)) return -1;
     c->precision = precision; return 0;
 }
 extern "C" int skw_ctx_get_precision(const skw_ctx* c) { return c->precision; }
+extern "C" int skw_ctx_set_cross_kv(skw_ctx* c, int type) {
+    if (type != SKW_CROSS_KV_F16 && type != SKW_CROSS_KV_Q8_0) { snprintf(c->errbuf, 512, "unknown cross_kv type %d", type); return -1; }
+    if (kv8_ensure(c, c->precision, type)) return -1;
+    c->cross_kv = type; return 0;
+}
+extern "C" int skw_ctx_get_cross_kv(const skw_ctx* c) { return c->cross_kv; }
 extern "C" void* skw_ctx_stream(const skw_ctx* c) { return (void*)c->stream; }
 extern "C" void skw_ctx_last_timing(const skw_ctx* c, skw_timing* out) { *out = c->timing; }
 
@@ -698,6 +724,12 @@ static std::map<std::string, std::vector<float>> g_taps; static bool g_taps_on =
 extern "C" long skw_layout_kfrag_off(int slot, int H, int Tpad, int key, int feat) { return skw_kfrag_off(slot, H, Tpad, key, feat); }
 extern "C" long skw_layout_vtfrag_off(int slot, int H, int Tpad, int feat, int pos) { return skw_vtfrag_off(slot, H, Tpad, feat, pos); }
 extern "C" int skw_layout_kperm(int k) { return skw_kperm(k); }
+// the q8 image of cross_kv = q8_0 (include/skw_kv8.h), in bytes: the int8 / the f16 block scale of K[key][feat] and of V[key][feat], and a slot's size
+extern "C" long skw_layout_kv8_kq_off(int slot, int H, int Tpad, int key, int feat) { return skw_kv8_kq_off(slot, H, Tpad, key, feat); }
+extern "C" long skw_layout_kv8_kd_off(int slot, int H, int Tpad, int key, int feat) { return skw_kv8_kd_off(slot, H, Tpad, key, feat); }
+extern "C" long skw_layout_kv8_vq_off(int slot, int H, int Tpad, int feat, int key) { return skw_kv8_vq_off(slot, H, Tpad, feat, key); }
+extern "C" long skw_layout_kv8_vd_off(int slot, int H, int Tpad, int feat, int key) { return skw_kv8_vd_off(slot, H, Tpad, feat, key); }
+extern "C" long skw_layout_kv8_slot_bytes(int H, int Tpad) { return skw_kv8_slot_bytes(H, Tpad); }
 extern "C" long skw_layout_afrag_off(int m, int p, int K) { return skw_afrag_off(m, p, K); }
 // tests: the fragment-order image of a host weight [N][K] (f16 bits), as the decode kernels read it (skw_make_wfrag)
 extern "C" int skw_debug_make_wfrag(const uint16_t* w_host, int N, int K, int perm, uint16_t* img_host) {
@@ -876,6 +908,17 @@ static void run_conv(skw_ctx* c, int Bw_all, int row0 = 0, int rows = 0) {
     b.gelu_tab = m->gelu_tab; b.pe = m->e_pe; b.n_ctx = nc;
     GEMM(c, b, m->conv2.n_in);
 }
+// cross_kv = q8_0: the q8 image of window slots slot0 .. slot0 + n - 1, every layer, from their f16 fragment-order images (one launch per layer; the slots' key counts are
+// slot_k's, in device memory).  Called behind the cross-K/V GEMMs of an encoder pass, and for the slots a temperature retry moved.  Without the flag: marks the image stale.
+static void kv8_refresh(skw_ctx* c, int slot0, int n, bool keep_fresh = false) {
+    if (!c->kv8()) { c->kv8_fresh = false; return; }
+    const skw_hparams& hp = c->m->hp; const int H = hp.n_text_head;
+    ProfScope p_(c, PC_OTHER, 0, (double)hp.n_text_layer * n * (4.0 * hp.n_audio_ctx * hp.n_text_state + (double)c->kv8_slot()));
+    for (int l = 0; l < hp.n_text_layer; ++l)
+        skw_kv8_quantize(c->crossK + (size_t)l * c->max_batch * c->kclip(), c->crossV + (size_t)l * c->max_batch * H * 64 * c->Tpad, c->crossKV8 + (size_t)l * c->max_batch * c->kv8_slot(),
+                         slot0, n, H, hp.n_audio_ctx, c->Tpad, c->var_k ? c->slot_k : nullptr, c->stream);
+    if (!keep_fresh) c->kv8_fresh = true;
+}
 // encoder blocks + ln_post (+ cross K/V) over Bw windows; input c->x
 // rows: rows per slot of the activations (enc_rows_for; 0: n_audio_ctx).  Strides of Qh / Kh / Vt and of cross K / V stay those of the full context
 static void run_encoder(skw_ctx* c, int Bw_all, bool want_f32_out, bool cross, int row0 = 0, int rows = 0) {
@@ -980,6 +1023,7 @@ static void run_encoder(skw_ctx* c, int Bw_all, bool want_f32_out, bool cross, i
                 GEMM(c, a, d);
             }
         }
+        kv8_refresh(c, row0, Bw);
     }
     c->last_enc_B = Bw_all;
 }
@@ -1143,6 +1187,11 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
             } else if (xq_mq && skw_xattn_prefill_exact(dq16, ck, cv, datt16, c->pf_nseq, c->pf_nq_max, c->pf_meta, c->pf_meta + c->max_batch, c->pf_meta + 2 * c->max_batch, H, dt, nc,
                                                         c->Tpad, s, 0, c->var_k ? c->slot_k : nullptr)) {
             } else
+            if (c->kv8_step()) {      // cross_kv = q8_0: every launch of the single-query kernel reads the q8 image (2 x 1.0625 bytes per key and channel)
+                ProfScope p_(c, PC_DEC_XATTN, 4.0 * live * (double)nc * dt, 2.125 * live * (double)nc * dt, true);
+                skw_dec_cross_attn_kv8(dq16, c->crossKV8 + ((size_t)l * c->max_batch + r0) * c->kv8_slot(), Bw, H, dt, nc, c->Tpad, datt16, &st[0].active, s, 0, seqp, p_.ev_a(), p_.ev_b(), xa_frag,
+                                       prefill ? nullptr : kclk_node(c, c->cur_group, l), nkeys);
+            } else
             { ProfScope p_(c, PC_DEC_XATTN, 4.0 * live * (double)nc * dt, 4.0 * live * (double)nc * dt, true);
             skw_dec_cross_attn_vt(dq16, ck, cv, Bw, H, dt, nc, c->Tpad, datt16, &st[0].active, s, 0, c->kv_frag() ? 2 : c->precision == SKW_PRECISION_F16_MFMA, seqp, p_.ev_a(), p_.ev_b(), xa_frag,
                                   prefill ? nullptr : kclk_node(c, c->cur_group, l), nkeys);
@@ -1171,7 +1220,7 @@ static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogi
     for (size_t i = 0; i < c->step_graphs.size(); ++i) {
         auto& sg = c->step_graphs[i];
         if (sg.g == g && sg.r0 == r0 && sg.n == n && sg.precision == c->precision && sg.ln_stats == c->ln_stats_on && sg.kclk == c->kclk_on && sg.sw_epoch == skw_sw_epoch() &&
-            sg.var_k == (int)c->var_k && sg.rows == (int)rows && sg.cons == (int)cons && memcmp(&sg.lp, &lp, sizeof lp) == 0) {
+            sg.var_k == (int)c->var_k && sg.kv8 == (int)c->kv8_step() && sg.rows == (int)rows && sg.cons == (int)cons && memcmp(&sg.lp, &lp, sizeof lp) == 0) {
             if (i + 1 != c->step_graphs.size()) { auto hit = sg; c->step_graphs.erase(c->step_graphs.begin() + i); c->step_graphs.push_back(hit); }   // most recently used last
             return c->step_graphs.back().exec;
         }
@@ -1192,7 +1241,7 @@ static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogi
     if (exec) {
         // bounded: a long-lived server with ragged batches would otherwise keep one executable graph per (group, rows, params) forever
         if (c->step_graphs.size() >= 24) { hipGraphExecDestroy(c->step_graphs.front().exec); c->step_graphs.erase(c->step_graphs.begin()); }
-        skw_ctx::StepGraph sg; sg.g = g; sg.r0 = r0; sg.n = n; sg.precision = c->precision; sg.ln_stats = c->ln_stats_on; sg.kclk = c->kclk_on; sg.var_k = (int)c->var_k;
+        skw_ctx::StepGraph sg; sg.g = g; sg.r0 = r0; sg.n = n; sg.precision = c->precision; sg.ln_stats = c->ln_stats_on; sg.kclk = c->kclk_on; sg.var_k = (int)c->var_k; sg.kv8 = (int)c->kv8_step();
          sg.sw_epoch = skw_sw_epoch(); sg.lp = lp; sg.rows = (int)rows; sg.cons = (int)cons; sg.exec = exec; c->step_graphs.push_back(sg);
     }
     return exec;
@@ -1284,10 +1333,10 @@ __global__ void k_slot_copy(const half_t* src, long src_layer_stride, half_t* ds
 }
 // The windows in `old_slots` (ascending new slot order 0 .. R-1) are decoded again at the next temperature: their cross K/V move to slots
 // 0 .. R-1 through a staging copy (a direct move could overwrite another retry's source), instead of running the encoder on them again.
+static bool retry_slots_in_place(const std::vector<int>& old_slots) { for (size_t k = 0; k < old_slots.size(); ++k) if (old_slots[k] != (int)k) return false; return true; }
 static int move_retry_slots(skw_ctx* c, const std::vector<int>& old_slots) {
     char* errbuf = c->errbuf; const skw_hparams& hp = c->m->hp; const int R = (int)old_slots.size(), L = hp.n_text_layer;
-    bool same = true; for (int k = 0; k < R; ++k) same = same && old_slots[k] == k;
-    if (same) return 0;
+    if (retry_slots_in_place(old_slots)) return 0;
     const long ke = (long)c->kclip(), ka = (long)c->Tpad * hp.n_text_state, ve = (long)hp.n_text_head * 64 * c->Tpad;      // ka: the staging buffer is sized like crossK (Tpad rows per slot)
     if (!c->stageK || !c->stageV || !c->slot_map) {      // all three or none: a partial failure must not leave a later retry launching k_slot_copy on a null buffer
         half_t *sk = nullptr, *sv = nullptr; int* sm = nullptr;
@@ -1512,6 +1561,8 @@ static int stage_window(skw_ctx* c, const FullRequest& rq, CallState& cs, Window
         HIPCHK(hipMemcpyAsync(c->forced_dev, w.fbuf.data(), sizeof(int) * w.fbuf.size(), hipMemcpyHostToDevice, c->stream));
     }
     HIPCHK(hipEventRecord(c->ev[2], c->stream));
+    // the retried windows' q8 image, from the f16 images that moved with them (nothing moved: the image of slots 0 .. R-1 still stands)
+    if (R > 0 && c->kv8_step() && !retry_slots_in_place(w.retry_old)) kv8_refresh(c, 0, R, true);
     if (R < Bw) { run_conv(c, Bw, R, w.enc_rows); run_encoder(c, Bw, false, true, R, w.enc_rows); }
     HIPCHK(hipEventRecord(c->ev[3], c->stream));
     // decoder state
@@ -2381,6 +2432,78 @@ extern "C" int skw_debug_attn16(skw_ctx* c, int form, int H, int n_ctx, int n_sl
     if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(o.data(), dout, nO * 2, hipMemcpyDeviceToHost))) return -1;
     cleanup();
     for (int r = 0; r < orows; ++r) for (int n = 0; n < d; ++n)
+        out_host[(size_t)r * d + n] = skw_f16_to_f32(o[ofrag ? (size_t)skw_afrag_off(r, skw_kperm(n), d) : (size_t)r * d + skw_kperm(n)]);
+    return 0;
+}
+
+// tests (tests/test_gpu_kv8.py): the two kernels of cross_kv = q8_0 on host-supplied operands, in the style of skw_debug_attn16 (whose packing, pads and sentinel these share).
+// K / V [slot][n_ctx][H*64] arrive as f16 bit patterns in natural order and become the f16 fragment-order images, pad patterns from fill_from[s] up; slot_k (null: n_ctx) are the
+// quantiser's key counts per slot.  The q8 image starts as the byte 0xEE, so what k_kv8_quantize does not write is visible.
+struct Kv8Hook { half_t *dk = nullptr, *dv = nullptr; uint8_t* img = nullptr; int* dslot_k = nullptr; size_t img_bytes = 0; ~Kv8Hook() { hipFree(dk); hipFree(dv); hipFree(img); hipFree(dslot_k); } };
+static const char* kv8_hook_quantize(skw_ctx* c, Kv8Hook& k8, int H, int n_ctx, int n_slots, const uint16_t* K_host, const uint16_t* V_host, const int* fill_from, int k_pad, int v_pad,
+                                     const int* slot_k) {
+    if (H < 1 || H > 32 || n_ctx < 1 || n_ctx > 4096 || n_slots < 1 || n_slots > 64 || !fill_from || !K_host || !V_host) return "bad geometry";
+    for (int s = 0; s < n_slots; ++s) if (fill_from[s] < 0 || fill_from[s] > n_ctx || (slot_k && (slot_k[s] < 1 || slot_k[s] > n_ctx))) return "fill_from / slot_k outside the slot";
+    const int d = H * 64, Tpad = (n_ctx + 31) & ~31; const size_t nKV = (size_t)n_slots * Tpad * d;
+    std::vector<uint16_t> q(1), k(nKV, (uint16_t)k_pad), v(nKV, (uint16_t)v_pad);
+    const uint16_t q0 = 0;
+    attn_hook_pack(AttnHookLayout{0, 0, 1, 0, 1}, H, n_ctx, n_slots, &q0, K_host, V_host, fill_from, q, k, v);
+    k8.img_bytes = (size_t)n_slots * skw_kv8_slot_bytes(H, Tpad);
+    if (hipMalloc((void**)&k8.dk, nKV * 2) != hipSuccess || hipMalloc((void**)&k8.dv, nKV * 2) != hipSuccess || hipMalloc((void**)&k8.img, k8.img_bytes) != hipSuccess ||
+        hipMalloc((void**)&k8.dslot_k, sizeof(int) * 64) != hipSuccess) return "device allocation failed";
+    int sk[64] = {0}; if (slot_k) for (int s = 0; s < n_slots; ++s) sk[s] = slot_k[s];
+    if (hipMemcpy(k8.dk, k.data(), nKV * 2, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(k8.dv, v.data(), nKV * 2, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(k8.img, 0xEE, k8.img_bytes) != hipSuccess || hipMemcpy(k8.dslot_k, sk, sizeof sk, hipMemcpyHostToDevice) != hipSuccess) return "copy to the device failed";
+    skw_kv8_quantize(k8.dk, k8.dv, k8.img, 0, n_slots, H, n_ctx, Tpad, slot_k ? k8.dslot_k : nullptr, c->stream);
+    return nullptr;
+}
+// -> img_host [n_slots * skw_layout_kv8_slot_bytes(H, Tpad)]: the image as the kernel wrote it
+extern "C" int skw_debug_kv8_quantize(skw_ctx* c, int H, int n_ctx, int n_slots, const uint16_t* K_host, const uint16_t* V_host, const int* fill_from, int k_pad, int v_pad,
+                                      const int* slot_k, uint8_t* img_host) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    Kv8Hook k8;
+    if (const char* what = kv8_hook_quantize(c, k8, H, n_ctx, n_slots, K_host, V_host, fill_from, k_pad, v_pad, slot_k)) { snprintf(errbuf, 512, "skw_debug_kv8_quantize: %s", what); return -1; }
+    HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(img_host, k8.img, k8.img_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+// The quantise kernel, then skw_dec_cross_attn_kv8 through its launcher.  Q [rows][H*64]; active / seq / count (= n_keys) are [rows] or null and reach the kernel as fields of a
+// SkwSeqState array.  flags: 2 ofrag, 4 f32_out (the output rows unrounded), 8 raw.  out_host: f32 [rows][H*64] in natural order — rows the kernel leaves alone hold `sentinel`
+// (as f16; with f32_out the 32-bit pattern sentinel | sentinel << 16) — or, raw, the f32 scores [rows][H][n_ctx], NaN where nothing was written.
+extern "C" int skw_debug_attn_kv8(skw_ctx* c, int H, int n_ctx, int n_slots, int rows, int flags, const uint16_t* Q_host, const uint16_t* K_host, const uint16_t* V_host,
+                                  const int* fill_from, int k_pad, int v_pad, const int* slot_k, const int* active, const int* seq, const int* count, int sentinel, float* out_host) {
+    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
+    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_attn_kv8: %s", what); return -1; };
+    if (rows < 1 || rows > 65536 || !Q_host || !out_host) return bad("bad geometry");
+    const int ofrag = (flags >> 1) & 1, f32_out = (flags >> 2) & 1, raw = (flags >> 3) & 1;
+    if (ofrag && f32_out) return bad("ofrag and f32_out exclude each other");
+    Kv8Hook k8;
+    if (const char* what = kv8_hook_quantize(c, k8, H, n_ctx, n_slots, K_host, V_host, fill_from, k_pad, v_pad, slot_k)) return bad(what);
+    const int d = H * 64, Tpad = (n_ctx + 31) & ~31;
+    for (int b = 0; b < rows; ++b) {
+        const int s = seq ? seq[b] : b;
+        if (s < 0 || s >= n_slots) return bad("a row's sequence lies outside the slots");
+        if (count && (count[b] < 0 || count[b] > (slot_k ? slot_k[s] : n_ctx))) return bad("a row's key count lies beyond what its slot was quantised with");
+    }
+    const size_t nO = (size_t)(ofrag ? (rows + 15) & ~15 : rows) * d * (f32_out ? 2 : 1), nR = raw ? (size_t)rows * H * n_ctx : 1;
+    std::vector<uint16_t> o(nO, (uint16_t)sentinel);
+    std::vector<SkwSeqState> st(rows); memset((void*)st.data(), 0, sizeof(SkwSeqState) * rows);
+    for (int b = 0; b < rows; ++b) { st[b].active = active ? active[b] : 1; st[b].pad = seq ? seq[b] : b; st[b].n_keys = count ? count[b] : 0; }
+    half_t *dq = nullptr, *dout = nullptr; SkwSeqState* dst = nullptr; float* draw = nullptr;
+    auto cleanup = [&]() { hipFree(dq); hipFree(dout); hipFree(dst); hipFree(draw); };
+    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_attn_kv8: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
+    if (!chk(hipMalloc((void**)&dq, (size_t)rows * d * 2)) || !chk(hipMalloc((void**)&dout, nO * 2)) || !chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * rows))) return -1;
+    if (!chk(hipMalloc((void**)&draw, nR * 4)) || !chk(hipMemset(draw, 0xFF, nR * 4))) return -1;
+    if (!chk(hipMemcpy(dq, Q_host, (size_t)rows * d * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dout, o.data(), nO * 2, hipMemcpyHostToDevice))) return -1;
+    if (!chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * rows, hipMemcpyHostToDevice))) return -1;
+    skw_dec_cross_attn_kv8(dq, k8.img, rows, H, d, n_ctx, Tpad, dout, active ? &dst[0].active : nullptr, c->stream, f32_out, seq ? &dst[0].pad : nullptr, nullptr, nullptr, ofrag, nullptr,
+                           count ? &dst[0].n_keys : nullptr, raw ? draw : nullptr);
+    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError())) return -1;
+    if (raw) { if (!chk(hipMemcpy(out_host, draw, nR * 4, hipMemcpyDeviceToHost))) return -1; cleanup(); return 0; }
+    if (!chk(hipMemcpy(o.data(), dout, nO * 2, hipMemcpyDeviceToHost))) return -1;
+    cleanup();
+    if (f32_out) memcpy(out_host, o.data(), (size_t)rows * d * 4);
+    else for (int r = 0; r < rows; ++r) for (int n = 0; n < d; ++n)
         out_host[(size_t)r * d + n] = skw_f16_to_f32(o[ofrag ? (size_t)skw_afrag_off(r, skw_kperm(n), d) : (size_t)r * d + skw_kperm(n)]);
     return 0;
 }

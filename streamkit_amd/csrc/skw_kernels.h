@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include "skw_window_rules.h"
 #include "../../include/skw_align.h"
+#include "../../include/skw_kv8.h"
 
 typedef _Float16 half_t;
 
@@ -192,6 +193,17 @@ void skw_dec_cross_attn_vt(const half_t* q, const half_t* ck, const half_t* cvt,
                            // nkeys (stride of `active`; null: n_ctx): &state[0].n_keys — row b attends over the first nkeys[b] keys of its sequence (0: n_ctx).  Read from device
                            //  memory, so a captured step holds no key count; n_ctx and Tpad stay the strides of the buffers
                            const int* nkeys = nullptr);
+
+// ---------------- 8-bit cross K / V (cross_kv = q8_0; include/skw_kv8.h: contract, format and byte order; skw_kernels_kv8.hip) ----------------
+// kf / vtf: a layer's f16 fragment-order cross K / V^T images of n_slots window slots -> img, the q8 image (skw_kv8_slot_bytes per slot).  slot_k: [n_slots] key counts in device
+// memory (null, or an entry outside 1 .. n_ctx: n_ctx); a key at or past the count is a pad whatever it holds.
+// Slots slot0 .. slot0 + n_slots - 1 of the three buffers (all three start at the layer's slot 0; slot_k too is indexed by the slot).
+void skw_kv8_quantize(const half_t* kf, const half_t* vtf, uint8_t* img, int slot0, int n_slots, int H, int n_ctx, int Tpad, const int* slot_k, hipStream_t s);
+// skw_dec_cross_attn_vt(pv16 = 2) over the q8 image: same rows, flags, events, clock and key counts.  raw (tests; null in every other run): the launch writes its f32 scores
+// [B][H][n_ctx] instead of `out`.
+void skw_dec_cross_attn_kv8(const half_t* q, const uint8_t* img, int B, int H, int d, int n_ctx, int Tpad, half_t* out, const int* active, hipStream_t s, int f32_out = 0,
+                            const int* seq = nullptr, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, int ofrag = 0, SkwKClk* clk = nullptr, const int* nkeys = nullptr,
+                            float* raw = nullptr);
 
 // SkwSeqState (the per-sequence decoding state kept on the device), SkwTokenOut, SKW_DELTA_MIN and SKW_PROMPT_CAP: skw_window_rules.h, with the token loop's update rule
 #define SKW_RNG_WORDS 625   // std::mt19937 state per clip: mt[624] + index

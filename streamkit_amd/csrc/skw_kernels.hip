@@ -237,15 +237,7 @@ void skw_gemm_smallm(const SkwGemmArgs& a, hipStream_t s) {
     }
 }
 
-// attention outputs: f16 in kperm order for the f16-weight path; f32 in natural order (the same buffer pointer, viewed as float) when the
-// projection that follows multiplies by block-quantised weights and ggml quantises the UNROUNDED f32 row (skw_kernels_q8.hip)
-__device__ __forceinline__ void att_store(half_t* out, long row_off, int col, float v, int f32_out) {
-    if (f32_out) ((float*)out)[row_off + col] = v; else out[row_off + skw_kperm(col)] = f2h(v);
-}
-// the decode step's attention outputs when the projection that follows reads a fragment-order A image (SkwGemmArgs::a_frag, skw_afrag_off): fk = its K (0: rows)
-__device__ __forceinline__ void att_store_m(half_t* out, int m, long ldo, int col, float v, int f32_out, int fk) {
-    if (fk && !f32_out) out[skw_afrag_off(m, skw_kperm(col), fk)] = f2h(v); else att_store(out, (long)m * ldo, col, v, f32_out);
-}
+// (att_store / att_store_m, the attention outputs' stores: skw_dev_common.h — the q8 cross-attention kernel of skw_kernels_kv8.hip shares them)
 // ------------------------------------------------------------------ LayerNorm
 __device__ __forceinline__ double wave_sum_f64(double v) { return skw_wave_sum_f64(v); }   // DPP + readlane, no LDS crossbar (skw_dev_common.h)
 // one wave per R rows; d <= 64 NC (NC = 12 for every width up to Whisper-small's, 24 up to 1536); FULL: d == 64 NC (Whisper-small: straight-line code, no tail predicates).

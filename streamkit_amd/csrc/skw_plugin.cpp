@@ -77,6 +77,7 @@ struct WhisperConfig {
     int batch_window_ms = 2; int max_batch = 64; bool flush_tail = false;
     bool mixed_batch = true;         // segments of differently configured instances share a GPU batch (skw_full_batch_mixed); false: a batch is cut at the first job whose parameters differ
     std::string precision = "exact"; // exact | f16_mfma  (include/skw_engine.h, SKW_PRECISION_*)
+    std::string cross_kv = "f16";    // f16 | q8_0  (include/skw_engine.h, SKW_CROSS_KV_*): how the decode steps' cross K / V is stored; q8_0 needs precision f16_mfma
     // skw_full_params.audio_ctx of this instance's segments: 0 (the model's context, the reference's behaviour), an integer 1 .. n_audio_ctx, or "auto" (skw_audio_ctx_for_samples per
     // segment).  An integer out of range is the engine's refusal, per request: it stays with the segment that carries it
     int audio_ctx = 0; bool audio_ctx_auto = false;
@@ -170,6 +171,12 @@ bool parse_config(const char* json, WhisperConfig* cfg, std::string* err) {
     if (!str("model_path", &cfg->model_path) || !str("language", &cfg->language) || !str("vad_model_path", &cfg->vad_model_path) || !str("vad_mode", &cfg->vad_mode)
         || !str("precision", &cfg->precision)) return false;
     if (cfg->precision != "exact" && cfg->precision != "f16_mfma") { *err = "Invalid config: precision must be \"exact\" or \"f16_mfma\""; return false; }
+    if (!str("cross_kv", &cfg->cross_kv)) return false;
+    if (cfg->cross_kv != "f16" && cfg->cross_kv != "q8_0") { *err = "Invalid config: cross_kv must be \"f16\" or \"q8_0\""; return false; }
+    if (cfg->cross_kv == "q8_0" && cfg->precision != "f16_mfma") {
+        *err = "Invalid config: cross_kv \"q8_0\" needs precision \"f16_mfma\": the exact precision reproduces the reference bit for bit and cannot read quantised cross K/V";
+        return false;
+    }
     if (!str("vad_device", &cfg->vad_device) || !str("initial_prompt", &cfg->initial_prompt)) return false;
     if (cfg->vad_device != "cpu" && cfg->vad_device != "gpu") { *err = "Invalid config: vad_device must be \"cpu\" or \"gpu\""; return false; }
     d = cfg->vad_batch_frames; if (!num("vad_batch_frames", &d)) return false;
@@ -287,6 +294,13 @@ struct SharedEngine {
     int n_vocab = 51865;        // the model's vocabulary (what suppress_tokens / logit_bias ids are checked against); set once at load
     bool mixed = true;          // scheduler: jobs join a batch whatever their parameters (mixed_batch of the instance created most recently; under mu)
     int precision = SKW_PRECISION_EXACT;
+    int cross_kv = SKW_CROSS_KV_F16;
+    // precision and cross_kv of this engine on a workspace just created; false (with the engine's message) when the q8 image cannot be allocated
+    bool configure(skw_ctx* c, std::string* err) {
+        skw_ctx_set_precision(c, precision);
+        if (skw_ctx_set_cross_kv(c, cross_kv) != 0) { if (err) *err = std::string("Failed to create Whisper state: ") + skw_ctx_last_error(c); return false; }
+        return true;
+    }
     static const int kMaxSamples = 16000 * 121;   // schema maximum of max_segment_duration_secs (120 s) + one VAD frame of slack: no segment is longer
     static int samples_for(float max_segment_secs) { const double s = std::min(120.0, std::max(1.0, (double)max_segment_secs)); return std::min(kMaxSamples, (int)std::ceil(s * 16000.0) + 1024); }
     // The workspace is sized for the longest segment an instance of this engine can cut (its max_segment_duration_secs) and the largest batch one asked
@@ -310,11 +324,13 @@ struct SharedEngine {
             const int rs = std::max(was_s, floor_samples), rb = std::max(was_b, floor_batch);
             if (rs > 0 && rb > 0 && (rs < ns || rb < nb)) {      // back to what there was: later batches of the usual size must not pay for this one
                 char e2[512] = {0};
-                if (skw_ctx* oc = skw_ctx_create(model, rb, rs, e2, sizeof e2)) { skw_ctx_set_precision(oc, precision); ctx = oc; max_samples = rs; max_batch = rb; }
+                if (skw_ctx* oc = skw_ctx_create(model, rb, rs, e2, sizeof e2)) {
+                    if (configure(oc, nullptr)) { ctx = oc; max_samples = rs; max_batch = rb; } else skw_ctx_free(oc);
+                }
             }
             return false;
         }
-        skw_ctx_set_precision(nc, precision);
+        if (!configure(nc, err)) { skw_ctx_free(nc); return false; }
         ctx = nc; max_samples = ns; max_batch = nb;
         return true;
     }
@@ -487,7 +503,8 @@ void build_job_context(WhisperPlugin* self, int32_t* out) {
 
 std::shared_ptr<SharedEngine> get_engine(const WhisperConfig& cfg, WhisperPlugin* who, std::string* err) {
     char keybuf[96];
-    snprintf(keybuf, sizeof keybuf, "|%d|%d|%s", cfg.use_gpu ? 1 : 0, cfg.gpu_device, cfg.precision.c_str());   // the reference's key (path, use_gpu, gpu_device) + the additive precision
+    // the reference's key (path, use_gpu, gpu_device) + the additive precision and cross_kv
+    snprintf(keybuf, sizeof keybuf, "|%d|%d|%s|%s", cfg.use_gpu ? 1 : 0, cfg.gpu_device, cfg.precision.c_str(), cfg.cross_kv.c_str());
     const std::string key = cfg.model_path + keybuf;
     EngineCache& cache = engine_cache();
     std::unique_lock<std::mutex> l(cache.mu);
@@ -522,6 +539,7 @@ std::shared_ptr<SharedEngine> get_engine(const WhisperConfig& cfg, WhisperPlugin
     eng->batch_limit = cfg.max_batch;
     eng->window_ms = cfg.batch_window_ms; eng->mixed = cfg.mixed_batch;
     eng->precision = cfg.precision == "f16_mfma" ? SKW_PRECISION_F16_MFMA : SKW_PRECISION_EXACT;
+    eng->cross_kv = cfg.cross_kv == "q8_0" ? SKW_CROSS_KV_Q8_0 : SKW_CROSS_KV_F16;
     eng->floor_samples = SharedEngine::samples_for(cfg.max_segment_duration_secs); eng->floor_batch = cfg.max_batch;
     if (!eng->ensure_workspace(eng->floor_samples, eng->floor_batch, err)) return nullptr;
     const auto t2 = std::chrono::steady_clock::now();
@@ -757,6 +775,7 @@ const char* const kSchema =
     "\"vad_device\":{\"type\":\"string\",\"description\":\"(additive) cpu (the Silero gate frame by frame on the host) | gpu (the Silero gate in the bit-exact contract arithmetic on the GPU of gpu_device; unused with the energy / always gates)\",\"default\":\"cpu\"},"
     "\"vad_batch_frames\":{\"type\":\"integer\",\"description\":\"(additive) complete 512-sample frames held back before the VAD gate evaluates them in one call; cuts, ids and timestamps do not depend on it, a cut is handed over up to N-1 frames (32 ms each) later; file transcription sets 64 or more\",\"default\":1,\"minimum\":1,\"maximum\":65536},"
     "\"precision\":{\"type\":\"string\",\"description\":\"(additive) exact (f32-chain contractions, bit-reproducible; block-quantised model files run ggml's q8 arithmetic) | f16_mfma (f16 matrix cores; quantised files as their f16 twin)\",\"default\":\"exact\"},"
+    "\"cross_kv\":{\"type\":\"string\",\"description\":\"(additive) f16 | q8_0: the decode steps read the window's cross K/V as ggml q8_0 blocks, half the bytes of every step; needs precision f16_mfma\",\"default\":\"f16\"},"
     "\"batch_window_ms\":{\"type\":\"integer\",\"description\":\"(additive) how long the per-GPU scheduler waits for concurrent instances before launching a batch\",\"default\":2},"
     "\"max_batch\":{\"type\":\"integer\",\"description\":\"(additive) largest number of segments transcribed in one GPU batch\",\"default\":64},"
     "\"audio_ctx\":{\"type\":[\"integer\",\"string\"],\"description\":\"(additive) whisper.cpp's audio_ctx per segment: 0 = the model's 1500 positions (30 s); N = encode and attend only N positions (20 ms each: the audio beyond N/50 s is not heard); \\\"auto\\\" = the positions the segment covers + 0.5 s, in 32-position blocks. Segments with different values share a batch\",\"default\":0},"
@@ -861,7 +880,8 @@ CResult plugin_update_params(CPluginHandle handle, const char* params) {
         std::string err;
         if (!parse_config(params, &nc, &err)) return err_result(err);
         if (nc.gpu_device_auto) nc.gpu_device = self->config.gpu_device;        // an "auto" instance stays on the device it was dealt
-        if (nc.model_path != self->config.model_path || nc.precision != self->config.precision || nc.use_gpu != self->config.use_gpu || nc.gpu_device != self->config.gpu_device) {
+        if (nc.model_path != self->config.model_path || nc.precision != self->config.precision || nc.cross_kv != self->config.cross_kv || nc.use_gpu != self->config.use_gpu ||
+            nc.gpu_device != self->config.gpu_device) {
             auto eng = get_engine(nc, self, &err);
             if (!eng) return err_result("Failed to reload Whisper model: " + err);
             if (!check_rule_ids(nc, eng->n_vocab, &err)) return err_result(err);      // (before the instance lets go of the engine it has)

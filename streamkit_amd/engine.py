@@ -150,6 +150,14 @@ def lib():
         L.skw_ctx_last_error.argtypes = [C.c_void_p]
         L.skw_ctx_set_precision.argtypes = [C.c_void_p, C.c_int]
         L.skw_ctx_get_precision.argtypes = [C.c_void_p]
+        L.skw_ctx_set_cross_kv.argtypes = [C.c_void_p, C.c_int]
+        L.skw_ctx_get_cross_kv.argtypes = [C.c_void_p]
+        for name in ("kq", "kd", "vq", "vd"):
+            f = getattr(L, "skw_layout_kv8_%s_off" % name); f.restype = C.c_long; f.argtypes = [C.c_int] * 5
+        L.skw_layout_kv8_slot_bytes.restype = C.c_long
+        L.skw_layout_kv8_slot_bytes.argtypes = [C.c_int, C.c_int]
+        L.skw_debug_kv8_quantize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.skw_debug_attn_kv8.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
         L.skw_ctx_stream.restype = C.c_void_p
         L.skw_ctx_stream.argtypes = [C.c_void_p]
         L.skw_ctx_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
@@ -383,6 +391,17 @@ class Context:
     def get_precision(self):
         v = lib().skw_ctx_get_precision(self.h)
         return [k for k, x in self.PRECISIONS.items() if x == v][0]
+
+    CROSS_KV = {"f16": 0, "q8_0": 1}
+
+    def set_cross_kv(self, name):
+        """'f16' (default) or 'q8_0': the decode steps' cross attention streams cross K / V as ggml q8_0 blocks (include/skw_kv8.h) — half the bytes of every step.  Effective
+        only with precision 'f16_mfma'; the exact precision ignores it.  From the next call on this context."""
+        self._check(lib().skw_ctx_set_cross_kv(self.h, self.CROSS_KV[name]))
+
+    def get_cross_kv(self):
+        v = lib().skw_ctx_get_cross_kv(self.h)
+        return [k for k, x in self.CROSS_KV.items() if x == v][0]
 
     def default_params(self):
         p = FullParams()
@@ -676,6 +695,38 @@ class Context:
                                            int(sentinel), out.ctypes.data))
         return out
 
+    def kv8_quantize(self, H, n_ctx, K, V, fill_from, k_pad=0x7E00, v_pad=0x7E00, slot_k=None):
+        """k_kv8_quantize on caller-supplied K / V [slots][n_ctx][H*64] (float16 or uint16 bit patterns, natural order; positions from fill_from[s] up hold the pad patterns);
+        slot_k: the slots' key counts (None: n_ctx).  -> the q8 image as uint8 [slots][slot bytes], 0xEE where the kernel wrote nothing (byte order: the exported skw_layout_kv8_* functions)."""
+        d = H * 64
+        bits = lambda a: np.ascontiguousarray(a.view(np.uint16) if a.dtype == np.float16 else a, dtype=np.uint16)
+        K = bits(K); V = bits(V); n_slots = K.shape[0]
+        assert K.shape == (n_slots, n_ctx, d) and V.shape == K.shape
+        fill_from = np.ascontiguousarray(fill_from, dtype=np.int32); assert fill_from.size == n_slots
+        sk = None if slot_k is None else np.ascontiguousarray(slot_k, dtype=np.int32)
+        img = np.empty((n_slots, kv8_slot_bytes(H, (n_ctx + 31) & ~31)), np.uint8)
+        self._check(lib().skw_debug_kv8_quantize(self.h, H, n_ctx, n_slots, K.ctypes.data, V.ctypes.data, fill_from.ctypes.data, int(k_pad), int(v_pad),
+                                                 None if sk is None else sk.ctypes.data, img.ctypes.data))
+        return img
+
+    def attn_kv8(self, H, n_ctx, Q, K, V, fill_from, k_pad=0x7E00, v_pad=0x7E00, slot_k=None, active=None, seq=None, count=None, ofrag=0, f32_out=0, raw=0, sentinel=0x5A5A):
+        """The quantise kernel, then the q8 cross attention through its launcher (skw_debug_attn_kv8), on operands as attn16's "cross16" form takes them; slot_k: the quantiser's
+        key count per slot (None: n_ctx).  -> f32 [rows][H*64] in natural order (f32_out: unrounded), or with raw the kernel's f32 scores [rows][H][n_ctx], NaN where unwritten."""
+        d = H * 64
+        bits = lambda a: np.ascontiguousarray(a.view(np.uint16) if a.dtype == np.float16 else a, dtype=np.uint16)
+        ints = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        Q = bits(Q); K = bits(K); V = bits(V); n_slots, rows = K.shape[0], Q.shape[0]
+        assert K.shape == (n_slots, n_ctx, d) and V.shape == K.shape and Q.shape == (rows, d)
+        fill_from, slot_k, active, seq, count = (ints(a) for a in (fill_from, slot_k, active, seq, count))
+        assert fill_from.size == n_slots and (slot_k is None or slot_k.size == n_slots)
+        for a in (active, seq, count):
+            assert a is None or a.size == rows
+        out = np.empty((rows, H, n_ctx) if raw else (rows, d), dtype=np.float32)
+        self._check(lib().skw_debug_attn_kv8(self.h, H, n_ctx, n_slots, rows, (2 if ofrag else 0) | (4 if f32_out else 0) | (8 if raw else 0), Q.ctypes.data, K.ctypes.data, V.ctypes.data,
+                                             fill_from.ctypes.data, int(k_pad), int(v_pad), ptr(slot_k), ptr(active), ptr(seq), ptr(count), int(sentinel), out.ctypes.data))
+        return out
+
     def xattn_exact(self, mq, H, n_ctx, Q, K, V, fill_from, row0, nq, slot, slot_k=None, f32_out=False, k_pad=0x7E00, v_pad=0x7E00, sentinel=0x5A5A):
         """The exact precision's prompt-pass cross attention on caller-supplied operands (skw_debug_xattn_exact).  Q [rows][H*64], K / V [slots][n_ctx][H*64] as float16 (or uint16
         bit patterns), natural order; sequences (row0, nq, slot); slot_k None or a key count per slot.  mq=0: the single-query kernel on every owned row, mq=1: the
@@ -964,3 +1015,8 @@ class PolyphaseStream:
     def close(self):
         if self.h:
             lib().skw_polyphase_stream_free(self.h); self.h = None
+
+
+def kv8_slot_bytes(H, Tpad):
+    """bytes of one window slot of the q8 cross K / V image (include/skw_kv8.h)"""
+    return int(lib().skw_layout_kv8_slot_bytes(H, Tpad))

@@ -26,19 +26,43 @@ SMALL_MODEL_LOGIT_ERR_BOUND = 0.40
 MICRO_MODEL_LOGIT_ERR_BOUND = 0.70
 
 
-def bounds_for(hp):
-    """(logit_err_bound, margin_bound) for a model of these hyper-parameters: the benchmark geometry (d >= 768), the small test models, the d < 256 micro ones"""
+# cross_kv = "q8_0" (include/skw_kv8.h): the f16_mfma leg with the decode steps' cross K / V as q8_0 blocks, still against the EXACT precision.  Measured on an MI355X
+# (profiles/kv8/: bench_kv8.json, test_gpu_kv8.txt), each rounded up by 10 - 15 % as the bounds above were:
+# Benchmark model, the 64 x 30 s batch, 6 473 decisions: 66 differ (f16 in the same run: 18), every one on the exact mode's runner-up, largest exact-mode margin at one 0.3155 -> 0.36;
+# the deciding logits differ by at most 0.5836 -> 0.66 (f16 in the same run: 0.2171).  The 8-bit K and V add a relative 2^-8 per element where f16 adds 2^-11: about 2.7 x the logit
+# error, and a flip needs margin <= err(top1) + err(top2).
+# Tiny model: the five traced calls of tests/test_gpu_kv8.py (traced_runs; the test prints each call's figures, profiles/kv8/test_gpu_kv8.txt).  Largest logit error 0.4682, in
+# the K = 17 call (few keys average the least of the rounding away; the other four reach 0.2643 - 0.3537) -> 0.53; largest margin at a disagreement 0.0827, in the call of four
+# 30 s clips (0.0328 in the K = 750 call, no disagreement in the others) -> 0.095.
+KV8_LOGIT_ERR_BOUND = 0.66
+KV8_MARGIN_BOUND = 0.36
+KV8_SMALL_MODEL_LOGIT_ERR_BOUND = 0.53
+KV8_SMALL_MODEL_MARGIN_BOUND = 0.095
+
+
+def bounds_for(hp, cross_kv=None):
+    """(logit_err_bound, margin_bound) for a model of these hyper-parameters: the benchmark geometry (d >= 768), the small test models, the d < 256 micro ones.
+    cross_kv="q8_0": the bounds of that leg (benchmark geometry and the small test models; the micro models were not measured)"""
     d = hp.n_text_state
+    if cross_kv == "q8_0":
+        if d < 256:
+            raise ValueError("no measured q8_0 bounds for a d = %d model" % d)
+        return (KV8_LOGIT_ERR_BOUND, KV8_MARGIN_BOUND) if d >= 768 else (KV8_SMALL_MODEL_LOGIT_ERR_BOUND, KV8_SMALL_MODEL_MARGIN_BOUND)
     return (LOGIT_ERR_BOUND if d >= 768 else SMALL_MODEL_LOGIT_ERR_BOUND if d >= 256 else MICRO_MODEL_LOGIT_ERR_BOUND), MARGIN_BOUND
 
 
-def teacher_forced_compare(ctx, clips=None, params=None, device_ptrs=None, n_samples=None, logit_err_bound=None, margin_bound=None, contexts=None):
+def teacher_forced_compare(ctx, clips=None, params=None, device_ptrs=None, n_samples=None, logit_err_bound=None, margin_bound=None, contexts=None, cross_kv=None):
     """Runs the batch in the exact precision (free, traced), then in f16_mfma fed with the exact run's decisions.  Returns a dict of counts and
     the two result lists; leaves the context in the precision it was in.  The bounds are in logit units and belong to a model's logit scale (the
     defaults: bounds_for(model)); a model with another scale passes its own (tests/test_gpu_f16.py: 7e-4 of the range).
     contexts=[int32[513] or None per clip]: each clip decodes behind that carried text in both runs (engine.context_new); the arrays are left as they were, what the runs leave
-    comes back as contexts_exact / contexts_forced."""
-    eb, mb = bounds_for(ctx.model.hp)
+    comes back as contexts_exact / contexts_forced.
+    cross_kv=None: the context's flag is left alone (every call is the one it was before the flag existed).  "q8_0" / "f16": the forced f16_mfma leg runs with that flag and the
+    context gets back the one it had; the default bounds are then bounds_for(model, cross_kv)."""
+    if logit_err_bound is None or margin_bound is None:
+        eb, mb = bounds_for(ctx.model.hp, cross_kv if cross_kv == "q8_0" else None)
+    else:
+        eb, mb = logit_err_bound, margin_bound
     logit_err_bound = eb if logit_err_bound is None else logit_err_bound
     margin_bound = mb if margin_bound is None else margin_bound
     was = ctx.get_precision()
@@ -48,8 +72,15 @@ def teacher_forced_compare(ctx, clips=None, params=None, device_ptrs=None, n_sam
     cx_f = None if contexts is None else [None if x is None else x.copy() for x in contexts]
     res_e, tr_e = ctx.full_batch(clips, params, trace=True, contexts=cx_e, **kw)
     ctx.set_precision("f16_mfma")
-    res_f, tr_f = ctx.full_batch(clips, params, forced=[t["chosen_id"] for t in tr_e], contexts=cx_f, **kw)
-    ctx.set_precision(was)
+    kv_was = None if cross_kv is None else ctx.get_cross_kv()
+    if cross_kv is not None:
+        ctx.set_cross_kv(cross_kv)
+    try:
+        res_f, tr_f = ctx.full_batch(clips, params, forced=[t["chosen_id"] for t in tr_e], contexts=cx_f, **kw)
+    finally:
+        if cross_kv is not None:
+            ctx.set_cross_kv(kv_was)
+        ctx.set_precision(was)
     steps = disagree = 0
     worst_margin = 0.0          # largest exact-mode margin at a step where the f16_mfma argmax differs
     worst_err = 0.0             # largest |logit difference| seen (fed token; winner when both modes agree on it)
