@@ -876,6 +876,46 @@ int skwo_debug_process_logits(const skwo_model* m, const skwo_params* p, const i
     free(dc.logits); free(dc.logprobs); free(dc.probs); free(dc.tokens);
     return 0;
 }
+/* test hook: one std::generate_canonical<double, 53> from the std::mt19937 state rng_state[625] (advanced in place) — the u of the next draw */
+double skwo_debug_mt_canonical(uint32_t* rng_state) {
+    mt19937_t g; memcpy(g.mt, rng_state, sizeof g.mt); g.idx = (int)rng_state[624];
+    const double u = mt_canonical(&g);
+    memcpy(rng_state, g.mt, sizeof g.mt); rng_state[624] = (uint32_t)g.idx;
+    return u;
+}
+/* test hook: ONE call of whisper_process_logits + whisper_sample_token on caller-supplied logits, as skwo_debug_process_logits, at a temperature: > 0 draws from
+ * std::discrete_distribution over the decoder's probs on the std::mt19937 in rng_state[625] (mt[624] + index, in and out; > 624 is refused: -2), 0 takes the best token
+ * and leaves the generator alone.  out_probs: the f32 row the draw reads.  -1 if the token loop could not have produced the history. */
+int skwo_debug_sample_logits(const skwo_model* m, const skwo_params* p, const int32_t* hist, int n_hist, const float* raw_logits, float temperature, uint32_t* rng_state,
+                             float* out_logits, float* out_logprobs, float* out_probs, skwo_token* chosen, float* no_speech_prob) {
+    const int NV = m->hp.n_vocab;
+    if (!rng_state || rng_state[624] > 624u) return -2;
+    decoder_t dc; memset(&dc, 0, sizeof dc);
+    dc.logits = xmalloc_f(NV); dc.logprobs = xmalloc_f(NV); dc.probs = xmalloc_f(NV); dc.cap = n_hist + 1; dc.tokens = (skwo_token*)calloc(dc.cap, sizeof(skwo_token)); dc.min_margin = INFINITY;
+    dc.seek_delta = 100 * WHISPER_CHUNK_SIZE; dc.has_ts = 0;
+    for (int i = 0; i < n_hist; ++i) {
+        dc.tokens[i].id = hist[i]; dc.n_tokens = i + 1;
+        if (hist[i] > m->tok_beg) {
+            const int sd = 2 * (hist[i] - m->tok_beg);
+            if (dc.has_ts && dc.seek_delta > sd && dc.result_len < i) { free(dc.logits); free(dc.logprobs); free(dc.probs); free(dc.tokens); return -1; }   /* the loop would have failed here */
+            dc.seek_delta = sd; dc.result_len = i + 1; dc.has_ts = 1;
+        }
+    }
+    float nsp = 0.0f;
+    process_logits(m, p, &dc, raw_logits, &nsp, temperature);
+    if (out_logits) memcpy(out_logits, dc.logits, sizeof(float) * NV);
+    if (out_logprobs) memcpy(out_logprobs, dc.logprobs, sizeof(float) * NV);
+    if (out_probs) memcpy(out_probs, dc.probs, sizeof(float) * NV);
+    if (temperature > 0.0f) {
+        mt19937_t g; memcpy(g.mt, rng_state, sizeof g.mt); g.idx = (int)rng_state[624];
+        const skwo_token tk = sample_dist(m, &dc, &g);
+        if (chosen) *chosen = tk;
+        memcpy(rng_state, g.mt, sizeof g.mt); rng_state[624] = (uint32_t)g.idx;
+    } else if (chosen) *chosen = sample_best(m, &dc);
+    if (no_speech_prob) *no_speech_prob = nsp;
+    free(dc.logits); free(dc.logprobs); free(dc.probs); free(dc.tokens);
+    return 0;
+}
 /* the ids the static suppression rules name, for the checker's side of the comparison: kind 0 = specials (not, sot, nosp, solm, translate, transcribe, prev, languages),
  * 1 = the non-speech list (suppress_nst), 2 = the blank rule's pair (eot, " ").  Returns the count (ids may be NULL). */
 int skwo_debug_rule_ids(const skwo_model* m, int kind, int32_t* ids, int cap) {

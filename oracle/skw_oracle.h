@@ -121,6 +121,12 @@ void skwo_result_free(skwo_result*);
  * leaves the timestamp-mass rule out; -1 if the token loop could not have produced the history */
 int skwo_debug_process_logits(const skwo_model*, const skwo_params*, const int32_t* hist, int n_hist, const float* raw_logits, float temperature, int flags,
                               float* out_logits, float* out_logprobs, skwo_token* chosen, float* no_speech_prob);
+/* the same at a temperature (tests/test_cpu_sampler_draw.py, tests/test_gpu_sampler_draw.py): > 0 runs whisper_sample_token(best = false) on the std::mt19937 state
+ * rng_state[625] (mt[624] + index, in and out; an index above 624: -2), 0 runs best = true and leaves the state alone; out_probs: the f32 row the draw reads */
+int skwo_debug_sample_logits(const skwo_model*, const skwo_params*, const int32_t* hist, int n_hist, const float* raw_logits, float temperature, uint32_t* rng_state,
+                             float* out_logits, float* out_logprobs, float* out_probs, skwo_token* chosen, float* no_speech_prob);
+/* one std::generate_canonical<double, 53> from a std::mt19937 state (advanced in place): the u of the state's next draw */
+double skwo_debug_mt_canonical(uint32_t* rng_state);
 /* kind 0: always-suppressed specials; 1: the suppress_nst list; 2: the blank rule's pair; 3: {eot, notimestamps, timestamp_begin, nospeech, sot} */
 int skwo_debug_rule_ids(const skwo_model*, int kind, int32_t* ids, int cap);
 

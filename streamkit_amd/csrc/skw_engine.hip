@@ -1997,12 +1997,25 @@ extern "C" int skw_full_batch_traced(skw_ctx* c, const skw_full_params* p, const
 // oracle/skwo_debug_process_logits does.  Outputs per row: the decision (skw_token), its trace record, and (form 1, optional) the filtered logits.
 // pv (skw_debug_sample_rows_mixed): one skw_full_params per row — the launch is the per-row form of the sampler, each row under its own rules and its own static mask.
 // rv (skw_debug_sample_rows_rules): one skw_decode_rules (or NULL) per row — k_dec_constrain runs on the rows' logits ahead of the sampler, as in the decode step.
+// ex (skw_debug_sample_rows_ex): per-row temperatures and generator states, the launch with or without the trace buffers, and what else the sampler leaves behind:
+//  temperature [n_rows] (null: 0 everywhere) — lp.any_sampled is 1 iff some row's is > 0; rng_state [n_rows][625], in and out (null: every row on generator 0, untouched
+//  memory of the context): row r draws from generator r (clip_idx[r] = r), an index above 624 is refused like skw_full_batch_rng's; trace = 0: forced = trace = nullptr
+//  reach the launcher (k_dec_sample<false, any_sampled, ROWS>), trace_out is left alone; probs_out [n_rows][n_vocab]: the f32 probabilities of rows at a temperature > 0
+//  (other rows' entries are left alone); no_speech_prob / n_tokens / cur_token / active [n_rows]: the row's state after the launch; kernel_id: SKW_SMPK_* bits of the
+//  kernel the launcher picked (skw_dec_sample_kernel, the function it branches on).
+struct skw_sample_rows_ex { const float* temperature; uint32_t* rng_state; int32_t trace; int32_t kernel_id; float* probs_out; float* no_speech_prob;
+                            int32_t* n_tokens; int32_t* cur_token; int32_t* active; };
 static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const skw_full_params* pv, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
                                   const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out,
-                                  const skw_decode_rules* const* rv = nullptr) {
+                                  const skw_decode_rules* const* rv = nullptr, skw_sample_rows_ex* ex = nullptr) {
     char* errbuf = c->errbuf; errbuf[0] = 0;
     WS_READY(c);
     if (n_rows < 1 || n_rows > c->max_batch) { snprintf(errbuf, 512, "n_rows %d outside [1, %d]", n_rows, c->max_batch); return -1; }
+    if (ex && ex->rng_state) for (int r = 0; r < n_rows; ++r) if (ex->rng_state[(size_t)r * SKW_RNG_WORDS + 624] > 624u) {
+        snprintf(errbuf, 512, "row %d: the generator state handed in is not a std::mt19937 state (index %u)", r, ex->rng_state[(size_t)r * SKW_RNG_WORDS + 624]); return -1; }
+    if (ex && ex->temperature && !ex->rng_state) for (int r = 0; r < n_rows; ++r) if (ex->temperature[r] > 0.0f) {
+        snprintf(errbuf, 512, "row %d: a temperature > 0 needs rng_state (one generator per row)", r); return -1; }
+    const bool with_trace = !ex || ex->trace;
     HIPCHK(hipSetDevice(c->m->device));
     const skw_model* m = c->m; const int NV = m->hp.n_vocab, MT = c->max_tok;
     for (int r = 0; r < n_rows; ++r) if (n_hist[r] < 0 || n_hist[r] >= MT || n_hist[r] > hist_stride) { snprintf(errbuf, 512, "row %d: history of %d tokens (at most %d)", r, n_hist[r], MT - 1);
@@ -2020,12 +2033,15 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
         HIPCHK(hipMemcpyAsync(c->row_rules, rules.data(), sizeof(SkwRowRules) * n_rows, hipMemcpyHostToDevice, c->stream));
     } else { build_static_mask(c, p); lp = make_logit_params(m, p); }
     lp.any_sampled = 0;
+    if (ex && ex->temperature) for (int r = 0; r < n_rows; ++r) if (ex->temperature[r] > 0.0f) lp.any_sampled = 1;
     std::vector<SkwTokenOut> toks((size_t)n_rows * MT); memset(toks.data(), 0, toks.size() * sizeof(SkwTokenOut));
     std::vector<int> forced((size_t)n_rows * MT, -1), zero(n_rows, 0);
+    if (ex && ex->rng_state) for (int r = 0; r < n_rows; ++r) zero[r] = r;      // (row r on generator r)
     for (int r = 0; r < n_rows; ++r) {
         SkwSeqState& s = c->h_st[r]; memset(&s, 0, sizeof s);
         s.active = 1; s.seek_delta = SKW_WINDOW_FRAMES; s.seek = 0; s.n_prompt = 1; s.min_margin = INFINITY;
         s.cur_pos = n_hist[r]; s.n_tokens = n_hist[r];
+        if (ex && ex->temperature) s.temperature = ex->temperature[r];
         // the history's timestamps through the token loop's update (as the parent of this hook, oracle/skwo_debug_process_logits, replays them): how has_ts / seek_delta /
         // result_len follow them, and the one failure a history can show.  No stop rule can fire: no budget, no loop bound, the audio without end, and <|endoftext|> is no timestamp
         s.seek_end = INT32_MAX;
@@ -2042,22 +2058,38 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
     HIPCHK(hipMemcpyAsync(c->forced_dev, forced.data(), sizeof(int) * forced.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->clip_idx, zero.data(), sizeof(int) * n_rows, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->logits, logits_host, sizeof(float) * (size_t)n_rows * NV, hipMemcpyHostToDevice, c->stream));
+    if (ex && ex->rng_state) HIPCHK(hipMemcpyAsync(c->rng, ex->rng_state, sizeof(uint32_t) * SKW_RNG_WORDS * n_rows, hipMemcpyHostToDevice, c->stream));
+    const int* forced_dev = with_trace ? c->forced_dev : nullptr; SkwTraceStep* trace_dev = with_trace ? c->trace_dev : nullptr;
     if (rv) skw_dec_constrain(c->logits, NV, lp.tok_eot, c->row_cons, c->st, c->toks, MT, n_rows, c->stream);
     skw_debug_force_stream_sampler(form == 1);
+    if (ex) ex->kernel_id = skw_dec_sample_kernel(lp, trace_dev != nullptr, pv != nullptr);
     if (pv) skw_dec_sample_rows(c->logits, c->static_mask_pair, lp, c->row_rules, c->st, c->toks, MT, n_rows, c->d_row_live, c->probs, c->rng, c->clip_idx, c->prompt_buf, c->stream,
-                                c->forced_dev, c->trace_dev);
-    else skw_dec_sample(c->logits, c->static_mask, lp, c->st, c->toks, MT, n_rows, c->d_row_live, c->probs, c->rng, c->clip_idx, c->prompt_buf, c->stream, c->forced_dev, c->trace_dev);
+                                forced_dev, trace_dev);
+    else skw_dec_sample(c->logits, c->static_mask, lp, c->st, c->toks, MT, n_rows, c->d_row_live, c->probs, c->rng, c->clip_idx, c->prompt_buf, c->stream, forced_dev, trace_dev);
     skw_debug_force_stream_sampler(0);
     HIPCHK(hipGetLastError());
     std::vector<SkwTraceStep> tr((size_t)n_rows * MT);
     HIPCHK(hipMemcpyAsync(toks.data(), c->toks, sizeof(SkwTokenOut) * toks.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(tr.data(), c->trace_dev, sizeof(SkwTraceStep) * tr.size(), hipMemcpyDeviceToHost, c->stream));
+    if (with_trace) HIPCHK(hipMemcpyAsync(tr.data(), c->trace_dev, sizeof(SkwTraceStep) * tr.size(), hipMemcpyDeviceToHost, c->stream));
     if (filtered_out) HIPCHK(hipMemcpyAsync(filtered_out, c->logits, sizeof(float) * (size_t)n_rows * NV, hipMemcpyDeviceToHost, c->stream));
+    std::vector<SkwSeqState> st_after(ex ? n_rows : 0);
+    if (ex) {
+        HIPCHK(hipMemcpyAsync(st_after.data(), c->st, sizeof(SkwSeqState) * n_rows, hipMemcpyDeviceToHost, c->stream));
+        if (ex->rng_state) HIPCHK(hipMemcpyAsync(ex->rng_state, c->rng, sizeof(uint32_t) * SKW_RNG_WORDS * n_rows, hipMemcpyDeviceToHost, c->stream));
+        if (ex->probs_out && ex->temperature) for (int r = 0; r < n_rows; ++r) if (ex->temperature[r] > 0.0f)
+            HIPCHK(hipMemcpyAsync(ex->probs_out + (size_t)r * NV, c->probs + (size_t)r * skw_probs_row_floats(NV), sizeof(float) * NV, hipMemcpyDeviceToHost, c->stream));
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int r = 0; r < n_rows; ++r) {
         const SkwTokenOut& t = toks[(size_t)r * MT + n_hist[r]];
         if (tok_out) { skw_token o; o.id = t.id; o.tid = t.tid; o.p = t.p; o.plog = t.plog; o.pt = t.pt; o.ptsum = t.ptsum; o.margin = t.margin; tok_out[r] = o; }
-        if (trace_out) memcpy(&trace_out[r], &tr[(size_t)r * MT + n_hist[r]], sizeof(skw_trace_step));
+        if (trace_out && with_trace) memcpy(&trace_out[r], &tr[(size_t)r * MT + n_hist[r]], sizeof(skw_trace_step));
+        if (ex) {
+            if (ex->no_speech_prob) ex->no_speech_prob[r] = st_after[r].no_speech_prob;
+            if (ex->n_tokens) ex->n_tokens[r] = st_after[r].n_tokens;
+            if (ex->cur_token) ex->cur_token[r] = st_after[r].cur_token;
+            if (ex->active) ex->active[r] = st_after[r].active;
+        }
     }
     return 0;
 }
@@ -2075,6 +2107,12 @@ extern "C" int skw_debug_sample_rows_rules(skw_ctx* c, const skw_full_params* pa
                                            const skw_decode_rules* const* rules /* [n_rows], entries may be NULL */) {
     if (!params || !rules) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_rules: params and rules are one per row (rules entries may be NULL)"); return -1; }
     return debug_sample_rows_impl(c, params, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out, rules);
+}
+// per_row: p is one skw_full_params per row (the per-row form of the sampler, as skw_debug_sample_rows_mixed), else one block for the launch
+extern "C" int skw_debug_sample_rows_ex(skw_ctx* c, const skw_full_params* p, int per_row, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
+                                        const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out, skw_sample_rows_ex* ex) {
+    if (!p || !ex) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_ex: params and ex are required"); return -1; }
+    return debug_sample_rows_impl(c, p, per_row ? p : nullptr, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out, nullptr, ex);
 }
 extern "C" void skw_trace_free(skw_trace* t) { if (!t) return; free(t->steps); t->steps = nullptr; t->n = 0; }
 extern "C" void skw_result_free(skw_result* r) { if (!r) return; free(r->segments); free(r->tokens); free(r->text); memset(r, 0, sizeof *r); }

@@ -250,6 +250,9 @@ struct SkwRowConstraints { float penalty; int32_t ngram, n_bias, pad; int32_t bi
 // k_dec_constrain, between the logits GEMM and the sampler: bias, repetition penalty over the distinct text tokens (id < tok_eot) of the row's pass so far (toks[0 .. n_tokens)), then the
 // no-repeat n-gram ban over the same tokens; one workgroup per row, the row's logits edited in place.  Rows that are finished, still feeding their prompt or unconstrained return at once.
 void skw_dec_constrain(float* logits, int n_vocab, int tok_eot, const SkwRowConstraints* cons, const SkwSeqState* st, const SkwTokenOut* toks, int max_tok, int B, hipStream_t s);
+// the kernel a sampler launch runs, as bits: k_dec_sample<TRACE, DRAW, ROWS>, or k_dec_sample_stream<ROWS> with SKW_SMPK_STREAM set (trace: a trace buffer is handed in)
+enum { SKW_SMPK_ROWS = 1, SKW_SMPK_DRAW = 2, SKW_SMPK_TRACE = 4, SKW_SMPK_STREAM = 8 };
+int skw_dec_sample_kernel(const SkwLogitParams& p, bool trace, bool rows);
 void skw_debug_force_stream_sampler(int on);   // tests: the streaming sampler (filters the logits row in place) even where the register-resident form applies
 void skw_rng_seed(uint32_t* rng, int n_clips, uint32_t seed, hipStream_t s);   // std::mt19937(seed) for every clip
 

@@ -14,6 +14,7 @@
 #include <atomic>
 #include <cstring>
 #include "../../include/skw_math.h"
+#include "../../include/skw_draw.h"
 
 #include "skw_dev_common.h"
 
@@ -1540,28 +1541,20 @@ __device__ __forceinline__ void smp_trace_step(SkwTokenOut& tk, const float* lg,
 // S + p == S under round-to-nearest whenever 0 <= p < ulp(S) / 2: a 64-element block whose largest element is below that bound cannot move the running sum,
 // whatever the order inside it, and since the sum never decreases it stays immovable — such blocks are skipped WITHOUT changing a bit of the sequential result.
 // (Peaked distributions — most real steps — leave a few dozen elements in the chain; a flat one keeps all 51 865.)
-// 2^(exponent(s) - 53); 0 for s == 0 / subnormal: nothing is skipped then
-__device__ __forceinline__ double half_ulp_f64(double s) { const int e = (int)((__double_as_longlong(s) >> 52) & 0x7ff); return e == 0 ? 0.0 : __longlong_as_double((long long)max(e - 53, 1) << 52); }
+// The serial walks themselves (the half-ulp bound, the first chain's sum, the second chain's cp with its block-end compare and last-element rule) are
+// include/skw_draw.h: host and device, held to the sequential definition on the CPU by tests/cpp/draw_main.cpp.
 __device__ int block_discrete_draw(const float* probs, double* q, int n, uint32_t* mt, float* lds, double* s_sum, int* s_hit) {
     const int tid = threadIdx.x, nt = blockDim.x;
-    typedef double f64x2 __attribute__((ext_vector_type(2)));
-    __shared__ double bmax[64];                                  // per 64-element block of the staged chunk
+    __shared__ double bmax[SKW_DRAW_CHUNK / SKW_DRAW_BLOCK];      // per 64-element block of the staged chunk
     double* ldsd = (double*)lds;                                 // the chunk as doubles: 4 096 per stage (the serial lane then issues one LDS read and two adds per two elements)
     double sum = 0.0;
-    for (int c0 = 0; c0 < n; c0 += 4096) {
-        const int m = min(4096, n - c0);
+    for (int c0 = 0; c0 < n; c0 += SKW_DRAW_CHUNK) {
+        const int m = min(SKW_DRAW_CHUNK, n - c0);
         for (int i = tid; i < m; i += nt) ldsd[i] = (double)probs[c0 + i];
         __syncthreads();
         if (tid < 64) { double mx = 0.0; for (int i = tid * 64; i < min(tid * 64 + 64, m); ++i) mx = fmax(mx, ldsd[i]); bmax[tid] = mx; }
         __syncthreads();
-        if (tid == 0) {
-            for (int b0 = 0; b0 < m; b0 += 64) {
-                if (bmax[b0 >> 6] < half_ulp_f64(sum)) continue;
-                const int e = min(b0 + 64, m); int i = b0;
-                for (; i + 2 <= e; i += 2) { const f64x2 v = *(const f64x2*)(ldsd + i); sum += v[0]; sum += v[1]; }
-                for (; i < e; ++i) sum += ldsd[i];
-            }
-        }
+        if (tid == 0) sum = skw_draw_sum_chunk(ldsd, bmax, m, sum, nullptr);
         __syncthreads();
     }
     if (tid == 0) {
@@ -1576,27 +1569,13 @@ __device__ int block_discrete_draw(const float* probs, double* q, int n, uint32_
     __threadfence_block();
     __syncthreads();
     double cp = 0.0;
-    for (int c0 = 0; c0 < n; c0 += 4096) {
-        const int m = min(4096, n - c0);
+    for (int c0 = 0; c0 < n; c0 += SKW_DRAW_CHUNK) {
+        const int m = min(SKW_DRAW_CHUNK, n - c0);
         for (int i = tid; i < m; i += nt) ldsd[i] = q[c0 + i];
         __syncthreads();
         if (tid < 64) { double mx = 0.0; for (int i = tid * 64; i < min(tid * 64 + 64, m); ++i) mx = fmax(mx, ldsd[i]); bmax[tid] = mx; }
         __syncthreads();
-        if (tid == 0) {
-            int hit = -1;
-            for (int b0 = 0; b0 < m && hit < 0; b0 += 64) {
-                const int e = min(b0 + 64, m); const bool last_block = c0 + e == n;
-                if (!last_block && bmax[b0 >> 6] < half_ulp_f64(cp)) continue;      // (the block that holds the last element is walked: cp = 1 there by definition)
-                if (!last_block) {      // cp never decreases: a block whose END is still below u holds no hit — one compare per block instead of one per element
-                    double c2 = cp; int i = b0;
-                    for (; i + 2 <= e; i += 2) { const f64x2 v = *(const f64x2*)(ldsd + i); c2 += v[0]; c2 += v[1]; }
-                    for (; i < e; ++i) c2 += ldsd[i];
-                    if (c2 < u) { cp = c2; continue; }
-                }
-                for (int i = b0; i < e; ++i) { cp += ldsd[i]; if (c0 + i == n - 1) cp = 1.0; if (!(cp < u)) { hit = c0 + i; break; } }
-            }
-            *s_hit = hit;
-        }
+        if (tid == 0) *s_hit = skw_draw_cp_chunk(ldsd, bmax, m, c0, n, u, &cp, nullptr);
         __syncthreads();
         if (*s_hit >= 0) break;      // (uniform)
         __syncthreads();
@@ -1694,8 +1673,11 @@ __global__ __launch_bounds__(1024) void k_dec_sample_stream(float* logits_all, c
     sum_ts = block_sum_f64(sum_ts, sh_d);
     // margin between the two largest admissible logits
     float t1 = block_max(top1, sh_f);
-    float cand = (top1 == t1) ? top2 : top1;   // exact duplicates of the max report a margin of 0 via top2 only within a thread; fine for diagnostics
+    float cand = (top1 == t1) ? top2 : top1;
     float t2 = block_max(cand, sh_f);
+    // an exact duplicate of the maximum in ANOTHER thread is the runner-up (margin 0, as the sequential rule and the register-resident form have it): a thread that holds
+    // the maximum offers only its own second value above
+    if (block_sum_f64(top1 == t1 ? 1.0 : 0.0, sh_d) > 1.0) t2 = t1;
     if (sampled) { __threadfence_block(); __syncthreads(); }
     if (tid != 0) return;
     SkwTokenOut tk; tk.id = best.i; tk.p = best.v;
@@ -1967,17 +1949,24 @@ void skw_static_mask_pack(const uint8_t* mask, int n_vocab, uint8_t* out) {
 }
 static int g_force_stream_sampler = 0;      // tests: run the streaming form where the register-resident one would (it leaves the filtered row in memory)
 void skw_debug_force_stream_sampler(int on) { g_force_stream_sampler = on; }
+// which sampler a launch runs: the function the launcher itself branches on (tests assert it through skw_debug_sample_rows_ex)
+int skw_dec_sample_kernel(const SkwLogitParams& p, bool trace, bool rows) {
+    if (!g_force_stream_sampler && p.n_vocab <= SMP_PT * SMP_NT && std::min(p.tok_eot, p.tok_beg) >= SMP_TX * SMP_NT)
+        return (trace ? SKW_SMPK_TRACE | SKW_SMPK_DRAW : p.any_sampled ? SKW_SMPK_DRAW : 0) | (rows ? SKW_SMPK_ROWS : 0);
+    return SKW_SMPK_STREAM | (rows ? SKW_SMPK_ROWS : 0);
+}
 template <bool ROWS>
 static void dec_sample_launch(float* logits, const uint8_t* static_mask, const SkwLogitParams& p, SkwSeqState* st, SkwTokenOut* toks, int max_tok, int B, int* n_active,
                               float* probs, uint32_t* rng, const int* clip_idx, const int* prompt_buf, hipStream_t s, const int* forced, SkwTraceStep* trace, const SkwRowRules* rules) {
-    if (!g_force_stream_sampler && p.n_vocab <= SMP_PT * SMP_NT && std::min(p.tok_eot, p.tok_beg) >= SMP_TX * SMP_NT) {
-        if (trace) hipLaunchKernelGGL((k_dec_sample<true, true, ROWS>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng, clip_idx, prompt_buf,
-            forced, trace, rules);
-        else if (p.any_sampled) hipLaunchKernelGGL((k_dec_sample<false, true, ROWS>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs,
-            rng, clip_idx, prompt_buf, nullptr, nullptr, rules);
-        else hipLaunchKernelGGL((k_dec_sample<false, false, ROWS>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng, clip_idx, prompt_buf,
-            nullptr, nullptr, rules);
-    } else hipLaunchKernelGGL(k_dec_sample_stream<ROWS>, dim3(B), dim3(1024), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng, clip_idx, prompt_buf, forced, trace, rules);
+    const int k = skw_dec_sample_kernel(p, trace != nullptr, ROWS);
+    if (k & SKW_SMPK_STREAM) hipLaunchKernelGGL(k_dec_sample_stream<ROWS>, dim3(B), dim3(1024), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng, clip_idx,
+        prompt_buf, forced, trace, rules);
+    else if (k & SKW_SMPK_TRACE) hipLaunchKernelGGL((k_dec_sample<true, true, ROWS>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng,
+        clip_idx, prompt_buf, forced, trace, rules);
+    else if (k & SKW_SMPK_DRAW) hipLaunchKernelGGL((k_dec_sample<false, true, ROWS>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs,
+        rng, clip_idx, prompt_buf, nullptr, nullptr, rules);
+    else hipLaunchKernelGGL((k_dec_sample<false, false, ROWS>), dim3(B), dim3(SMP_NT), 0, s, logits, static_mask, p, st, toks, max_tok, n_active, probs, rng, clip_idx, prompt_buf,
+        nullptr, nullptr, rules);
 }
 void skw_dec_sample(float* logits, const uint8_t* static_mask, SkwLogitParams p, SkwSeqState* st, SkwTokenOut* toks, int max_tok, int B, int* n_active,
                     float* probs, uint32_t* rng, const int* clip_idx, const int* prompt_buf, hipStream_t s, const int* forced, SkwTraceStep* trace) {

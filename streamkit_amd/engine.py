@@ -209,6 +209,8 @@ def lib():
         L.skw_debug_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
         L.skw_debug_sample_rows.argtypes = [C.c_void_p, C.POINTER(FullParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.skw_debug_sample_rows_mixed.argtypes = [C.c_void_p, C.POINTER(FullParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.skw_debug_sample_rows_ex.argtypes = [C.c_void_p, C.POINTER(FullParams), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(SampleRowsEx)]
         L.skw_debug_enable.argtypes = [C.c_int]
         L.skw_debug_get.restype = C.c_long
         L.skw_debug_get.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
@@ -281,6 +283,17 @@ class Gemm16EpiArgs(C.Structure):      # struct skw_gemm16_epi_args (skw_engine.
                 ("pos", C.c_void_p), ("force_small", C.c_int32),
                 ("C", C.c_void_p), ("c_bytes", C.c_int64), ("ldc", C.c_int64), ("C2", C.c_void_p), ("C3", C.c_void_p), ("c2_bytes", C.c_int64), ("ldc2", C.c_int64),
                 ("kernel_id", C.c_int32)]
+
+
+class SampleRowsEx(C.Structure):      # skw_sample_rows_ex (skw_engine.hip)
+    _fields_ = [("temperature", C.c_void_p), ("rng_state", C.c_void_p), ("trace", C.c_int32), ("kernel_id", C.c_int32), ("probs_out", C.c_void_p), ("no_speech_prob", C.c_void_p),
+                ("n_tokens", C.c_void_p), ("cur_token", C.c_void_p), ("active", C.c_void_p)]
+
+
+# what a sampler launch ran (SKW_SMPK_* of skw_kernels.h): k_dec_sample<TRACE, DRAW, ROWS> or k_dec_sample_stream<ROWS>
+def sampler_kernel_name(kernel_id):
+    b = lambda m: "true" if kernel_id & m else "false"
+    return "k_dec_sample_stream<%s>" % b(1) if kernel_id & 8 else "k_dec_sample<%s, %s, %s>" % (b(4), b(2), b(1))
 
 
 _TOKEN_DT = np.dtype([("id", "<i4"), ("tid", "<i4"), ("p", "<f4"), ("plog", "<f4"), ("pt", "<f4"), ("ptsum", "<f4"), ("margin", "<f4")])      # struct Token
@@ -630,12 +643,15 @@ class Context:
         self._check(lib().skw_decode_logits(self.h, t.ctypes.data, t.size, out.ctypes.data))
         return out
 
-    def sample_rows(self, hists, logits, params=None, form=0, want_filtered=False, rules=None):
+    def sample_rows(self, hists, logits, params=None, form=0, want_filtered=False, rules=None, temperature=None, rng_state=None, trace=True, extras=False):
         """K11 on its own (skw_debug_sample_rows): one sampler launch decides the next token of len(hists) decoders whose sampled tokens so far are
         hists[r], on caller-supplied logits [rows][n_vocab].  form 0: the decode step's sampler; 1: the streaming kernel (leaves the filtered row
         in memory: want_filtered).  -> (tokens structured array, trace records, filtered logits or None)
         params=[FullParams per row]: the per-row form of the sampler (skw_debug_sample_rows_mixed) — every row under its own rules and its own static mask.
-        rules=[DecodeRules or None per row]: skw_debug_sample_rows_rules — k_dec_constrain on the rows' logits, then the per-row form of the sampler."""
+        rules=[DecodeRules or None per row]: skw_debug_sample_rows_rules — k_dec_constrain on the rows' logits, then the per-row form of the sampler.
+        temperature=[per row], rng_state=uint32 [rows][625] (updated in place: row r draws from generator r), trace=False (the launch without trace buffers) or extras=True:
+        skw_debug_sample_rows_ex — a fourth element is returned, a dict of kernel (the instantiation the launcher picked), probs [rows][n_vocab] (rows at a temperature > 0;
+        NaN elsewhere), no_speech_prob, n_tokens, cur_token, active [rows] (the rows' state after the launch)."""
         per_row = isinstance(params, (list, tuple))
         R = len(hists)
         if rules is not None:
@@ -652,6 +668,21 @@ class Context:
         filt = np.empty_like(lg) if want_filtered else None
         toks = np.zeros(R, dtype=_TOKEN_DT)
         tr = np.zeros(R, dtype=TRACE_DT)
+        if temperature is not None or rng_state is not None or not trace or extras:
+            if rules is not None:
+                raise ValueError("sample_rows: rules= goes with the plain call only")
+            NV = self.model.hp.n_vocab
+            t = np.zeros(R, np.float32) if temperature is None else np.ascontiguousarray(temperature, dtype=np.float32).reshape(R)
+            if rng_state is not None:
+                assert rng_state.dtype == np.uint32 and rng_state.shape == (R, 625) and rng_state.flags["C_CONTIGUOUS"]
+            out = dict(probs=np.full((R, NV), np.nan, np.float32), no_speech_prob=np.zeros(R, np.float32), n_tokens=np.zeros(R, np.int32), cur_token=np.zeros(R, np.int32),
+                       active=np.zeros(R, np.int32))
+            ex = SampleRowsEx(t.ctypes.data, None if rng_state is None else rng_state.ctypes.data, 1 if trace else 0, -1, out["probs"].ctypes.data, out["no_speech_prob"].ctypes.data,
+                              out["n_tokens"].ctypes.data, out["cur_token"].ctypes.data, out["active"].ctypes.data)
+            self._check(lib().skw_debug_sample_rows_ex(self.h, p if per_row else C.byref(p), 1 if per_row else 0, R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
+                                                       filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data, C.byref(ex)))
+            out["kernel"] = sampler_kernel_name(ex.kernel_id)
+            return toks, tr, filt, out
         if rules is not None:
             self._check(lib().skw_debug_sample_rows_rules(self.h, p if per_row else (FullParams * R)(*([p] * R)), R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
                                                           filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data, rules_ptr))

@@ -243,6 +243,22 @@ def test_discrete_distribution_restatement_matches_libstdcxx(tmp_path):
         out = (C.c_int32 * n_draws)()
         lib.skwo_discrete_draw(w.ctypes.data_as(C.c_void_p), n, C.c_uint32(seed), n_draws, out)
         assert list(out) == ref, kind
+    # the adversarial rows of tests/sampler_draw_lib.py at the vocabulary's size: the oracle's restatement AND the numpy reference the sampler's tests use, both against libstdc++
+    import sampler_draw_lib as sd
+    n = 51865
+    for fi, fam in enumerate(sd.WEIGHT_FAMILIES):
+        w = sd.weight_family(fam, n, np.random.default_rng(100 * fi + n % 97))
+        n_draws = 320   # crosses the twist
+        inp = "%d %d %d\n%s\n" % (fi, n_draws, n, " ".join(repr(float(x)) for x in w))
+        ref = [int(x) for x in subprocess.check_output([exe], input=inp.encode()).split()]
+        out = (C.c_int32 * n_draws)()
+        lib.skwo_discrete_draw(w.ctypes.data_as(C.c_void_p), n, C.c_uint32(fi), n_draws, out)
+        assert list(out) == ref, fam
+        st = sd.mt_state(fi, 624); _, _, cp = sd.draw_ref(w, 0.0); got = []
+        for _ in range(n_draws):
+            u, st = sd.generator_ref(st)
+            got.append(int(np.searchsorted(cp, u, "left")))
+        assert got == ref, fam
 
 
 def test_temperature_ladder_in_oracle(micro_model_path):

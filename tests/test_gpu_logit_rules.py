@@ -50,8 +50,9 @@ def test_sampler_matches_transformers_checked_fixture(gpu_tiny, oracle_tiny):
                         x[lr.hf_extra_suppressed(h, sp, NV)] = -np.inf
                     rows.append(x)
                 lg = np.stack(rows)
-                tk0, tr0, _ = ctx.sample_rows(hists, lg, p, form=0)
-                tk1, tr1, filt = ctx.sample_rows(hists, lg, p, form=1, want_filtered=True)
+                tk0, tr0, _, ex0 = ctx.sample_rows(hists, lg, p, form=0, extras=True)
+                tk1, tr1, filt, ex1 = ctx.sample_rows(hists, lg, p, form=1, want_filtered=True, extras=True)
+                assert (ex0["kernel"], ex1["kernel"]) == ("k_dec_sample<true, true, false>", "k_dec_sample_stream<false>")
                 for r, c in enumerate(batch):
                     want = c[variant]
                     # the admissible set (streaming form) and the decision (both forms) against the HF-checked fixture
@@ -60,8 +61,10 @@ def test_sampler_matches_transformers_checked_fixture(gpu_tiny, oracle_tiny):
                     assert np.float32(tk0["plog"][r]) == np.float32(want["plog"]) and np.float32(tk1["plog"][r]) == np.float32(want["plog"])
                     # ... and every field of the decision against the oracle on the same input, bit for bit
                     o = lr.oracle_process(om, po, hists[r], rows[r])
-                    for f in ("id", "tid", "p", "plog", "pt", "ptsum"):
+                    for f in ("id", "tid", "p", "plog", "pt", "ptsum", "margin"):
                         assert np.float32(tk0[f][r]) == np.float32(o[2][f]) and np.float32(tk1[f][r]) == np.float32(o[2][f]), (c["seed"], variant, f, tk0[f][r], tk1[f][r], o[2][f])
+                    # (computed on the first decision of a window only; 0 elsewhere, on both sides)
+                    assert np.float32(ex0["no_speech_prob"][r]) == np.float32(o[3]) and np.float32(ex1["no_speech_prob"][r]) == np.float32(o[3]), (c["seed"], variant, o[3])
                     assert np.array_equal(np.isneginf(filt[r]), np.isneginf(o[0]))
                     fin = ~np.isneginf(o[0])
                     assert np.array_equal(filt[r][fin], o[0][fin])
