@@ -26,6 +26,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "skw_align_params.h"      /* skw_align_params; the arithmetic and its helpers: skw_align.h */
+#include "skw_grammar.h"           /* skw_grammar: the table, the rule it applies to a row of logits, its check and CPU evaluator */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -222,6 +223,22 @@ int  skw_align_batch(skw_ctx*, const skw_full_params* params /* [n_clips] */, co
                      const int32_t* const* text_tokens, const int32_t* n_text, const skw_align_params* const* align, skw_token_times* times /* [n_clips] out */);
 void skw_token_times_free(skw_token_times*);
 
+/* Grammar-constrained decoding: a clip may bring a grammar — a byte-level DFA the transcript's text has to match in full (include/skw_grammar.h states the table, the rule and
+ * its limits: REGULAR languages only, where whisper.cpp's grammar_rules are GBNF; per temperature pass and per window, so it is meant for utterances of one window; timestamps
+ * are transparent to the match; the penalty is finite, so where the sampler's own masks remove every fitting token the best non-fitting one wins).  The rule is stage 4 on the
+ * f32 logits row, after skw_decode_rules' three and ahead of the sampler (k_dec_grammar); not applied in the language-detection pass nor while a row feeds its prompt.
+ * skw_full_batch_grammar is skw_full_batch_aligned with one grammar per clip: grammar == NULL or a NULL entry is skw_full_batch_aligned for that clip, bit for bit, and a call
+ * in which no clip has a grammar launches exactly what that call launches (no new kernel, no allocation, the same step graphs).  Every clip may bring its own grammar; equal
+ * tables are uploaded once, and the context keeps the last few it saw (keyed by content), so a caller that hands in the same grammar segment after segment uploads it once.
+ * A bad record (skw_grammar_check) fails the call before anything runs, naming the clip.  Not part of the traced / teacher-forced entries.
+ * skw_grammar_compile makes a grammar from a pattern (the regular-expression subset of streamkit_amd/csrc/skw_grammar_compile.h; flags: SKW_GRAMMAR_IGNORE_CASE = 1):
+ * 0 and *out (release with skw_grammar_free), or -1 and the compiler's message in err.  A table made any other way is as good: fill in the struct. */
+int  skw_full_batch_grammar(skw_ctx*, const skw_full_params* params /* [n_clips] */, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                            uint32_t* const* rng_state, int32_t* const* context, const skw_decode_rules* const* rules, const skw_align_params* const* align,
+                            skw_token_times* times, const skw_grammar* const* grammar /* NULL, or [n_clips] with entries that may be NULL */, skw_result* results);
+int  skw_grammar_compile(const char* pattern, size_t len, int flags, float penalty, skw_grammar** out, char* err, size_t errlen);
+void skw_grammar_free(skw_grammar*);
+
 /* ---- decision trace / teacher forcing (parity instrumentation of the hot path; the reference has no counterpart) ----
  * skw_full_batch_traced is skw_full_batch that also returns, per clip, one record for EVERY sampling decision it made, in execution order
  * over all windows and temperature passes (discarded tokens included).  With forced_ids[i] == NULL the run is free (forced_id == chosen_id).
@@ -255,7 +272,7 @@ typedef struct { float mel_ms, encode_ms, decode_ms, total_ms; int32_t n_windows
 void skw_ctx_last_timing(const skw_ctx*, skw_timing* out);
 /* per-kernel-class event timing (adds an event pair around every launch; use for roofline accounting, not for the timed run).
  * classes: 0 k_gemm, 1 k_gemm_smallm, 2 k_attn_encoder, 3 k_layernorm, 4 k_mel, 5 k_dec_self_attn, 6 k_dec_sample, 7 other, 8 k_dec_cross_attn, 9 k_dec_constrain,
- *          10 k_align_qk, 11 k_align_reduce, 12 k_align_dtw (word timestamps) */
+ *          10 k_align_qk, 11 k_align_reduce, 12 k_align_dtw (word timestamps), 13 k_dec_grammar (both of its launches) */
 void skw_ctx_profile(skw_ctx*, int on);
 int  skw_ctx_profile_get(skw_ctx*, int cls, char* name, size_t name_len, long* count, double* ms, double* algorithmic_flops, double* algorithmic_bytes);
 /* In-kernel launch clock of the decode step's dominant kernel (the f16_mfma cross attention).  HIP events cannot sit between the kernels of a captured step graph, and an eager,

@@ -9,6 +9,7 @@
 #include "skw_kernels.h"
 #include "skw_tokenizer.h"
 #include "skw_decode_rules.h"
+#include "skw_grammar_compile.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -488,7 +489,7 @@ struct skw_ctx {
     hipStream_t stream = nullptr; hipEvent_t ev[6] = {};
     hipStream_t cur = nullptr;                       // stream the launch helpers enqueue on (== stream outside the decode groups)
     static const int MAX_GROUPS = 8; hipStream_t gstream[MAX_GROUPS] = {}; hipEvent_t gev[MAX_GROUPS] = {}; int n_groups = 1;
-    struct StepGraph { int g, r0, n, precision, ln_stats, kclk, var_k, kv8; unsigned sw_epoch; SkwLogitParams lp; int rows, cons; hipGraphExec_t exec; };
+    struct StepGraph { int g, r0, n, precision, ln_stats, kclk, var_k, kv8; unsigned sw_epoch; SkwLogitParams lp; int rows, cons, gram; hipGraphExec_t exec; };
     std::vector<StepGraph> step_graphs; int use_graphs = 1;
     char errbuf[512] = {0};
     std::vector<void*> allocs;
@@ -519,6 +520,14 @@ struct skw_ctx {
     // skw_full_batch_mixed: both static masks back to back ([0] without, [1] with the non-speech list; written at the first mixed call) and the rows' own rules, per window
     uint8_t* static_mask_pair = nullptr; int static_mask_pair_built = 0; SkwRowRules* row_rules = nullptr;
     SkwRowConstraints* row_cons = nullptr;           // skw_full_batch_rules: the rows' decoding constraints, per window (read by k_dec_constrain, which only constrained calls launch)
+    // skw_full_batch_grammar (include/skw_grammar.h): the rows' grammar records, per window (read and advanced by k_dec_grammar_state / k_dec_grammar, which only calls with a
+    // grammar launch); the text tokens' bytes on the device (offsets + bytes, built at the first such call: grammar_vocab_ensure); a small content-keyed cache of uploaded
+    // tables, so a node instance's grammar is uploaded once and not per segment (most recently used last; entries of the call in flight are never evicted); and the call's
+    // record per clip (next == nullptr: the clip has none)
+    SkwRowGrammar* row_gram = nullptr; int32_t* gr_voc_off = nullptr; uint8_t* gr_voc_bytes = nullptr;
+    struct GrammarImage { uint64_t hash; int n_states; std::vector<uint16_t> next; std::vector<uint8_t> accept; uint16_t* d_next; uint8_t* d_accept; long stamp; };
+    const int32_t* dbg_active = nullptr;      // skw_debug_sample_rows_grammar: rows the hook marks as finished (only inside that call)
+    std::vector<GrammarImage> gr_cache; long gr_stamp = 0, gr_uploads = 0; std::vector<SkwRowGrammar> gr_clip;
     SkwSeqState* h_st = nullptr; SkwTokenOut* h_toks = nullptr; // pinned
     int* h_row_live = nullptr; int* d_row_live = nullptr;      // per-row live flags in pinned host memory and their device-side address: k_dec_sample clears a row's flag itself,
                                                                // so a step ends with no 4-byte copy kernel (4.2 us in the chain of every step) — the host reads the flags after the stream drains
@@ -665,6 +674,7 @@ extern "C" skw_ctx* skw_ctx_create(skw_model* m, int max_batch, int max_samples,
     want("static_mask_pair", c->static_mask_pair, 2 * skw_static_mask_bytes(hp.n_vocab), true);
     want("row_rules", c->row_rules, B, true);
     want("row_cons", c->row_cons, B, true);
+    want("row_gram", c->row_gram, B, true);
     if (m->quant) {      // ggml q8 arithmetic (quantised files, exact precision): unrounded f32 activations and their q8 blocks
         want("y32", c->y32, enc_rows * d, false);
         want("h32", c->h32, enc_rows * 4 * d, false);
@@ -710,6 +720,8 @@ extern "C" void skw_ctx_free(skw_ctx* c) {
     for (int g = 0; g < skw_ctx::MAX_GROUPS; ++g) { if (c->gstream[g]) { hipStreamSynchronize(c->gstream[g]); hipStreamDestroy(c->gstream[g]); } if (c->gev[g]) hipEventDestroy(c->gev[g]); }
     for (void* p : c->allocs) hipFree(p);
     hipFree(c->stageK); hipFree(c->stageV); hipFree(c->slot_map); hipFree(c->forced_dev); hipFree(c->trace_dev); hipFree(c->kclk);
+    for (auto& gi : c->gr_cache) hipFree(gi.d_next);      // (d_accept is the tail of the same allocation)
+    hipFree(c->gr_voc_off);
     hipFree(c->al_P); hipFree(c->al_acc); hipFree(c->al_x); hipFree(c->al_seqs); hipFree(c->al_times);
     if (c->h_st) hipHostFree(c->h_st); if (c->h_toks) hipHostFree(c->h_toks); if (c->h_row_live) hipHostFree(c->h_row_live);
     for (int i = 0; i < 6; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -779,9 +791,9 @@ static void tap(skw_ctx* c, const char* name, const void* dev, int rows, int col
 
 // ------------------------------------------------------------------ per-kernel-class profiling (HIP events on the engine stream)
 enum ProfClass { PC_GEMM = 0, PC_GEMM_SMALL, PC_ATTN_ENC, PC_LAYERNORM, PC_MEL, PC_DEC_ATTN, PC_DEC_SAMPLE, PC_OTHER, PC_DEC_XATTN, PC_DEC_CONSTRAIN, PC_ALIGN_QK,
-                 PC_ALIGN_REDUCE, PC_ALIGN_DTW, PC_COUNT };
+                 PC_ALIGN_REDUCE, PC_ALIGN_DTW, PC_DEC_GRAMMAR, PC_COUNT };
 static const char* const g_prof_names[PC_COUNT] = {"k_gemm", "k_gemm_smallm", "k_attn_encoder", "k_layernorm", "k_mel", "k_dec_self_attn", "k_dec_sample", "other", "k_dec_cross_attn",
-                                                 "k_dec_constrain", "k_align_qk", "k_align_reduce", "k_align_dtw"};
+                                                 "k_dec_constrain", "k_align_qk", "k_align_reduce", "k_align_dtw", "k_dec_grammar"};
 struct ProfRec { int cls; double flops, bytes; hipEvent_t a, b; };
 struct ProfState { bool on = false; std::vector<ProfRec> recs;
 std::vector<hipEvent_t> pool; size_t next = 0; double ms[PC_COUNT] = {}, flops[PC_COUNT] = {}, bytes[PC_COUNT] = {}; long count[PC_COUNT] = {}; };
@@ -1216,11 +1228,12 @@ static void run_decoder_step(skw_ctx* c, int r0, int Bw, int pos, bool want_logi
 // rows: the per-row form of the sampler (skw_full_batch_mixed) — lp then holds model constants and any_sampled only, so one graph serves every parameter mix of its shape
 // cons: some clip of the call has decoding constraints (skw_full_batch_rules): k_dec_constrain sits between the logits GEMM and the sampler; the rows' records are device memory,
 //  so that graph too serves every mix.  Calls without constraints key cons = 0 and replay the graphs they always did
-static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogitParams& lp, bool rows, bool cons) {
+// gram: some clip of the call has a grammar (skw_full_batch_grammar): k_dec_grammar follows k_dec_constrain; keyed and served from device records the same way
+static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogitParams& lp, bool rows, bool cons, bool gram) {
     for (size_t i = 0; i < c->step_graphs.size(); ++i) {
         auto& sg = c->step_graphs[i];
         if (sg.g == g && sg.r0 == r0 && sg.n == n && sg.precision == c->precision && sg.ln_stats == c->ln_stats_on && sg.kclk == c->kclk_on && sg.sw_epoch == skw_sw_epoch() &&
-            sg.var_k == (int)c->var_k && sg.kv8 == (int)c->kv8_step() && sg.rows == (int)rows && sg.cons == (int)cons && memcmp(&sg.lp, &lp, sizeof lp) == 0) {
+            sg.var_k == (int)c->var_k && sg.kv8 == (int)c->kv8_step() && sg.rows == (int)rows && sg.cons == (int)cons && sg.gram == (int)gram && memcmp(&sg.lp, &lp, sizeof lp) == 0) {
             if (i + 1 != c->step_graphs.size()) { auto hit = sg; c->step_graphs.erase(c->step_graphs.begin() + i); c->step_graphs.push_back(hit); }   // most recently used last
             return c->step_graphs.back().exec;
         }
@@ -1231,6 +1244,7 @@ static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogi
     run_decoder_step(c, r0, n, 0, true, s);
     c->cur_group = 0;
     if (cons) skw_dec_constrain(c->logits + (size_t)r0 * NV, NV, lp.tok_eot, c->row_cons + r0, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, s);
+    if (gram) skw_dec_grammar(c->logits + (size_t)r0 * NV, NV, lp.tok_eot, c->row_gram + r0, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->gr_voc_off, c->gr_voc_bytes, s);
     if (rows) skw_dec_sample_rows(c->logits + (size_t)r0 * NV, c->static_mask_pair, lp, c->row_rules + r0, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->d_row_live + r0,
         c->probs + (size_t)r0 * skw_probs_row_floats(NV), c->rng, c->clip_idx + r0, c->prompt_buf + (size_t)r0 * SKW_PROMPT_CAP, s);
     else skw_dec_sample(c->logits + (size_t)r0 * NV, c->static_mask, lp, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->d_row_live + r0,
@@ -1242,7 +1256,7 @@ static hipGraphExec_t step_graph(skw_ctx* c, int g, int r0, int n, const SkwLogi
         // bounded: a long-lived server with ragged batches would otherwise keep one executable graph per (group, rows, params) forever
         if (c->step_graphs.size() >= 24) { hipGraphExecDestroy(c->step_graphs.front().exec); c->step_graphs.erase(c->step_graphs.begin()); }
         skw_ctx::StepGraph sg; sg.g = g; sg.r0 = r0; sg.n = n; sg.precision = c->precision; sg.ln_stats = c->ln_stats_on; sg.kclk = c->kclk_on; sg.var_k = (int)c->var_k; sg.kv8 = (int)c->kv8_step();
-         sg.sw_epoch = skw_sw_epoch(); sg.lp = lp; sg.rows = (int)rows; sg.cons = (int)cons; sg.exec = exec; c->step_graphs.push_back(sg);
+         sg.sw_epoch = skw_sw_epoch(); sg.lp = lp; sg.rows = (int)rows; sg.cons = (int)cons; sg.gram = (int)gram; sg.exec = exec; c->step_graphs.push_back(sg);
     }
     return exec;
 }
@@ -1377,6 +1391,7 @@ struct FullRequest {
     const skw_align_params* const* align = nullptr; skw_token_times* times = nullptr; bool aligned = false;
     // skw_align_batch: no decoding — text[i][0 .. n_text[i]) is aligned to clip i's first window
     const int32_t* const* text = nullptr; const int32_t* n_text = nullptr;
+    const skw_grammar* const* grammar = nullptr; bool grammared = false;      // skw_full_batch_grammar; grammared: some clip has one (set by validate_request)
     bool wants_align(int ci) const { return align && align[ci] && align[ci]->enabled; }
     bool mixed() const { return pv != nullptr; }
     bool tracing() const { return traces != nullptr; }
@@ -1403,6 +1418,7 @@ struct WindowBatch {
     int R = 0, Bw = 0, enc_rows = 0, prefill_passes = 0;
     std::vector<int> sk, ks, pbuf, np_row, fbuf; std::vector<SkwRowRules> rules;      // per row: seek, key count, prompt (SKW_PROMPT_CAP ids) and its length, forced tokens, request rules
     std::vector<SkwRowConstraints> cons;      // per row: decoding constraints (constrained calls only)
+    std::vector<SkwRowGrammar> gram;          // per row: the grammar record, its walk at the start (calls with a grammar only)
 };
 struct RowGroups { int G = 0; int r0[skw_ctx::MAX_GROUPS], n[skw_ctx::MAX_GROUPS]; bool live[skw_ctx::MAX_GROUPS]; };
 }
@@ -1439,6 +1455,14 @@ static int validate_request(skw_ctx* c, FullRequest& rq) {
         if (!skw_decode_rules_check(rq.rules[i], hp.n_vocab, who, errbuf, 512)) return -3;
         if (!skw_decode_rules_is_default(rq.rules[i])) rq.constrained = true;
     }
+    rq.grammared = false;
+    if (rq.grammar) for (int i = 0; i < rq.n_clips; ++i) {
+        char who[32]; snprintf(who, sizeof who, "clip %d", i);
+        bool checked = false; for (int k = 0; k < i && !checked; ++k) checked = rq.grammar[k] == rq.grammar[i];      // (one record handed in for several clips is read once)
+        if (!checked && !skw_grammar_check(rq.grammar[i], who, errbuf, 512)) return -3;
+        if (rq.grammar[i]) rq.grammared = true;
+    }
+    if (rq.grammared && rq.tracing()) { snprintf(errbuf, 512, "grammars are not part of the traced entries"); return -3; }
     rq.aligned = false;
     if (rq.align) for (int i = 0; i < rq.n_clips; ++i) {
         if (!skw_align_check_params(rq.align[i], hp.n_text_layer, hp.n_text_head, i, errbuf, 512)) return -3;
@@ -1553,6 +1577,10 @@ static int stage_window(skw_ctx* c, const FullRequest& rq, CallState& cs, Window
         w.cons.resize(Bw); for (int j = 0; j < Bw; ++j) w.cons[j] = make_row_constraints(rq.rules[act[j]]);
         HIPCHK(hipMemcpyAsync(c->row_cons, w.cons.data(), sizeof(SkwRowConstraints) * Bw, hipMemcpyHostToDevice, c->stream));
     }
+    if (rq.grammared) {      // the rows' grammars: the walk starts over in every window and every temperature pass
+        w.gram.resize(Bw); for (int j = 0; j < Bw; ++j) w.gram[j] = c->gr_clip[act[j]];
+        HIPCHK(hipMemcpyAsync(c->row_gram, w.gram.data(), sizeof(SkwRowGrammar) * Bw, hipMemcpyHostToDevice, c->stream));
+    }
     cs.lp.any_sampled = 0; for (int j = 0; j < Bw; ++j) if (cs.temps[act[j]][cs.tidx[act[j]]] > 0.0f) cs.lp.any_sampled = 1;      // (part of the step graph's key: greedy passes run the lean sampler)
     if (rq.tracing()) {      // this pass's forced tokens per row: the clip's sequence from its cursor on (-1 = none: the row feeds its own choices)
         w.fbuf.assign((size_t)Bw * c->max_tok, -1);
@@ -1641,6 +1669,9 @@ static void sample_group(skw_ctx* c, const FullRequest& rq, const SkwLogitParams
     c->cur = c->gstream[g];
     if (rq.constrained) { ProfScope p_(c, PC_DEC_CONSTRAIN, 0, 0);
       skw_dec_constrain(c->logits + (size_t)r0 * NV, NV, lp.tok_eot, c->row_cons + r0, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->gstream[g]); }
+    if (rq.grammared) { ProfScope p_(c, PC_DEC_GRAMMAR, 0, 8.0 * n * NV);      // (a pass over the rows to read and one to write; the table's touched rows are noise beside it)
+      skw_dec_grammar(c->logits + (size_t)r0 * NV, NV, lp.tok_eot, c->row_gram + r0, c->st + r0, c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->gr_voc_off, c->gr_voc_bytes,
+                      c->gstream[g]); }
     { ProfScope p_(c, PC_DEC_SAMPLE, 0, 4.0 * n * NV);
       if (rq.mixed()) skw_dec_sample_rows(c->logits + (size_t)r0 * NV, c->static_mask_pair, lp, c->row_rules + r0, c->st + r0,
         c->toks + (size_t)r0 * c->max_tok, c->max_tok, n, c->d_row_live + r0, c->probs + (size_t)r0 * skw_probs_row_floats(NV), c->rng,
@@ -1665,7 +1696,7 @@ static int step_loop(skw_ctx* c, const FullRequest& rq, CallState& cs, const Win
     HIPCHK(hipEventRecord(c->ev[5], c->stream));
     for (int g = 0; g < G; ++g) HIPCHK(hipStreamWaitEvent(c->gstream[g], c->ev[5], 0));
     hipGraphExec_t gexec[skw_ctx::MAX_GROUPS] = {};
-    if (use_graphs && !profiling && !tracing) for (int g = 0; g < G; ++g) gexec[g] = step_graph(c, g, rg.r0[g], rg.n[g], lp, rq.mixed(), rq.constrained);   // nullptr -> eager launches
+    if (use_graphs && !profiling && !tracing) for (int g = 0; g < G; ++g) gexec[g] = step_graph(c, g, rg.r0[g], rg.n[g], lp, rq.mixed(), rq.constrained, rq.grammared);   // nullptr -> eager launches
     // The host learns whether a group still has live rows only by waiting for its stream, and a wait + relaunch per step leaves the
     // GPU idle for the turnaround.  So steps are enqueued `ahead` at a time and the count is read once per block: a step that
     // runs after the last row of its group has finished changes nothing (its attention and sampling kernels return at once for
@@ -1873,12 +1904,67 @@ static int finish_call(skw_ctx* c, const FullRequest& rq, CallState& cs) {
     return 0;
 }
 
+// ---- grammars on the device (skw_full_batch_grammar, the debug hook)
+// the text tokens' bytes, once per context: offsets [tok_eot + 1] and the bytes behind them in one allocation
+static int grammar_vocab_ensure(skw_ctx* c) {
+    if (c->gr_voc_off) return 0;
+    char* errbuf = c->errbuf; const skw_model* m = c->m; const int n = m->tok_eot;
+    std::vector<int32_t> off((size_t)n + 1, 0); std::vector<uint8_t> bytes;
+    for (int t = 0; t < n; ++t) { const std::string& tx = m->tok_str[t]; bytes.insert(bytes.end(), tx.begin(), tx.end()); off[t + 1] = (int32_t)bytes.size(); }
+    const size_t ob = sizeof(int32_t) * off.size(); void* p = nullptr;
+    if (hipMalloc(&p, ob + std::max<size_t>(1, bytes.size())) != hipSuccess || !p) { snprintf(errbuf, 512, "grammar: the vocabulary image could not be allocated"); return -1; }
+    c->gr_voc_off = (int32_t*)p; c->gr_voc_bytes = (uint8_t*)p + ob;
+    HIPCHK(hipMemcpy(c->gr_voc_off, off.data(), ob, hipMemcpyHostToDevice));
+    if (!bytes.empty()) HIPCHK(hipMemcpy(c->gr_voc_bytes, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+    ++c->gr_uploads;
+    return 0;
+}
+// gr_clip[i] = clip i's record (checked already; NULL: none).  Equal tables are one upload — within the call and, through the cache, across calls
+static int grammar_upload(skw_ctx* c, const skw_grammar* const* gv, int n) {
+    char* errbuf = c->errbuf; static const size_t CACHE_MAX = 8;
+    if (grammar_vocab_ensure(c)) return -1;
+    const long call = ++c->gr_stamp;
+    c->gr_clip.assign(n, SkwRowGrammar{nullptr, nullptr, 0.0f, 0, 0, 0u});
+    for (int i = 0; i < n; ++i) {
+        const skw_grammar* g = gv[i]; if (!g) continue;
+        // (the same tables handed in for several clips — one node instance's segments, a caller's shared grammar — are recognised by address before anything is hashed)
+        int same = -1; for (int k = 0; k < i && same < 0; ++k) if (gv[k] && gv[k]->next == g->next && gv[k]->accept == g->accept && gv[k]->n_states == g->n_states) same = k;
+        if (same >= 0) { c->gr_clip[i] = c->gr_clip[same]; c->gr_clip[i].penalty = g->penalty; continue; }
+        const size_t nn = (size_t)g->n_states * 256; uint64_t h = 1469598103934665603ull;      // FNV-1a over the tables
+        for (size_t k = 0; k < nn; ++k) { h = (h ^ g->next[k]) * 1099511628211ull; }
+        for (int k = 0; k < g->n_states; ++k) { h = (h ^ g->accept[k]) * 1099511628211ull; }
+        skw_ctx::GrammarImage* hit = nullptr;
+        for (auto& gi : c->gr_cache) if (gi.hash == h && gi.n_states == g->n_states && memcmp(gi.next.data(), g->next, nn * 2) == 0 && memcmp(gi.accept.data(), g->accept, g->n_states) == 0) {
+            hit = &gi; break; }
+        if (!hit) {
+            // room: the least recently used table that no clip of this call holds goes first
+            while (c->gr_cache.size() >= CACHE_MAX) {
+                size_t old = c->gr_cache.size();
+                for (size_t k = 0; k < c->gr_cache.size(); ++k) if (c->gr_cache[k].stamp != call && (old == c->gr_cache.size() || c->gr_cache[k].stamp < c->gr_cache[old].stamp)) old = k;
+                if (old == c->gr_cache.size()) break;      // (every cached table is in use by this call: the cache grows for its duration)
+                HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->gr_cache[old].d_next); c->gr_cache.erase(c->gr_cache.begin() + old);
+            }
+            void* p = nullptr;
+            if (hipMalloc(&p, nn * 2 + g->n_states) != hipSuccess || !p) { snprintf(errbuf, 512, "clip %d: grammar: the table could not be allocated on the device", i); return -1; }
+            skw_ctx::GrammarImage gi; gi.hash = h; gi.n_states = g->n_states; gi.next.assign(g->next, g->next + nn); gi.accept.assign(g->accept, g->accept + g->n_states);
+            gi.d_next = (uint16_t*)p; gi.d_accept = (uint8_t*)p + nn * 2; gi.stamp = call;
+            if (hipMemcpy(gi.d_next, g->next, nn * 2, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(gi.d_accept, g->accept, g->n_states, hipMemcpyHostToDevice) != hipSuccess) {
+                hipFree(p); snprintf(errbuf, 512, "clip %d: grammar: the table could not be copied to the device", i); return -1; }
+            ++c->gr_uploads; c->gr_cache.push_back(std::move(gi)); hit = &c->gr_cache.back();
+        }
+        hit->stamp = call;
+        c->gr_clip[i] = SkwRowGrammar{hit->d_next, hit->d_accept, g->penalty, g->n_states, 0, 0u};
+    }
+    return 0;
+}
+
 static int full_batch_impl(skw_ctx* c, FullRequest rq) {
     char* errbuf = c->errbuf; errbuf[0] = 0;
     WS_READY(c);
     if (int rc = validate_request(c, rq)) return rc;
     HIPCHK(hipSetDevice(c->m->device));
     if (rq.tracing() && ensure_trace_buffers(c)) return -1;
+    if (rq.grammared) if (int rc = grammar_upload(c, rq.grammar, rq.n_clips)) return rc;
     CallState cs(rq.n_clips); c->al_tap_next = 0;
     if (int rc = load_call(c, rq, cs)) return rc;
     if (int rc = detect_languages(c, rq, cs)) return rc;
@@ -1957,6 +2043,21 @@ extern "C" int skw_full_batch_aligned(skw_ctx* c, const skw_full_params* params,
         rq.align = align; rq.times = times;
         return full_batch_impl(c, rq); });
 }
+extern "C" int skw_full_batch_grammar(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
+                                      uint32_t* const* rng_state, int32_t* const* context, const skw_decode_rules* const* rules, const skw_align_params* const* align,
+                                      skw_token_times* times, const skw_grammar* const* grammar, skw_result* results) {
+    return guarded(c, "skw_full_batch_grammar", [&] {
+        if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_grammar: params is NULL (one skw_full_params per clip)"); return -1; }
+        if (times) for (int i = 0; i < n_clips; ++i) { times[i].n = 0; times[i].t0 = times[i].t1 = nullptr; }
+        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state; rq.context = context; rq.rules = rules;
+        rq.align = align; rq.times = times; rq.grammar = grammar;
+        return full_batch_impl(c, rq); });
+}
+extern "C" int skw_grammar_compile(const char* pattern, size_t len, int flags, float penalty, skw_grammar** out, char* err, size_t errlen) {
+    return skw_grammar_compile_impl(pattern, len, flags, penalty, out, err, errlen);
+}
+extern "C" void skw_grammar_free(skw_grammar* g) { skw_grammar_free_impl(g); }
+extern "C" long skw_debug_grammar_uploads(const skw_ctx* c) { return c->gr_uploads; }      // tests: device allocations made for grammars so far (the vocabulary image, then one per cache miss)
 extern "C" int skw_align_batch(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                const int32_t* const* text_tokens, const int32_t* n_text, const skw_align_params* const* align, skw_token_times* times) {
     return guarded(c, "skw_align_batch", [&] {
@@ -2007,7 +2108,7 @@ struct skw_sample_rows_ex { const float* temperature; uint32_t* rng_state; int32
                             int32_t* n_tokens; int32_t* cur_token; int32_t* active; };
 static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const skw_full_params* pv, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
                                   const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out,
-                                  const skw_decode_rules* const* rv = nullptr, skw_sample_rows_ex* ex = nullptr) {
+                                  const skw_decode_rules* const* rv = nullptr, skw_sample_rows_ex* ex = nullptr, const skw_grammar* const* gv = nullptr) {
     char* errbuf = c->errbuf; errbuf[0] = 0;
     WS_READY(c);
     if (n_rows < 1 || n_rows > c->max_batch) { snprintf(errbuf, 512, "n_rows %d outside [1, %d]", n_rows, c->max_batch); return -1; }
@@ -2026,6 +2127,11 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
         for (int r = 0; r < n_rows; ++r) { char who[32]; snprintf(who, sizeof who, "row %d", r); if (!skw_decode_rules_check(rv[r], NV, who, errbuf, 512)) return -3; }
         cons.resize(n_rows); for (int r = 0; r < n_rows; ++r) cons[r] = make_row_constraints(rv[r]);
         HIPCHK(hipMemcpyAsync(c->row_cons, cons.data(), sizeof(SkwRowConstraints) * n_rows, hipMemcpyHostToDevice, c->stream));
+    }
+    if (gv) {
+        for (int r = 0; r < n_rows; ++r) { char who[32]; snprintf(who, sizeof who, "row %d", r); if (!skw_grammar_check(gv[r], who, errbuf, 512)) return -3; }
+        if (int rc = grammar_upload(c, gv, n_rows)) return rc;
+        HIPCHK(hipMemcpyAsync(c->row_gram, c->gr_clip.data(), sizeof(SkwRowGrammar) * n_rows, hipMemcpyHostToDevice, c->stream));
     }
     if (pv) {
         build_static_mask_pair(c); lp = mixed_logit_params(m);
@@ -2051,6 +2157,7 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
                 snprintf(errbuf, 512, "row %d: the token loop cannot produce this history (timestamp goes backwards at %d)", r, i); return -1; }
         }
         s.seek_end = SKW_WINDOW_FRAMES;
+        if (c->dbg_active && !c->dbg_active[r]) s.active = 0;
         c->h_row_live[r] = 1;
     }
     HIPCHK(hipMemcpyAsync(c->st, c->h_st, sizeof(SkwSeqState) * n_rows, hipMemcpyHostToDevice, c->stream));
@@ -2061,6 +2168,7 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
     if (ex && ex->rng_state) HIPCHK(hipMemcpyAsync(c->rng, ex->rng_state, sizeof(uint32_t) * SKW_RNG_WORDS * n_rows, hipMemcpyHostToDevice, c->stream));
     const int* forced_dev = with_trace ? c->forced_dev : nullptr; SkwTraceStep* trace_dev = with_trace ? c->trace_dev : nullptr;
     if (rv) skw_dec_constrain(c->logits, NV, lp.tok_eot, c->row_cons, c->st, c->toks, MT, n_rows, c->stream);
+    if (gv) skw_dec_grammar(c->logits, NV, lp.tok_eot, c->row_gram, c->st, c->toks, MT, n_rows, c->gr_voc_off, c->gr_voc_bytes, c->stream);
     skw_debug_force_stream_sampler(form == 1);
     if (ex) ex->kernel_id = skw_dec_sample_kernel(lp, trace_dev != nullptr, pv != nullptr);
     if (pv) skw_dec_sample_rows(c->logits, c->static_mask_pair, lp, c->row_rules, c->st, c->toks, MT, n_rows, c->d_row_live, c->probs, c->rng, c->clip_idx, c->prompt_buf, c->stream,
@@ -2107,6 +2215,17 @@ extern "C" int skw_debug_sample_rows_rules(skw_ctx* c, const skw_full_params* pa
                                            const skw_decode_rules* const* rules /* [n_rows], entries may be NULL */) {
     if (!params || !rules) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_rules: params and rules are one per row (rules entries may be NULL)"); return -1; }
     return debug_sample_rows_impl(c, params, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out, rules);
+}
+// constrain -> grammar -> sampler, as in the decode step: rules as above (NULL: no row has a record), grammar one skw_grammar (or NULL) per row.  active [n_rows] (or NULL):
+// 0 marks a row as finished before the launch — every kernel leaves it alone
+extern "C" int skw_debug_sample_rows_grammar(skw_ctx* c, const skw_full_params* params /* [n_rows] */, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
+                                             const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out,
+                                             const skw_decode_rules* const* rules, const skw_grammar* const* grammar, const int32_t* active) {
+    if (!params || !grammar) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_grammar: params and grammar are one per row (grammar entries may be NULL)"); return -1; }
+    return guarded(c, "skw_debug_sample_rows_grammar", [&] {
+        c->dbg_active = active;
+        const int rc = debug_sample_rows_impl(c, params, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out, rules, nullptr, grammar);
+        c->dbg_active = nullptr; return rc; });
 }
 // per_row: p is one skw_full_params per row (the per-row form of the sampler, as skw_debug_sample_rows_mixed), else one block for the launch
 extern "C" int skw_debug_sample_rows_ex(skw_ctx* c, const skw_full_params* p, int per_row, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,

@@ -253,6 +253,13 @@ void skw_dec_constrain(float* logits, int n_vocab, int tok_eot, const SkwRowCons
 // the kernel a sampler launch runs, as bits: k_dec_sample<TRACE, DRAW, ROWS>, or k_dec_sample_stream<ROWS> with SKW_SMPK_STREAM set (trace: a trace buffer is handed in)
 enum { SKW_SMPK_ROWS = 1, SKW_SMPK_DRAW = 2, SKW_SMPK_TRACE = 4, SKW_SMPK_STREAM = 8 };
 int skw_dec_sample_kernel(const SkwLogitParams& p, bool trace, bool rows);
+// The grammar of one row (skw_full_batch_grammar, include/skw_grammar.h) in device memory, written by the host per window and temperature pass: the tables' device addresses
+// (next == nullptr: the row has no grammar), the penalty, and the walk CARRIED across the pass's steps — state = the DFA state after the first n_seen sampled tokens of the
+// pass (the host writes 0, 0).  k_dec_grammar_state advances it by the tokens that arrived since; k_dec_grammar then masks the row from it (skw_kernels_grammar.hip).
+struct SkwRowGrammar { const uint16_t* next; const uint8_t* accept; float penalty; int32_t n_states, n_seen; uint32_t state; };
+// voc_off [tok_eot + 1] / voc_bytes: the text tokens' bytes, skw_grammar_vocab on the device.  Between k_dec_constrain (when present) and the sampler.
+void skw_dec_grammar(float* logits, int n_vocab, int tok_eot, SkwRowGrammar* gr, const SkwSeqState* st, const SkwTokenOut* toks, int max_tok, int B,
+                     const int32_t* voc_off, const uint8_t* voc_bytes, hipStream_t s);
 void skw_debug_force_stream_sampler(int on);   // tests: the streaming sampler (filters the logits row in place) even where the register-resident form applies
 void skw_rng_seed(uint32_t* rng, int n_clips, uint32_t seed, hipStream_t s);   // std::mt19937(seed) for every clip
 

@@ -6,7 +6,8 @@
 //
 // Params beyond the reference's are ADDITIVE (unknown keys are ignored by the reference's serde config, lib.rs:66-104):
 // vad_mode, batch_window_ms, max_batch, mixed_batch, flush_tail, precision, gpu_device: "auto", initial_prompt, carry_context, repetition_penalty,
-// no_repeat_ngram_size, suppress_tokens, logit_bias (decoding constraints per instance, skw_full_batch_rules), and input_sample_rate / input_resample_mode (the
+// no_repeat_ngram_size, suppress_tokens, logit_bias (decoding constraints per instance, skw_full_batch_rules), grammar / grammar_choices / grammar_ignore_case /
+// grammar_penalty (a pattern the transcript has to match, skw_full_batch_grammar), and input_sample_rate / input_resample_mode (the
 // audio::resampler node's arithmetic run inside this plugin, skw_resampler_core.h: a 48 kHz Opus source then needs no node in between).
 // One BEHAVIOURAL difference remains and is not additive: with the default vad_mode "auto" the Silero model at `vad_model_path`
 // gates what Whisper sees exactly as in the reference (skw_silero.h) only when that file exists; when it does not, the
@@ -25,6 +26,7 @@
 #include <sys/stat.h>
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <chrono>
 #include <condition_variable>
 #include <cmath>
@@ -94,6 +96,9 @@ struct WhisperConfig {
     // (additive) timestamp_granularity: "segment" (the reference's output, byte for byte) | "word" (one segment per word: skw_words.h on the token times of skw_full_batch_aligned).
     // alignment_heads: "top:N" (every head of the top N decoder layers; N = 0: half of them, the default) or explicit [layer, head] pairs in align.head_mask
     bool word_timestamps = false; int align_top = 0; bool align_explicit = false; skw_align_params align;
+    // (additive) grammar | grammar_choices, grammar_ignore_case, grammar_penalty: the pattern this instance's transcripts have to match (include/skw_grammar.h: a regular
+    // expression compiled to a byte DFA — the regular subset of whisper.cpp's grammar_rules), compiled when the parameters are parsed; null: none
+    std::shared_ptr<skw_grammar> grammar;
     WhisperConfig() { skw_decode_rules_set_default(&rules); memset(&align, 0, sizeof align); align.median_width = 7; }
 };
 
@@ -138,6 +143,44 @@ bool parse_decode_rules(const skw::JsonValue& v, WhisperConfig* cfg, std::string
             cfg->max_bias_id = std::max(cfg->max_bias_id, (int)e.arr[0].num);
         }
     }
+    return true;
+}
+// grammar (a pattern) | grammar_choices (strings: " ?(c1|c2|...)[.!?]?" with each choice escaped), grammar_ignore_case, grammar_penalty -> cfg->grammar.  The default penalty
+// is 100, whisper.cpp's grammar_penalty default as recalled (it could not be checked against its source here).
+bool parse_grammar(const skw::JsonValue& v, WhisperConfig* cfg, std::string* err) {
+    auto bad = [&](const std::string& m) { *err = "Invalid config: " + m; return false; };
+    const skw::JsonValue* gp = v.get("grammar"); const skw::JsonValue* gc = v.get("grammar_choices");
+    bool icase = false; float penalty = 100.0f;
+    if (const skw::JsonValue* x = v.get("grammar_ignore_case")) { if (x->type != skw::JsonValue::Bool) return bad("grammar_ignore_case must be a boolean"); icase = x->b; }
+    if (const skw::JsonValue* x = v.get("grammar_penalty")) {
+        if (x->type != skw::JsonValue::Number || !std::isfinite((float)x->num) || !((float)x->num > 0.0f)) return bad("grammar_penalty must be a finite number > 0");
+        penalty = (float)x->num;
+    }
+    cfg->grammar.reset();
+    if (gp && gc) return bad("grammar and grammar_choices cannot both be given");
+    std::string pattern;
+    if (gp) {
+        if (gp->type != skw::JsonValue::String) return bad("grammar must be a string (a pattern)");
+        if (gp->str.empty()) return true;      // (the default: no grammar)
+        pattern = gp->str;
+    } else if (gc) {
+        if (gc->type != skw::JsonValue::Array) return bad("grammar_choices must be an array of strings");
+        if (gc->arr.empty()) return true;
+        pattern = " ?(";
+        for (size_t k = 0; k < gc->arr.size(); ++k) {
+            const skw::JsonValue& e = gc->arr[k];
+            if (e.type != skw::JsonValue::String || e.str.empty()) return bad("grammar_choices must be an array of non-empty strings");
+            if (k) pattern += "|";
+            for (unsigned char ch : e.str) {      // every ASCII character that is not a letter or a digit is escaped: the choice is matched literally
+                if (ch < 0x80 && !std::isalnum(ch)) pattern += '\\';
+                pattern += (char)ch;
+            }
+        }
+        pattern += ")[.!?]?";
+    } else return true;
+    skw_grammar* g = nullptr; char e[256] = {0};
+    if (skw_grammar_compile(pattern.data(), pattern.size(), icase ? 1 : 0, penalty, &g, e, sizeof e) != 0) return bad(std::string(gp ? "grammar: " : "grammar_choices: ") + e);
+    cfg->grammar = std::shared_ptr<skw_grammar>(g, skw_grammar_free);
     return true;
 }
 // the ids against the loaded model's vocabulary (create_instance and update_params, once the engine is known)
@@ -231,6 +274,7 @@ bool parse_config(const char* json, WhisperConfig* cfg, std::string* err) {
             cfg->align_explicit = true;
         } else { *err = msg; return false; }
     }
+    if (!parse_grammar(v, cfg, err)) return false;
     return parse_decode_rules(v, cfg, err);
 }
 
@@ -270,6 +314,7 @@ struct Job {
     const skw_decode_rules* decode_rules() const { return constrained ? &rules : nullptr; }
     skw_align_params align; bool want_align = false; skw_token_times times{0, nullptr, nullptr};      // timestamp_granularity "word": the instance's alignment record, the token times
     const skw_align_params* align_params() const { return want_align ? &align : nullptr; }
+    std::shared_ptr<skw_grammar> grammar;      // the owning instance's grammar when the segment was queued (null: none); shared, so update_params cannot free it under a batch
     void set_samples(const std::vector<float>& v) {
         n = v.size(); pinned = PinnedPool::get().acquire(n);
         if (pinned.p) memcpy(pinned.p, v.data(), n * sizeof(float)); else pcm_pageable = v;      // (no page-locked memory to be had: the ordinary copy path)
@@ -279,6 +324,7 @@ struct Job {
 };
 std::atomic<long> g_engine_calls{0}, g_batch_jobs{0}, g_mixed_calls{0};      // skw_whisper_plugin_batch_stats
 std::atomic<long> g_align_calls{0};      // engine calls that aligned at least one job (skw_full_batch_aligned)
+std::atomic<long> g_grammar_calls{0};    // engine calls in which at least one job had a grammar (skw_full_batch_grammar)
 std::atomic<long> g_context_calls{0}, g_rules_calls{0};                                        // skw_whisper_plugin_context_stats: engine calls that carried at least one context
 struct SharedEngine {
     skw_model* model = nullptr;
@@ -360,7 +406,8 @@ struct SharedEngine {
                 while (!queue.empty() && (int)batch.size() < batch_limit) {
                     // arrival order, whatever the jobs' params: every row of skw_full_batch_mixed decodes under its own.  mixed_batch: false cuts at the first job that differs
                     if (!mixed && !batch.empty() && (memcmp(&batch[0]->params, &queue.front()->params, sizeof(skw_full_params)) != 0 ||
-                                                     memcmp(&batch[0]->rules, &queue.front()->rules, sizeof(skw_decode_rules)) != 0)) break;      // (and where the rules differ)
+                                                     memcmp(&batch[0]->rules, &queue.front()->rules, sizeof(skw_decode_rules)) != 0 ||
+                                                     batch[0]->grammar.get() != queue.front()->grammar.get())) break;      // (and where the rules or the grammar differ)
                     batch.push_back(queue.front()); queue.pop_front();
                 }
             }
@@ -386,7 +433,12 @@ struct SharedEngine {
                     // word timestamps: a batch in which some job asks is ONE aligned call (jobs that do not ask hand in NULL: their rows are the rules call's); otherwise as before
                     std::vector<const skw_align_params*> als(n); std::vector<skw_token_times> tms(n, skw_token_times{0, nullptr, nullptr}); bool any_align = false;
                     for (int i = 0; i < n; ++i) { als[i] = batch[i]->align_params(); any_align = any_align || als[i] != nullptr; }
-                    rc = any_align ? skw_full_batch_aligned(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), any_ctx ? cxs.data() : nullptr, any_rules ? rls.data() : nullptr,
+                    // grammars: a batch in which some job has one is ONE grammar call (jobs without hand in NULL: their rows are the aligned call's); otherwise as before
+                    std::vector<const skw_grammar*> grs(n); bool any_gram = false;
+                    for (int i = 0; i < n; ++i) { grs[i] = batch[i]->grammar.get(); any_gram = any_gram || grs[i] != nullptr; }
+                    rc = any_gram ? skw_full_batch_grammar(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), any_ctx ? cxs.data() : nullptr, any_rules ? rls.data() : nullptr,
+                                                           any_align ? als.data() : nullptr, any_align ? tms.data() : nullptr, grs.data(), res.data())
+                       : any_align ? skw_full_batch_aligned(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), any_ctx ? cxs.data() : nullptr, any_rules ? rls.data() : nullptr,
                                                             als.data(), tms.data(), res.data())
                        : any_rules ? skw_full_batch_rules(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), any_ctx ? cxs.data() : nullptr, rls.data(), res.data())
                        : any_ctx ? skw_full_batch_context(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), cxs.data(), res.data())
@@ -395,6 +447,7 @@ struct SharedEngine {
                     g_engine_calls.fetch_add(1); g_batch_jobs.fetch_add(n); if (differ) g_mixed_calls.fetch_add(1); if (any_ctx) g_context_calls.fetch_add(1);
                     if (any_rules) g_rules_calls.fetch_add(1);
                     if (any_align) g_align_calls.fetch_add(1);
+                    if (any_gram) g_grammar_calls.fetch_add(1);
                     if (rc == 0) for (int i = 0; i < n; ++i) { batch[i]->result = res[i]; batch[i]->times = tms[i]; } else why = skw_ctx_last_error(ctx);
                     if (rc != 0 && (differ || rules_differ || (any_align && n > 1))) {
                         // A refusal must stay with the request that earned it: jobs of differently configured instances share this call, and one of them being refused
@@ -405,7 +458,9 @@ struct SharedEngine {
                             int32_t* cx = cxs[i];      // (the refused call wrote no context back: each job's own, as it was queued)
                             const skw_decode_rules* rl = rls[i];
                             const skw_align_params* al = als[i]; skw_token_times tm{0, nullptr, nullptr};
-                            int r1 = al ? skw_full_batch_aligned(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, cx ? &cx : nullptr, rl ? &rl : nullptr, &al, &tm, &one)
+                            const skw_grammar* gr = grs[i];      // (a job's grammar goes with it into its own call)
+                            int r1 = gr ? skw_full_batch_grammar(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, cx ? &cx : nullptr, rl ? &rl : nullptr, al ? &al : nullptr, al ? &tm : nullptr, &gr, &one)
+                                   : al ? skw_full_batch_aligned(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, cx ? &cx : nullptr, rl ? &rl : nullptr, &al, &tm, &one)
                                    : rl ? skw_full_batch_rules(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, cx ? &cx : nullptr, &rl, &one)
                                    : cx ? skw_full_batch_context(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &cx, &one) : skw_full_batch_rng(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &one);
                             g_engine_calls.fetch_add(1);
@@ -683,6 +738,7 @@ bool transcribe_and_emit(WhisperPlugin* self, const Emit& em, const skw::Segment
     job->params.audio_ctx = self->config.audio_ctx_auto ? skw_audio_ctx_for_samples((int)job->n, self->engine->n_audio_ctx) : self->config.audio_ctx;
     job->rng = self->rng;
     job->rules = self->config.rules; job->constrained = !skw_decode_rules_is_default(&job->rules);      // (additive) what the instance is configured for now, like audio_ctx
+    job->grammar = self->config.grammar;      // (additive) the instance's grammar as it is configured now: update_params takes effect from the next segment
     if (self->config.word_timestamps) {      // (additive) the instance's alignment record as it is configured now; "top:N" is resolved against the loaded model
         job->align = self->config.align; job->align.enabled = 1; job->want_align = true;
         if (!self->config.align_explicit) { const int L = self->engine->n_text_layer;
@@ -788,6 +844,10 @@ const char* const kSchema =
     "\"no_repeat_ngram_size\":{\"type\":\"integer\",\"description\":\"(additive) no n-gram of this many text tokens occurs twice within a window (timestamps in between are skipped); 0 = off\",\"default\":0,\"minimum\":0},"
     "\"suppress_tokens\":{\"type\":\"array\",\"items\":{\"type\":\"integer\",\"minimum\":0},\"description\":\"(additive) token ids that are never produced (the id-level form of whisper.cpp's suppress_regex); with logit_bias at most 256 distinct ids, each below the model's vocabulary size\",\"default\":[]},"
     "\"logit_bias\":{\"type\":\"array\",\"items\":{\"type\":\"array\",\"minItems\":2,\"maxItems\":2},\"description\":\"(additive) [token id, bias] pairs: the bias is added to the token's logit at every sampling decision; an id also under suppress_tokens stays suppressed. Segments with different decoding rules share a batch\",\"default\":[]},"
+    "\"grammar\":{\"type\":\"string\",\"description\":\"(additive) a pattern every segment's text has to match in full (whisper.cpp's grammar_rules, restricted to REGULAR languages: a regular expression over bytes — literals, escapes, \\\\d \\\\w \\\\s, ., [...], groups, |, ? * + {m,n}). Tokens that cannot continue a match lose grammar_penalty logits, the end of the text loses it while the match is incomplete. The match restarts in every 30 s window and ignores timestamps: meant for short utterances. Not with grammar_choices. Segments with and without grammars share a batch\",\"default\":\"\"},"
+    "\"grammar_choices\":{\"type\":\"array\",\"items\":{\"type\":\"string\"},\"description\":\"(additive) the grammar as a list of allowed utterances (commands, names, yes / no): compiled as ' ?(c1|c2|...)[.!?]?' with each choice matched literally\",\"default\":[]},"
+    "\"grammar_ignore_case\":{\"type\":\"boolean\",\"description\":\"(additive) ASCII letters of the grammar match either case\",\"default\":false},"
+    "\"grammar_penalty\":{\"type\":\"number\",\"description\":\"(additive) whisper.cpp's grammar_penalty: what a token that does not fit the grammar loses; finite on purpose (a token the grammar dislikes can still win when nothing that fits is left)\",\"default\":100.0,\"exclusiveMinimum\":0.0},"
     "\"flush_tail\":{\"type\":\"boolean\",\"description\":\"(additive) transcribe buffered speech when the input stream ends (the reference drops it)\",\"default\":false},"
     "\"input_sample_rate\":{\"type\":\"integer\",\"description\":\"(additive) sample rate of the mono f32 packets fed to this node; anything but 16000 is resampled to 16 kHz on the GPU with the audio::resampler node's arithmetic (chunk_frames 960) before VAD segmentation\",\"default\":16000,\"minimum\":1000,\"maximum\":768000},"
     "\"input_resample_mode\":{\"type\":\"string\",\"description\":\"(additive) linear (rubato FastFixedIn/Linear, bit for bit what audio::resampler gives) | polyphase (Kaiser-windowed sinc)\",\"default\":\"linear\"}"
@@ -948,6 +1008,8 @@ extern "C" void skw_whisper_plugin_batch_stats(long* engine_calls, long* jobs, l
 extern "C" void skw_whisper_plugin_context_stats(long* context_calls) { if (context_calls) *context_calls = g_context_calls.load(); }
 // additive, for tests: engine calls that carried at least one job with decoding constraints (skw_full_batch_rules); a process whose instances set none of the four keys stays at 0
 extern "C" void skw_whisper_plugin_rules_stats(long* rules_calls) { if (rules_calls) *rules_calls = g_rules_calls.load(); }
+// additive, for tests: engine calls in which at least one job had a grammar (skw_full_batch_grammar); a process whose instances set neither grammar key stays at 0
+extern "C" long skw_whisper_plugin_grammar_calls(void) { return g_grammar_calls.load(); }
 // additive, for tests: engine calls that aligned at least one job (skw_full_batch_aligned); a process whose instances all keep timestamp_granularity "segment" stays at 0
 extern "C" void skw_whisper_plugin_align_stats(long* align_calls) { if (align_calls) *align_calls = g_align_calls.load(); }
 // additive, for tests: the node's own parsing of repetition_penalty / no_repeat_ngram_size / suppress_tokens / logit_bias out of a parameter object, and the check of the ids against

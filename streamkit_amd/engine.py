@@ -92,6 +92,75 @@ def rules_array(rules, n, n_vocab, who):
     return list(rules), (C.c_void_p * n)(*[None if r is None else C.addressof(r) for r in rules])
 
 
+GRAMMAR_MAX_STATES = 4096      # SKW_GRAMMAR_MAX_STATES
+GRAMMAR_DEAD = 0xFFFF          # SKW_GRAMMAR_DEAD
+GRAMMAR_IGNORE_CASE = 1        # SKW_GRAMMAR_IGNORE_CASE
+
+
+class GrammarRec(C.Structure):      # skw_grammar (include/skw_grammar.h)
+    _fields_ = [("n_states", C.c_int32), ("next", C.c_void_p), ("accept", C.c_void_p), ("penalty", C.c_float)]
+
+
+class Grammar:
+    """A grammar for grammar-constrained decoding (include/skw_grammar.h): a dense byte-level DFA — next uint16 [n_states][256] (GRAMMAR_DEAD: no match can continue), accept
+    uint8 [n_states], state 0 the start — and the finite penalty > 0 that tokens which cannot continue a match lose.  Regular languages only (whisper.cpp's GBNF is a pushdown
+    grammar; this is its regular subset).  Grammar.compile(pattern) builds the tables from a regular expression (full match over bytes; the subset of
+    streamkit_amd/csrc/skw_grammar_compile.h); Grammar.from_tables(next, accept, penalty) takes them as they are — the engine checks them when they are used."""
+
+    def __init__(self, nxt, accept, penalty):
+        self.next = np.ascontiguousarray(nxt, dtype=np.uint16).reshape(-1, 256)
+        self.accept = np.ascontiguousarray(accept, dtype=np.uint8).reshape(-1)
+        self.penalty = float(penalty)
+        self.rec = GrammarRec(self.accept.size, self.next.ctypes.data, self.accept.ctypes.data, self.penalty)
+
+    @classmethod
+    def from_tables(cls, nxt, accept, penalty=100.0):
+        return cls(nxt, accept, penalty)
+
+    @classmethod
+    def compile(cls, pattern, ignore_case=False, penalty=100.0):
+        """pattern: str (taken as its UTF-8 bytes) or bytes.  Raises ValueError with the compiler's message."""
+        pat = pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern)
+        out = C.c_void_p(); err = C.create_string_buffer(256)
+        if lib().skw_grammar_compile(pat, len(pat), GRAMMAR_IGNORE_CASE if ignore_case else 0, float(penalty), C.byref(out), err, 256) != 0:
+            raise ValueError(err.value.decode(errors="replace"))
+        try:
+            rec = GrammarRec.from_address(out.value)
+            n = rec.n_states
+            nxt = np.frombuffer((C.c_uint16 * (n * 256)).from_address(rec.next), dtype=np.uint16).copy()
+            acc = np.frombuffer((C.c_uint8 * n).from_address(rec.accept), dtype=np.uint8).copy()
+        finally:
+            lib().skw_grammar_free(out)
+        return cls(nxt, acc, penalty)
+
+    @property
+    def n_states(self):
+        return int(self.accept.size)
+
+    def walk(self, data, state=0):
+        """the state after `data` from `state`, or GRAMMAR_DEAD"""
+        s = int(state)
+        for b in bytes(data):
+            if s == GRAMMAR_DEAD:
+                break
+            s = int(self.next[s, b])
+        return s
+
+    def matches(self, data):
+        s = self.walk(data)
+        return s != GRAMMAR_DEAD and bool(self.accept[s])
+
+
+def grammars_array(grammars, n, who):
+    """[Grammar | None] * n -> (c_void_p * n) of the records' addresses, NULL where None (the Grammar objects keep the tables alive: hold on to the list)"""
+    if len(grammars) != n:
+        raise ValueError("%d grammars for %d %ss" % (len(grammars), n, who))
+    for i, g in enumerate(grammars):
+        if g is not None and not isinstance(g, Grammar):
+            raise ValueError("%s %d: grammars must be Grammar or None" % (who, i))
+    return (C.c_void_p * n)(*[None if g is None else C.addressof(g.rec) for g in grammars])
+
+
 class Segment(C.Structure):
     _fields_ = [("t0", C.c_int64), ("t1", C.c_int64), ("tok_begin", C.c_int32), ("tok_end", C.c_int32),
                 ("text_off", C.c_int32), ("text_len", C.c_int32)]
@@ -239,6 +308,13 @@ def lib():
         L.skw_align_batch.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_void_p), C.POINTER(TokenTimes)]
         L.skw_token_times_free.argtypes = [C.POINTER(TokenTimes)]
+        L.skw_full_batch_grammar.argtypes = [C.c_void_p, C.POINTER(FullParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(TokenTimes), C.POINTER(C.c_void_p), C.POINTER(Result)]
+        L.skw_grammar_compile.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_float, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+        L.skw_grammar_free.argtypes = [C.c_void_p]
+        L.skw_debug_grammar_uploads.restype = C.c_long; L.skw_debug_grammar_uploads.argtypes = [C.c_void_p]
+        L.skw_debug_sample_rows_grammar.argtypes = [C.c_void_p, C.POINTER(FullParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -421,7 +497,8 @@ class Context:
         lib().skw_full_default_params(C.byref(p))
         return p
 
-    def full_batch(self, clips, params=None, device_ptrs=None, n_samples=None, trace=False, forced=None, rng_states=None, contexts=None, rules=None, align=None):
+    def full_batch(self, clips, params=None, device_ptrs=None, n_samples=None, trace=False, forced=None, rng_states=None, contexts=None, rules=None, align=None,
+                   grammars=None):
         """clips: list of 1-D float32 numpy arrays (host), or device_ptrs + n_samples for HBM-resident PCM.
         trace=True (or forced=[per-clip int32 id sequences]): skw_full_batch_traced — returns (results, traces), traces[i] a structured
         array (TRACE_DT) with one record per sampling decision of clip i; with `forced` the decoder is fed those ids (teacher forcing).
@@ -437,8 +514,12 @@ class Context:
         here as the engine checks them (ValueError naming the clip).
         align=[AlignParams or None per clip] (align_params()): skw_full_batch_aligned — the clips that ask get word timestamps: each result gains "token_times", one (t0, t1) in
         centiseconds per token of "tokens", (-1, -1) for timestamp tokens and for clips that did not ask.  May be combined with per-clip params, rng_states, contexts and rules; not
-        with trace / forced."""
+        with trace / forced.
+        grammars=[Grammar or None per clip]: skw_full_batch_grammar — the clips that bring one are decoded under it (tokens whose text cannot continue a match lose the
+        grammar's penalty, <|endoftext|> loses it while the match is incomplete); None leaves the clip as it is without.  May be combined with everything align may."""
         per_clip = isinstance(params, (list, tuple))
+        if grammars is not None and (trace or forced is not None):
+            raise ValueError("full_batch: grammars cannot be combined with trace / forced (grammars are not part of the traced entries)")
         if align is not None and (trace or forced is not None):
             raise ValueError("full_batch: align cannot be combined with trace / forced")
         if rules is not None:
@@ -473,7 +554,21 @@ class Context:
             assert all(x is None or (x.dtype == np.int32 and x.size == CONTEXT_WORDS and x.flags["C_CONTIGUOUS"]) for x in contexts)
             cp = (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in contexts])
         times = None
-        if align is not None:
+        if grammars is not None:
+            gp = grammars_array(grammars, n, "clip")
+            if align is not None and len(align) != n:
+                raise ValueError("full_batch: %d alignment records for %d clips" % (len(align), n))
+            sp = None
+            if rng_states is not None:
+                assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
+                sp = (C.c_void_p * n)(*[None if s is None else s.ctypes.data for s in rng_states])
+            pp = p if per_clip else (FullParams * n)(*([p] * n))
+            ap = None
+            if align is not None:
+                ap = (C.c_void_p * n)(*[None if a is None else C.addressof(a) for a in align])
+                times = (TokenTimes * n)()
+            self._check(lib().skw_full_batch_grammar(self.h, pp, ptrs, ns, n, on_dev, sp, cp, rules_ptr if rules is not None else None, ap, times, gp, res))
+        elif align is not None:
             if len(align) != n:
                 raise ValueError("full_batch: %d alignment records for %d clips" % (len(align), n))
             sp = None
@@ -565,7 +660,7 @@ class Context:
 
     def profile_get(self):
         out = {}
-        for cls in range(13):
+        for cls in range(14):
             name = C.create_string_buffer(64); cnt = C.c_long(); ms = C.c_double(); fl = C.c_double(); by = C.c_double()
             if lib().skw_ctx_profile_get(self.h, cls, name, 64, C.byref(cnt), C.byref(ms), C.byref(fl), C.byref(by)) == 0:
                 out[name.value.decode()] = dict(count=cnt.value, ms=ms.value, flops=fl.value, bytes=by.value)
@@ -643,12 +738,15 @@ class Context:
         self._check(lib().skw_decode_logits(self.h, t.ctypes.data, t.size, out.ctypes.data))
         return out
 
-    def sample_rows(self, hists, logits, params=None, form=0, want_filtered=False, rules=None, temperature=None, rng_state=None, trace=True, extras=False):
+    def sample_rows(self, hists, logits, params=None, form=0, want_filtered=False, rules=None, temperature=None, rng_state=None, trace=True, extras=False,
+                    grammars=None, active=None):
         """K11 on its own (skw_debug_sample_rows): one sampler launch decides the next token of len(hists) decoders whose sampled tokens so far are
         hists[r], on caller-supplied logits [rows][n_vocab].  form 0: the decode step's sampler; 1: the streaming kernel (leaves the filtered row
         in memory: want_filtered).  -> (tokens structured array, trace records, filtered logits or None)
         params=[FullParams per row]: the per-row form of the sampler (skw_debug_sample_rows_mixed) — every row under its own rules and its own static mask.
         rules=[DecodeRules or None per row]: skw_debug_sample_rows_rules — k_dec_constrain on the rows' logits, then the per-row form of the sampler.
+        grammars=[Grammar or None per row] (with rules= or without; active=[0 / 1 per row]: 0 marks a row as finished before the launch): skw_debug_sample_rows_grammar —
+        k_dec_constrain (when rules are given), k_dec_grammar, then the per-row form of the sampler, as in the decode step.
         temperature=[per row], rng_state=uint32 [rows][625] (updated in place: row r draws from generator r), trace=False (the launch without trace buffers) or extras=True:
         skw_debug_sample_rows_ex — a fourth element is returned, a dict of kernel (the instantiation the launcher picked), probs [rows][n_vocab] (rows at a temperature > 0;
         NaN elsewhere), no_speech_prob, n_tokens, cur_token, active [rows] (the rows' state after the launch)."""
@@ -668,6 +766,15 @@ class Context:
         filt = np.empty_like(lg) if want_filtered else None
         toks = np.zeros(R, dtype=_TOKEN_DT)
         tr = np.zeros(R, dtype=TRACE_DT)
+        if grammars is not None:
+            if temperature is not None or rng_state is not None or not trace or extras:
+                raise ValueError("sample_rows: grammars= goes with the plain call only")
+            gp = grammars_array(grammars, R, "row")
+            act = None if active is None else np.ascontiguousarray(active, dtype=np.int32).reshape(R)
+            self._check(lib().skw_debug_sample_rows_grammar(self.h, p if per_row else (FullParams * R)(*([p] * R)), R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
+                                                            filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data,
+                                                            rules_ptr if rules is not None else None, gp, None if act is None else act.ctypes.data))
+            return toks, tr, filt
         if temperature is not None or rng_state is not None or not trace or extras:
             if rules is not None:
                 raise ValueError("sample_rows: rules= goes with the plain call only")
