@@ -1,420 +1,13 @@
-// skw_engine.hip — host side of libskw_engine.so: GGML model loading, device workspace,
-// and the batched restatement of whisper_full_with_state (greedy, T = 0) on top of skw_kernels.
+// skw_engine.hip — the engine proper of libskw_engine.so: the switchboard, the context and its device workspace, and the batched restatement of
+// whisper_full_with_state (greedy, T = 0) on top of skw_kernels; at its end, the test hooks that drive the engine's own phases.
+// The rest of the library's host side lives beside it: GGML model loading, the quantised-weight repack and the tokenizer accessors in skw_model.hip; the kernel-level
+// test and measurement hooks (skw_debug_* on caller-supplied operands, skw_layout_*) in skw_hooks.hip; the model-free resampler context in skw_dsp.hip.
+// What they share is skw_engine_priv.h.
 //
 // Reference call sites this replaces: /root/reference/plugins/native/whisper/src/lib.rs
-//   :354-363 model load, :377-379 state, :624-646 params + full(), :650-660 segment readout.
-#include "../../include/skw_engine.h"
-#include "../../include/skw_math.h"
-#include "../../include/skw_ggml_quant.h"
-#include "skw_kernels.h"
-#include "skw_tokenizer.h"
-#include "skw_decode_rules.h"
-#include "skw_grammar_compile.h"
-#include <hip/hip_runtime.h>
-#include <algorithm>
-#include <atomic>
-#include <mutex>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
+//   :377-379 state, :624-646 params + full(), :650-660 segment readout.
+#include "skw_engine_priv.h"
 
-#define WHISPER_SAMPLE_RATE 16000
-#define WHISPER_N_FFT 400
-#define WHISPER_HOP 160
-#define WHISPER_CHUNK_SIZE 30
-
-static const char* const g_lang[] = {"en", "zh", "de", "es", "ru", "ko", "fr", "ja", "pt", "tr", "pl", "ca", "nl", "ar", "sv", "it", "id", "hi", "fi", "vi",
-    "he", "uk", "el", "ms", "cs", "ro", "da", "hu", "ta", "no", "th", "ur", "hr", "bg", "lt", "la", "mi", "ml", "cy", "sk", "te", "fa", "lv", "bn", "sr", "az",
-    "sl", "kn", "et", "mk", "br", "eu", "is", "hy", "ne", "mn", "bs", "kk", "sq", "sw", "gl", "mr", "pa", "si", "km", "sn", "yo", "so", "af", "oc", "ka", "be",
-    "tg", "sd", "gu", "am", "yi", "lo", "uz", "fo", "ht", "ps", "tk", "nn", "mt", "sa", "lb", "my", "bo", "tl", "mg", "as", "tt", "haw", "ln", "ha", "ba", "jw", "su", "yue"};
-static const int g_n_lang = (int)(sizeof(g_lang) / sizeof(g_lang[0]));
-// whisper.cpp's g_lang also maps the full language names; whisper_lang_id accepts either spelling
-static const char* const g_lang_name[] = {"english", "chinese", "german", "spanish", "russian", "korean", "french", "japanese", "portuguese", "turkish", "polish", "catalan", "dutch",
-    "arabic", "swedish", "italian", "indonesian", "hindi", "finnish", "vietnamese", "hebrew", "ukrainian", "greek", "malay", "czech", "romanian", "danish", "hungarian", "tamil", "norwegian",
-    "thai", "urdu", "croatian", "bulgarian", "lithuanian", "latin", "maori", "malayalam", "welsh", "slovak", "telugu", "persian", "latvian", "bengali", "serbian", "azerbaijani", "slovenian",
-    "kannada", "estonian", "macedonian", "breton", "basque", "icelandic", "armenian", "nepali", "mongolian", "bosnian", "kazakh", "albanian", "swahili", "galician", "marathi", "punjabi",
-    "sinhala", "khmer", "shona", "yoruba", "somali", "afrikaans", "occitan", "georgian", "belarusian", "tajik", "sindhi", "gujarati", "amharic", "yiddish", "lao", "uzbek", "faroese",
-    "haitian creole", "pashto", "turkmen", "nynorsk", "maltese", "sanskrit", "luxembourgish", "myanmar", "tibetan", "tagalog", "malagasy", "assamese", "tatar", "hawaiian", "lingala", "hausa",
-    "bashkir", "javanese", "sundanese", "cantonese"};
-static_assert(sizeof(g_lang_name) / sizeof(g_lang_name[0]) == sizeof(g_lang) / sizeof(g_lang[0]), "one name per code");
-
-static const char* const NST_LIST[] = {"\"", "#", "(", ")", "*", "+", "/", ":", ";", "<", "=", ">", "@", "[", "\\", "]", "^", "_", "`", "{", "|", "}", "~",
-    "\xe3\x80\x8c", "\xe3\x80\x8d", "\xe3\x80\x8e", "\xe3\x80\x8f", "<<", ">>", "<<<", ">>>", "--", "---", "-(", "-[", "('", "(\"", "((", "))", "(((", ")))",
-    "[[", "]]", "{{", "}}", "\xe2\x99\xaa\xe2\x99\xaa", "\xe2\x99\xaa\xe2\x99\xaa\xe2\x99\xaa", "\xe2\x99\xa9", "\xe2\x99\xaa", "\xe2\x99\xab", "\xe2\x99\xac",
-        "\xe2\x99\xad", "\xe2\x99\xae", "\xe2\x99\xaf"};
-static const int N_NST_LIST = (int)(sizeof(NST_LIST) / sizeof(NST_LIST[0]));
-
-static void set_err(char* err, size_t n, const char* fmt, ...) {
-    if (!err || !n) return;
-    va_list ap; va_start(ap, fmt); vsnprintf(err, n, fmt, ap); va_end(ap);
-}
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(errbuf, 512, "HIP error '%s' at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
-
-struct DevLin { half_t* w = nullptr; float* b = nullptr; int n_out = 0, n_in = 0, k_pad = 0;
-                half_t* w_nat = nullptr;   // the same weight with the contraction axis in natural order (decoder projections fed by a LayerNorm: skw_gemm16_small_lnA)
-                half_t* w_frag = nullptr; half_t* w_nat_frag = nullptr;   // fragment-order images of w / w_nat for the f16 decode kernels (SkwGemmArgs::Wf; decoder layers only)
-                // ggml's arithmetic for a block-quantised weight (skw_kernels_q8.hip): int8 [n_out][n_in], scales / offsets [n_in / 32][n_pad]; null for f16 weights
-                int8_t* qw = nullptr; float* dwT = nullptr; float* mwT = nullptr; int n_pad = 0, qform = 0; };
-struct HostQ { std::vector<int8_t> q; std::vector<float> d, m; int n_out = 0, K = 0; };      // a quantised weight in the common integer form, host side
-struct DevLN { float* w = nullptr; float* b = nullptr; };
-struct EncLayer { DevLN attn_ln, mlp_ln; DevLin q, k, v, o, fc1, fc2; };
-struct DecLayer { DevLN attn_ln, cross_ln, mlp_ln; DevLin q, k, v, o, cq, ck, cv, co, fc1, fc2; DevLin qkv; /* q|k|v rows concatenated for the fused decode projection */ };
-
-// qblk: the file's blocks of a quantised tensor (data: its f16 twin)
-struct RawT { std::string name; int n_dims = 0; int ne[4] = {1, 1, 1, 1}; int type = 0; std::vector<uint8_t> data; size_t n = 0; std::vector<uint8_t> qblk; int qtype = 0; };
-
-struct skw_model {
-    skw_hparams hp{};
-    int device = 0;
-    std::vector<std::string> tok_str;
-    SkwTokenizer tokz;      // text -> ids (skw_model_tokenize): the entries below <|endoftext|>
-    int tok_eot, tok_sot, tok_translate, tok_transcribe, tok_solm, tok_prev, tok_nosp, tok_not, tok_beg;
-    int tok_space = -1, tok_sp_dash = -1, tok_sp_quote = -1; std::vector<int> nst_ids; int n_lang = 99;
-    // device
-    float *filters = nullptr, *hann = nullptr, *sin_t = nullptr, *cos_t = nullptr; int n_fft_bins = 201; int *mel_grp_lo = nullptr, *mel_grp_hi = nullptr;
-    uint16_t* gelu_tab = nullptr;
-    float* e_pe = nullptr; DevLin conv1, conv2; DevLN ln_post; std::vector<EncLayer> enc;
-    float* d_pe = nullptr; DevLin te; DevLN d_ln; std::vector<DecLayer> dec;
-    int quant = 0;             // ggml type of the matmul weights when the file is uniformly block-quantised and ggml's q8 arithmetic is available (exact precision runs it)
-    float* te32 = nullptr;     // quant: the token embedding dequantised to f32 [n_vocab][d] (get_rows does not round to f16)
-    std::vector<void*> allocs;
-};
-
-template <typename T> static T* dev_upload(skw_model* m, const T* h, size_t n) {
-    T* d = nullptr; if (hipMalloc((void**)&d, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) return nullptr;
-    if (n && hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return nullptr; }
-    m->allocs.push_back(d); return d;
-}
-static RawT* find_t(std::vector<RawT>& ts, const std::string& name) { for (auto& t : ts) if (t.name == name) return &t; return nullptr; }
-static const float* as_f32(RawT* t, std::vector<float>& tmp) {
-    if (t->type == 0) return (const float*)t->data.data();
-    tmp.resize(t->n); const uint16_t* h = (const uint16_t*)t->data.data(); for (size_t i = 0; i < t->n; ++i) tmp[i] = skw_f16_to_f32(h[i]); return tmp.data();
-}
-static bool is_matmul_weight(const RawT& t) {
-    const std::string& n = t.name;
-    return t.n_dims == 2 && n.size() > 7 && n.compare(n.size() - 7, 7, ".weight") == 0 && n.find("positional_embedding") == std::string::npos && n.find("ln") == std::string::npos;
-}
-// blocks: n_out rows of K / 32 blocks of ggml type qtype, as the file holds them
-static void host_q(int qtype, const uint8_t* blocks, int n_out, int K, HostQ* h) {
-    const int nb = K / 32; const size_t bb = skw_ggml_block_bytes(qtype);
-    h->n_out = n_out; h->K = K; h->q.resize((size_t)n_out * K); h->d.resize((size_t)n_out * nb); h->m.resize((size_t)n_out * nb);
-    for (size_t i = 0; i < (size_t)n_out * nb; ++i) skw_ggml_unpack_block(qtype, blocks + i * bb, h->q.data() + i * 32, &h->d[i], &h->m[i]);
-}
-static void host_q(const RawT& w, HostQ* h) { host_q(w.qtype, w.qblk.data(), w.ne[1], w.ne[0], h); }
-// int8 rows as they are; scales and offsets transposed to [block][n_pad] so that a lane's four adjacent features are one 16-byte load
-static bool up_q(skw_model* m, const HostQ& h, int qtype, DevLin* L) {
-    const int nb = h.K / 32, n_pad = (h.n_out + 63) & ~63;
-    std::vector<float> dT((size_t)nb * n_pad, 0.0f), mT((size_t)nb * n_pad, 0.0f);
-    for (int n = 0; n < h.n_out; ++n) for (int b = 0; b < nb; ++b) { dT[(size_t)b * n_pad + n] = h.d[(size_t)n * nb + b]; mT[(size_t)b * n_pad + n] = h.m[(size_t)n * nb + b]; }
-    L->qw = dev_upload(m, h.q.data(), h.q.size()); L->dwT = dev_upload(m, dT.data(), dT.size()); L->mwT = dev_upload(m, mT.data(), mT.size());
-    L->n_pad = n_pad; L->qform = skw_ggml_dot_form(qtype);
-    return L->qw && L->dwT && L->mwT;
-}
-// f16 weight [n_out][n_in] (or conv [oc][ic][kw]) -> device [n_out][k_pad] with the contraction axis in kperm order
-static bool up_lin(skw_model* m, std::vector<RawT>& ts, const std::string& wname, const char* bname, DevLin* L, char* err, size_t errlen, bool want_nat = false) {
-    RawT* w = find_t(ts, wname);
-    if (!w) { set_err(err, errlen, "missing tensor %s", wname.c_str()); return false; }
-    if (w->type != 1) { set_err(err, errlen, "tensor %s: only f16 matmul weights are supported (ggml type %d)", wname.c_str(), w->type); return false; }
-    int n_in, n_out, kw = 1, ic = 0;
-    if (w->n_dims == 2) { n_in = w->ne[0]; n_out = w->ne[1]; }
-    else if (w->n_dims == 3) { kw = w->ne[0]; ic = w->ne[1]; n_in = kw * ic; n_out = w->ne[2]; }
-    else { set_err(err, errlen, "tensor %s: bad dims", wname.c_str()); return false; }
-    const int k_pad = (n_in + 31) & ~31;
-    std::vector<uint16_t> h((size_t)n_out * k_pad, 0);
-    const uint16_t* src = (const uint16_t*)w->data.data();
-    for (int o = 0; o < n_out; ++o) {
-        uint16_t* dst = h.data() + (size_t)o * k_pad;
-        if (w->n_dims == 2) for (int i = 0; i < n_in; ++i) dst[skw_kperm(i)] = src[(size_t)o * n_in + i];
-        else for (int c = 0; c < ic; ++c) for (int t = 0; t < kw; ++t) dst[skw_kperm(t * ic + c)] = src[((size_t)o * ic + c) * kw + t];
-    }
-    L->n_in = n_in; L->n_out = n_out; L->k_pad = k_pad;
-    L->w = (half_t*)dev_upload(m, h.data(), h.size());
-    if (!L->w) { set_err(err, errlen, "device allocation failed for %s", wname.c_str()); return false; }
-    if (want_nat && w->n_dims == 2 && k_pad == n_in) { L->w_nat = (half_t*)dev_upload(m, src, (size_t)n_out * n_in);
-    if (!L->w_nat) { set_err(err, errlen, "device allocation failed for %s", wname.c_str()); return false; } }
-    if (m->quant && !w->qblk.empty()) { HostQ h; host_q(*w, &h); if (!up_q(m, h, w->qtype, L)) { set_err(err, errlen, "device allocation failed for %s", wname.c_str()); return false; } }
-    L->b = nullptr;
-    if (bname) {
-        RawT* b = find_t(ts, bname);
-        if (!b) { set_err(err, errlen, "missing tensor %s", bname); return false; }
-        std::vector<float> tmp; L->b = dev_upload(m, as_f32(b, tmp), b->n);
-    }
-    return true;
-}
-static bool up_ln(skw_model* m, std::vector<RawT>& ts, const std::string& wname, const std::string& bname, DevLN* L, char* err, size_t errlen) {
-    RawT* w = find_t(ts, wname); RawT* b = find_t(ts, bname);
-    if (!w || !b) { set_err(err, errlen, "missing tensor %s / %s", wname.c_str(), bname.c_str()); return false; }
-    std::vector<float> t1, t2; L->w = dev_upload(m, as_f32(w, t1), w->n); L->b = dev_upload(m, as_f32(b, t2), b->n); return L->w && L->b;
-}
-
-extern "C" int skw_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
-extern "C" void* skw_host_alloc(size_t bytes) { void* p = nullptr;
-if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; } return p; }
-extern "C" void skw_host_free(void* p) { if (p) (void)hipHostFree(p); }
-extern "C" int skw_model_lang_id(const char* lang) {
-    if (!lang) return -1;
-    for (int i = 0; i < g_n_lang; ++i) if (!strcmp(g_lang[i], lang)) return i;
-    for (int i = 0; i < g_n_lang; ++i) if (!strcmp(g_lang_name[i], lang)) return i;
-    return -1;
-}
-
-static skw_model* model_load_impl(const char* path, int device, int quant_mode, char* err, size_t errlen);
-extern "C" skw_model* skw_model_load_ex(const char* path, int device, int quant_mode, char* err, size_t errlen) {
-    try { return model_load_impl(path, device, quant_mode, err, errlen); }
-    catch (const std::exception& e) { set_err(err, errlen, "Failed to load Whisper model from '%s': %s", path ? path : "", e.what()); return nullptr; }   // nothing may unwind across the C ABI
-}
-extern "C" skw_model* skw_model_load(const char* path, int device, char* err, size_t errlen) { return skw_model_load_ex(path, device, SKW_QUANT_GGML, err, errlen); }
-extern "C" int skw_model_quant_type(const skw_model* m) { return m->quant; }
-static skw_model* model_load_impl(const char* path, int device, int quant_mode, char* err, size_t errlen) {
-    int ndev = skw_device_count();
-    if (ndev <= 0) { set_err(err, errlen, "no HIP device available: libskw_engine requires an MI355X (gfx950); there is no CPU fallback"); return nullptr; }
-    if (device < 0 || device >= ndev) { set_err(err, errlen, "gpu_device %d out of range (%d devices)", device, ndev); return nullptr; }
-    if (hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice(%d) failed", device); return nullptr; }
-    FILE* f = fopen(path, "rb");
-    if (!f) { set_err(err, errlen, "Failed to load Whisper model from '%s': cannot open file", path); return nullptr; }
-    int32_t magic = 0;
-    if (fread(&magic, 4, 1, f) != 1 || magic != 0x67676d6c) { fclose(f); set_err(err, errlen, "Failed to load Whisper model from '%s': bad magic", path); return nullptr; }
-    skw_model* m = new skw_model(); m->device = device;
-    auto fail = [&](const char* msg) -> skw_model* { set_err(err, errlen, "Failed to load Whisper model from '%s': %s", path, msg); fclose(f); skw_model_free(m); return nullptr; };
-    if (fread(&m->hp, 4, 11, f) != 11) return fail("short hparams");
-    {   // a corrupt header must fail here, not as std::bad_alloc across the C ABI
-        const skw_hparams& h = m->hp;
-        auto in = [](int v, int lo, int hi) { return v >= lo && v <= hi; };
-        if (!in(h.n_vocab, 1000, 200000) || !in(h.n_audio_ctx, 1, 4096) || !in(h.n_audio_state, 64, 1536) || !in(h.n_audio_head, 1, 32) || !in(h.n_audio_layer, 1, 64) ||
-            !in(h.n_text_ctx, 8, 4096) || !in(h.n_text_state, 64, 1536) || !in(h.n_text_head, 1, 32) || !in(h.n_text_layer, 1, 64) || !in(h.n_mels, 1, 256)) return fail("implausible hparams");
-    }
-    int32_t nm = 0, nf = 0;
-    if (fread(&nm, 4, 1, f) != 1 || fread(&nf, 4, 1, f) != 1) return fail("short mel filter header");
-    if (nm < 1 || nm > 256 || nf < 1 || nf > 4096) return fail("implausible mel filter header");
-    std::vector<float> filt((size_t)nm * nf);
-    if (fread(filt.data(), 4, filt.size(), f) != filt.size()) return fail("short mel filters");
-    m->n_fft_bins = nf;
-    if (nm != m->hp.n_mels) return fail("mel filter count differs from n_mels");
-    int32_t nv = 0; if (fread(&nv, 4, 1, f) != 1) return fail("short vocab");
-    if (nv < 0 || nv > 200000) return fail("implausible vocabulary size");
-    const int NV = m->hp.n_vocab; m->tok_str.assign(NV, std::string());
-    for (int i = 0; i < nv; ++i) {
-        uint32_t len = 0; if (fread(&len, 4, 1, f) != 1) return fail("short vocab");
-        if (len > 4096) return fail("implausible token length");
-        std::string s(len, '\0'); if (len && fread(&s[0], 1, len, f) != len) return fail("short vocab");
-        if (i < NV) m->tok_str[i] = s;
-    }
-    m->tok_eot = 50256; m->tok_sot = 50257; m->tok_translate = 50357; m->tok_transcribe = 50358; m->tok_solm = 50359;
-    m->tok_prev = 50360; m->tok_nosp = 50361; m->tok_not = 50362; m->tok_beg = 50363;
-    if (NV >= 51865) {
-        m->tok_eot++; m->tok_sot++; const int dt = NV - 51865;
-        m->tok_translate += 1 + dt; m->tok_transcribe += 1 + dt; m->tok_solm += 1 + dt; m->tok_prev += 1 + dt; m->tok_nosp += 1 + dt; m->tok_not += 1 + dt; m->tok_beg += 1 + dt;
-        m->n_lang = 99 + dt;
-    }
-    for (int i = nv; i < NV; ++i) {
-        char buf[64];
-        if (i > m->tok_beg) snprintf(buf, sizeof buf, "[_TT_%d]", i - m->tok_beg);
-        else if (i == m->tok_eot) snprintf(buf, sizeof buf, "[_EOT_]");
-        else if (i == m->tok_sot) snprintf(buf, sizeof buf, "[_SOT_]");
-        else if (i == m->tok_translate) snprintf(buf, sizeof buf, "[_TRANSLATE_]");
-        else if (i == m->tok_transcribe) snprintf(buf, sizeof buf, "[_TRANSCRIBE_]");
-        else if (i == m->tok_solm) snprintf(buf, sizeof buf, "[_SOLM_]");
-        else if (i == m->tok_prev) snprintf(buf, sizeof buf, "[_PREV_]");
-        else if (i == m->tok_nosp) snprintf(buf, sizeof buf, "[_NOSP_]");
-        else if (i == m->tok_not) snprintf(buf, sizeof buf, "[_NOT_]");
-        else if (i == m->tok_beg) snprintf(buf, sizeof buf, "[_BEG_]");
-        else if (i > m->tok_sot && i <= m->tok_sot + m->n_lang) snprintf(buf, sizeof buf, "[_LANG_%s]", g_lang[std::min(i - m->tok_sot - 1, g_n_lang - 1)]);
-        else snprintf(buf, sizeof buf, "[_extra_token_%d]", i);
-        m->tok_str[i] = buf;
-    }
-    m->tokz.build(m->tok_str, m->tok_eot);
-    { // token_to_id lookups performed by whisper_process_logits (a later duplicate string wins, as std::map::operator[] does)
-        std::map<std::string, int> t2i; for (int i = 0; i < NV; ++i) t2i[m->tok_str[i]] = i;
-        auto get = [&](const std::string& s) { auto it = t2i.find(s); return it == t2i.end() ? -1 : it->second; };
-        m->tok_space = get(" "); m->tok_sp_dash = get(" -"); m->tok_sp_quote = get(" '");
-        for (int j = 0; j < N_NST_LIST; ++j) for (int sp = 0; sp < 2; ++sp) { int id = get(std::string(sp ? " " : "") + NST_LIST[j]); if (id >= 0) m->nst_ids.push_back(id); }
-    }
-    std::vector<RawT> ts;
-    for (;;) {
-        int32_t nd, len, tt; if (fread(&nd, 4, 1, f) != 1) break;
-        if (fread(&len, 4, 1, f) != 1 || fread(&tt, 4, 1, f) != 1) return fail("short tensor header");
-        RawT t; t.n_dims = nd; t.type = tt; t.n = 1;
-        if (nd < 1 || nd > 4 || len < 0 || len > 255) return fail("corrupt tensor header");
-        for (int i = 0; i < nd; ++i) { int32_t e; if (fread(&e, 4, 1, f) != 1) return fail("short tensor header");
-        if (e < 1 || e > (1 << 24)) return fail("corrupt tensor header"); t.ne[i] = e; t.n *= (size_t)e; }
-        if (t.n > ((size_t)1 << 31)) return fail("corrupt tensor header");
-        t.name.resize(len); if (len && fread(&t.name[0], 1, len, f) != (size_t)len) return fail("short tensor name");
-        size_t esz = tt == 0 ? 4 : tt == 1 ? 2 : 0;
-        if (!esz) {   // block-quantised 2-D weights: decoded to f16 here (include/skw_ggml_quant.h, DEVIATION D4)
-            const size_t bb = skw_ggml_block_bytes(tt);
-            if (!bb || t.ne[0] % 32) { std::string msg = "tensor " + t.name + ": unsupported ggml type " + std::to_string(tt) + " (f32, f16, q4_0, q4_1, q5_0, q5_1, q8_0 are read)";
-            return fail(msg.c_str()); }
-            std::vector<uint8_t> blocks(t.n / 32 * bb); if (fread(blocks.data(), 1, blocks.size(), f) != blocks.size()) return fail("short tensor data");
-            t.data.resize(t.n * 2); skw_ggml_dequant_to_f16(tt, blocks.data(), t.n, (uint16_t*)t.data.data()); t.type = 1; t.qtype = tt; t.qblk = std::move(blocks);
-            ts.push_back(std::move(t)); continue;
-        }
-        t.data.resize(t.n * esz); if (fread(t.data.data(), 1, t.data.size(), f) != t.data.size()) return fail("short tensor data");
-        ts.push_back(std::move(t));
-    }
-    fclose(f); f = nullptr;
-    {   // ggml's q8 arithmetic needs every matmul weight in one block type (what whisper.cpp's quantize writes); anything else runs as the f16 twin
-        int qt = 0; bool uniform = quant_mode != 0 && !skw_sw(SW_QUANT_TWIN);
-        for (auto& t : ts) if (is_matmul_weight(t)) { if (t.qblk.empty()) uniform = false; else if (!qt) qt = t.qtype; else if (qt != t.qtype) uniform = false; }
-        m->quant = (uniform && qt) ? qt : 0;
-    }
-    auto fail2 = [&]() -> skw_model* { skw_model_free(m); return nullptr; };
-    // tables
-    m->filters = dev_upload(m, filt.data(), filt.size());
-    {   // per mel filter: the range of 4-bin groups with a non-zero tap (the filterbank comes from the model file; Slaney filters are narrow)
-        std::vector<int> lo(nm, 0), hi(nm, 0);
-        for (int j = 0; j < nm; ++j) { int a = nf, b = -1; for (int k = 0; k < nf; ++k) if (filt[(size_t)j * nf + k] != 0.0f) { a = std::min(a, k);
-        b = std::max(b, k); } if (b >= 0) { lo[j] = a / 4; hi[j] = b / 4 + 1; } }
-        m->mel_grp_lo = dev_upload(m, lo.data(), lo.size()); m->mel_grp_hi = dev_upload(m, hi.data(), hi.size());
-    }
-    {
-        std::vector<float> sn(WHISPER_N_FFT), cs(WHISPER_N_FFT), hn(WHISPER_N_FFT);
-        for (int i = 0; i < WHISPER_N_FFT; ++i) { double theta = (2 * M_PI * i) / WHISPER_N_FFT;
-        sn[i] = sinf(theta); cs[i] = cosf(theta); hn[i] = 0.5 * (1.0 - cosf((2.0 * M_PI * i) / (WHISPER_N_FFT))); }
-        m->sin_t = dev_upload(m, sn.data(), sn.size()); m->cos_t = dev_upload(m, cs.data(), cs.size()); m->hann = dev_upload(m, hn.data(), hn.size());
-        std::vector<uint16_t> gt(65536); for (int i = 0; i < 65536; ++i) gt[i] = skw_gelu_table_entry((uint16_t)i);
-        m->gelu_tab = dev_upload(m, gt.data(), gt.size());
-    }
-    std::vector<float> tmp;
-    RawT* t;
-    if (!(t = find_t(ts, "encoder.positional_embedding"))) { set_err(err, errlen, "missing encoder.positional_embedding"); return fail2(); }
-    m->e_pe = dev_upload(m, as_f32(t, tmp), t->n);
-    if (!(t = find_t(ts, "decoder.positional_embedding"))) { set_err(err, errlen, "missing decoder.positional_embedding"); return fail2(); }
-    m->d_pe = dev_upload(m, as_f32(t, tmp), t->n);
-    bool ok = true;
-    // fragment-order images of the decoder projections (SkwGemmArgs::Wf); =0: the f16 decode kernels read weight rows
-    const bool wfrag_on = skw_sw(SW_DEC_WFRAG) != 0;
-    ok = ok && up_lin(m, ts, "encoder.conv1.weight", "encoder.conv1.bias", &m->conv1, err, errlen);
-    // conv1 runs as a product over the im2col image [frames][3 n_mels padded]: the f16 GEMMs step K by 64 (80 bands: 240 -> 256, large-v3's 128: 384)
-    if (ok && ((m->conv1.k_pad & 63) || m->conv1.n_in != 3 * m->hp.n_mels || m->hp.n_mels > 128)) {
-        set_err(err, errlen, "encoder.conv1.weight: 3 x n_mels = %d taps do not pad to a multiple of 64 (n_mels 80 and 128 are supported)", m->conv1.n_in); ok = false;
-    }
-    ok = ok && up_lin(m, ts, "encoder.conv2.weight", "encoder.conv2.bias", &m->conv2, err, errlen);
-    ok = ok && up_ln(m, ts, "encoder.ln_post.weight", "encoder.ln_post.bias", &m->ln_post, err, errlen);
-    m->enc.resize(m->hp.n_audio_layer);
-    for (int l = 0; l < m->hp.n_audio_layer && ok; ++l) {
-        EncLayer& L = m->enc[l]; std::string p = "encoder.blocks." + std::to_string(l) + ".";
-        ok = ok && up_ln(m, ts, p + "attn_ln.weight", p + "attn_ln.bias", &L.attn_ln, err, errlen);
-        ok = ok && up_lin(m, ts, p + "attn.query.weight", (p + "attn.query.bias").c_str(), &L.q, err, errlen);
-        ok = ok && up_lin(m, ts, p + "attn.key.weight", nullptr, &L.k, err, errlen);
-        ok = ok && up_lin(m, ts, p + "attn.value.weight", (p + "attn.value.bias").c_str(), &L.v, err, errlen);
-        ok = ok && up_lin(m, ts, p + "attn.out.weight", (p + "attn.out.bias").c_str(), &L.o, err, errlen);
-        ok = ok && up_ln(m, ts, p + "mlp_ln.weight", p + "mlp_ln.bias", &L.mlp_ln, err, errlen);
-        ok = ok && up_lin(m, ts, p + "mlp.0.weight", (p + "mlp.0.bias").c_str(), &L.fc1, err, errlen);
-        ok = ok && up_lin(m, ts, p + "mlp.2.weight", (p + "mlp.2.bias").c_str(), &L.fc2, err, errlen);
-    }
-    ok = ok && up_lin(m, ts, "decoder.token_embedding.weight", nullptr, &m->te, err, errlen);
-    if (ok && m->quant) {   // get_rows on the quantised token embedding: q * d (+ m) in f32, not rounded to f16
-        RawT* te = find_t(ts, "decoder.token_embedding.weight"); const size_t bb = skw_ggml_block_bytes(te->qtype); std::vector<float> e32(te->n);
-        for (size_t i = 0; i < te->n / 32; ++i) skw_ggml_dequant_block(te->qtype, te->qblk.data() + i * bb, e32.data() + i * 32);
-        m->te32 = dev_upload(m, e32.data(), e32.size()); ok = m->te32 != nullptr;
-    }
-    ok = ok && up_ln(m, ts, "decoder.ln.weight", "decoder.ln.bias", &m->d_ln, err, errlen);
-    m->dec.resize(m->hp.n_text_layer);
-    for (int l = 0; l < m->hp.n_text_layer && ok; ++l) {
-        DecLayer& L = m->dec[l]; std::string p = "decoder.blocks." + std::to_string(l) + ".";
-        ok = ok && up_ln(m, ts, p + "attn_ln.weight", p + "attn_ln.bias", &L.attn_ln, err, errlen);
-        ok = ok && up_lin(m, ts, p + "attn.query.weight", (p + "attn.query.bias").c_str(), &L.q, err, errlen, true);
-        ok = ok && up_lin(m, ts, p + "attn.key.weight", nullptr, &L.k, err, errlen, true);
-        ok = ok && up_lin(m, ts, p + "attn.value.weight", (p + "attn.value.bias").c_str(), &L.v, err, errlen, true);
-        ok = ok && up_lin(m, ts, p + "attn.out.weight", (p + "attn.out.bias").c_str(), &L.o, err, errlen);
-        ok = ok && up_ln(m, ts, p + "cross_attn_ln.weight", p + "cross_attn_ln.bias", &L.cross_ln, err, errlen);
-        ok = ok && up_lin(m, ts, p + "cross_attn.query.weight", (p + "cross_attn.query.bias").c_str(), &L.cq, err, errlen, true);
-        ok = ok && up_lin(m, ts, p + "cross_attn.key.weight", nullptr, &L.ck, err, errlen);
-        ok = ok && up_lin(m, ts, p + "cross_attn.value.weight", (p + "cross_attn.value.bias").c_str(), &L.cv, err, errlen);
-        ok = ok && up_lin(m, ts, p + "cross_attn.out.weight", (p + "cross_attn.out.bias").c_str(), &L.co, err, errlen);
-        ok = ok && up_ln(m, ts, p + "mlp_ln.weight", p + "mlp_ln.bias", &L.mlp_ln, err, errlen);
-        ok = ok && up_lin(m, ts, p + "mlp.0.weight", (p + "mlp.0.bias").c_str(), &L.fc1, err, errlen, true);
-        ok = ok && up_lin(m, ts, p + "mlp.2.weight", (p + "mlp.2.bias").c_str(), &L.fc2, err, errlen);
-        if (ok) {   // fused q|k|v weight [3d][k_pad] and bias [3d] (k has no bias: zeros; adding 0.0f is exact)
-            const int d = L.q.n_out, kp = L.q.k_pad; L.qkv.n_in = L.q.n_in; L.qkv.n_out = 3 * d; L.qkv.k_pad = kp;
-            half_t* w = nullptr; float* b = nullptr;
-            if (hipMalloc((void**)&w, (size_t)3 * d * kp * 2) != hipSuccess || hipMalloc((void**)&b, (size_t)3 * d * 4) != hipSuccess) { set_err(err, errlen, "device allocation failed"); ok = false; }
-            else {
-                m->allocs.push_back(w); m->allocs.push_back(b);
-                hipMemcpy(w, L.q.w, (size_t)d * kp * 2, hipMemcpyDeviceToDevice);
-                hipMemcpy(w + (size_t)d * kp, L.k.w, (size_t)d * kp * 2, hipMemcpyDeviceToDevice);
-                hipMemcpy(w + (size_t)2 * d * kp, L.v.w, (size_t)d * kp * 2, hipMemcpyDeviceToDevice);
-                hipMemset(b, 0, (size_t)3 * d * 4); hipMemcpy(b, L.q.b, (size_t)d * 4, hipMemcpyDeviceToDevice); hipMemcpy(b + 2 * d, L.v.b, (size_t)d * 4, hipMemcpyDeviceToDevice);
-                L.qkv.w = w; L.qkv.b = b;
-                if (L.q.w_nat && L.k.w_nat && L.v.w_nat) {      // the concatenation again in natural k order
-                    half_t* wn = nullptr;
-                    if (hipMalloc((void**)&wn, (size_t)3 * d * kp * 2) == hipSuccess) {
-                        m->allocs.push_back(wn);
-                        hipMemcpy(wn, L.q.w_nat, (size_t)d * kp * 2, hipMemcpyDeviceToDevice);
-                        hipMemcpy(wn + (size_t)d * kp, L.k.w_nat, (size_t)d * kp * 2, hipMemcpyDeviceToDevice);
-                        hipMemcpy(wn + (size_t)2 * d * kp, L.v.w_nat, (size_t)d * kp * 2, hipMemcpyDeviceToDevice);
-                        L.qkv.w_nat = wn;
-                    }
-                }
-            }
-            // fragment-order images for the f16 decode kernels (skw_make_wfrag): every decoder projection the small-M kernels multiply by; fc1's rows in its GELU epilogue's order
-            if (ok && wfrag_on) {
-                auto mk = [&](DevLin& X, int perm) {
-                    if ((X.n_out & 15) || (X.k_pad & 31)) return;
-                    for (int nat = 0; nat < 2; ++nat) {
-                        const half_t* src = nat ? X.w_nat : X.w; if (!src) continue;
-                        half_t* img = nullptr; if (hipMalloc((void**)&img, (size_t)X.n_out * X.k_pad * 2) != hipSuccess) continue;      // (no image: the kernels read the rows)
-                        m->allocs.push_back(img); skw_make_wfrag(src, X.k_pad, X.n_out, X.k_pad, perm, img, nullptr);
-                        (nat ? X.w_nat_frag : X.w_frag) = img;
-                    }
-                };
-                mk(L.qkv, 0); mk(L.o, 0); mk(L.cq, 0); mk(L.co, 0); mk(L.fc1, 1); mk(L.fc2, 0);
-                mk(L.ck, 0); mk(L.cv, 0);      // the encoder pass's cross K / V^T products (k_gemm16w streams its weights from these images)
-            }
-            if (ok && m->quant) {   // the same concatenation in the integer form
-                HostQ hq, hk, hv, all; host_q(*find_t(ts, p + "attn.query.weight"), &hq); host_q(*find_t(ts, p + "attn.key.weight"), &hk); host_q(*find_t(ts, p + "attn.value.weight"), &hv);
-                all.n_out = 3 * d; all.K = hq.K;
-                for (const HostQ* h : {&hq, &hk, &hv}) { all.q.insert(all.q.end(), h->q.begin(), h->q.end());
-                all.d.insert(all.d.end(), h->d.begin(), h->d.end()); all.m.insert(all.m.end(), h->m.begin(), h->m.end()); }
-                ok = up_q(m, all, m->quant, &L.qkv);
-            }
-        }
-    }
-    // Encoder weights as fragment-order images too (k_gemm16w, the f16_mfma precision's big GEMM: weights go from these straight into MFMA operands).  Rows in the
-    // order of the epilogue that consumes the product: the kperm'ed-output epilogues (Q / K heads, FC1 and conv1 GELU) want strip row p = logical feature kperm^-1(p).
-    if (ok) {
-        auto mke = [&](DevLin& X, int perm) {
-            if ((X.n_out & 15) || (X.k_pad & 63) || !X.w) return;
-            half_t* img = nullptr;
-            if (hipMalloc((void**)&img, (size_t)X.n_out * X.k_pad * 2) != hipSuccess) return;      // (no image: k_gemm16 stages the rows through LDS)
-            m->allocs.push_back(img);
-            skw_make_wfrag(X.w, X.k_pad, X.n_out, X.k_pad, perm, img, nullptr);
-            X.w_frag = img;
-        };
-        mke(m->conv1, 1);
-        mke(m->conv2, 0);
-        for (EncLayer& L : m->enc) {
-            mke(L.q, 1);
-            mke(L.k, 1);
-            mke(L.v, 0);
-            mke(L.o, 0);
-            mke(L.fc1, 1);
-            mke(L.fc2, 0);
-        }
-        if (hipDeviceSynchronize() != hipSuccess) ok = false;
-    }
-    if (!ok) return fail2();
-    if ((m->hp.n_audio_state / m->hp.n_audio_head) != 64 || (m->hp.n_text_state / m->hp.n_text_head) != 64 || m->hp.n_audio_state % 128 || m->hp.n_text_state % 128 || m->hp.n_audio_state > 1536) {
-        // (a multiple of 128: the decoder's contractions are four contiguous K segments, D3'; every Whisper width — 384, 512, 768, 1024, 1280 — is one)
-        set_err(err, errlen, "unsupported model geometry (head dim must be 64, state a multiple of 128 and <= 1536)"); return fail2();
-    }
-    hipDeviceSynchronize();
-    return m;
-}
-extern "C" void skw_model_free(skw_model* m) { if (!m) return; hipSetDevice(m->device); for (void* p : m->allocs) hipFree(p); delete m; }
-extern "C" void skw_model_get_hparams(const skw_model* m, skw_hparams* out) { *out = m->hp; }
-extern "C" const char* skw_model_token_text(const skw_model* m, int id, int* len) {
-    if (id < 0 || id >= m->hp.n_vocab) { if (len) *len = 0; return ""; }
-    if (len) *len = (int)m->tok_str[id].size(); return m->tok_str[id].c_str();
-}
-extern "C" int skw_model_tokenize(const skw_model* m, const char* text, int32_t* ids, int cap) {
-    try { return m->tokz.tokenize_into(text, ids, (ids && cap > 0) ? cap : 0); } catch (const std::exception&) { return 0; }      // (nothing may unwind across the C ABI)
-}
 // the "auto" audio context of a clip: the positions its audio covers (20 ms each), half a second of margin, whole 32-key blocks — never more than the model's context
 extern "C" int skw_audio_ctx_for_samples(int n_samples, int n_audio_ctx) {
     if (n_samples >= WHISPER_SAMPLE_RATE * WHISPER_CHUNK_SIZE) return n_audio_ctx;
@@ -464,108 +57,21 @@ extern "C" int skw_debug_switch_get(const char* name) { const int i = sw_find(na
 // tests flip a switch in-process (takes effect at the point the table says: the next launch, context creation or model load; cached step graphs are re-captured)
 extern "C" int skw_debug_switch_set(const char* name, int value) { const int i = sw_find(name); if (i < 0) return -1; (void)skw_sw(i); g_sw_val[i] = value; g_sw_epoch.fetch_add(1); return 0; }
 
+// a row held at a value for a scope (skw_engine_priv.h): like skw_debug_switch_set, but the epoch stands — the kernel hooks launch no step graph
+SwOverride::SwOverride(int id_, int value) : id(id_), was(skw_sw(id_)) { g_sw_val[id] = value; }
+SwOverride::~SwOverride() { g_sw_val[id] = was; }
+void SwOverride::set(int value) { g_sw_val[id] = value; }
+
 // ------------------------------------------------------------------ context / workspace
-struct ProfState;
 // tests (SKW_TEST_ALLOC_POISON=1 in tests/conftest.py): workspace buffers of floating type that the engine does not zero are filled with NaNs when a context is created, so that a
 // kernel reading what no kernel wrote shows up as a changed result instead of passing on whatever hipMalloc returned (round 5: a resampler flag was read that way)
 static int g_alloc_poison = 0; static std::atomic<long> g_alloc_poisoned{0};
 extern "C" void skw_debug_alloc_poison(int on) { g_alloc_poison = on; }
 extern "C" long skw_debug_alloc_poisoned(void) { return g_alloc_poisoned.load(); }      // buffers filled so far
-static void poison_floats(void* p, size_t bytes) { if (g_alloc_poison && p) { (void)hipMemset(p, 0xFF, bytes); g_alloc_poisoned.fetch_add(1); } }
-struct skw_ctx {
-    int precision = SKW_PRECISION_EXACT;             // SKW_PRECISION_*: which form of the contractions runs (skw_ctx_set_precision)
-    int kv_frag_on = 1;                              // f16_mfma: cross K / V^T as fragment-order images (skw_kernels.h, skw_kfrag_off); SKW_XATTN_FRAG=0 keeps the row layouts
-    bool kv_frag() const { return kv_frag_on && precision == SKW_PRECISION_F16_MFMA; }
-    // cross_kv = q8_0 (skw_ctx_set_cross_kv; include/skw_kv8.h): the single-query cross attention of the f16_mfma precision reads the q8 image the encoder pass leaves beside the
-    // f16 fragment-order images.  Effective only with those images (kv8()): the exact precision owes the oracle its bits and ignores the flag.  kv8_fresh: the image holds the
-    // slots of the last encoder pass (false after a pass that ran without the flag) — what the decode step asks, so a flag flipped between an encode and a step changes nothing.
-    int cross_kv = SKW_CROSS_KV_F16; uint8_t* crossKV8 = nullptr; bool kv8_fresh = false;
-    bool kv8() const { return cross_kv == SKW_CROSS_KV_Q8_0 && kv_frag() && crossKV8; }
-    bool kv8_step() const { return kv8() && kv8_fresh; }
-    size_t kv8_slot() const { return (size_t)skw_kv8_slot_bytes(m->hp.n_text_head, Tpad); }
-    size_t kclip() const { return (size_t)(kv_frag() ? Tpad : m->hp.n_audio_ctx) * m->hp.n_text_state; }      // cross-K elements per window slot (the buffer is sized for the larger: Tpad rows)
-    ProfState* prof = nullptr;                       // per-kernel-class event timing (skw_ctx_profile); per context: contexts run on different host threads
-    skw_model* m = nullptr; int max_batch = 0, max_samples = 0, n_len_max = 0, Tpad = 0;
-    hipStream_t stream = nullptr; hipEvent_t ev[6] = {};
-    hipStream_t cur = nullptr;                       // stream the launch helpers enqueue on (== stream outside the decode groups)
-    static const int MAX_GROUPS = 8; hipStream_t gstream[MAX_GROUPS] = {}; hipEvent_t gev[MAX_GROUPS] = {}; int n_groups = 1;
-    struct StepGraph { int g, r0, n, precision, ln_stats, kclk, var_k, kv8; unsigned sw_epoch; SkwLogitParams lp; int rows, cons, gram; hipGraphExec_t exec; };
-    std::vector<StepGraph> step_graphs; int use_graphs = 1;
-    char errbuf[512] = {0};
-    std::vector<void*> allocs;
-    // front end
-    float* pcm = nullptr; long* pcm_off = nullptr; int* n_samples = nullptr; int* n_len = nullptr; float* mel = nullptr; float* clip_max = nullptr;
-    int *clip_idx = nullptr, *seek = nullptr;
-    // per-clip audio context (skw_full_params.audio_ctx): slot_k[slot] = the positions of the window in that slot, travelling with clip_idx / seek.  var_k: some slot of the
-    // current pass is shorter than n_audio_ctx — the attention kernels then take their extents from slot_k / SkwSeqState.n_keys (device memory); otherwise the launches are today's.
-    // enc_rows: rows per slot of the encoder's activations in the last pass (dense: the largest K of the pass, rounded — enc_rows_for); h1_T: the conv1 rows per slot whose pad
-    // rows are currently zero in h1
-    int* slot_k = nullptr; bool var_k = false; int enc_rows = 0, h1_T = 0;
-    half_t* im2col = nullptr; half_t* h1 = nullptr;
-    // encoder
-    float* x = nullptr; half_t* y16 = nullptr; half_t *Qh = nullptr, *Kh = nullptr, *Vt = nullptr; half_t* hbuf = nullptr; float* enc_out32 = nullptr;
-    half_t *crossK = nullptr, *crossV = nullptr;
-    // decoder
-    // ggml q8 arithmetic (quantised files, exact precision): unrounded f32 activations and their q8 blocks
-    float* dx = nullptr; half_t *dy16 = nullptr, *dq16 = nullptr, *datt16 = nullptr, *dh16 = nullptr;
-    half_t *selfK = nullptr, *selfV = nullptr; float* logits = nullptr;
-    float *y32 = nullptr, *h32 = nullptr, *encq32 = nullptr, *dy32 = nullptr, *datt32 = nullptr, *dh32 = nullptr;
-    int8_t* q8_a = nullptr; float *q8_d = nullptr, *q8_s = nullptr; int q8_kmax = 0;
-    // allocated at the first temperature retry (move_retry_slots)
-    half_t *stageK = nullptr, *stageV = nullptr; int* slot_map = nullptr;
-    int* prompt_buf = nullptr;                       // [B][SKW_PROMPT_CAP] per-row prompts
-    int* row_tok = nullptr;                          // per-row prompt token / detected language scratch
-    float* probs = nullptr; uint32_t* rng = nullptr;   // sampled (t > 0) passes: probability workspace, std::mt19937 state per clip
-    SkwSeqState* st = nullptr; SkwTokenOut* toks = nullptr; uint8_t* static_mask = nullptr; int static_mask_nst = -1;
-    // skw_full_batch_mixed: both static masks back to back ([0] without, [1] with the non-speech list; written at the first mixed call) and the rows' own rules, per window
-    uint8_t* static_mask_pair = nullptr; int static_mask_pair_built = 0; SkwRowRules* row_rules = nullptr;
-    SkwRowConstraints* row_cons = nullptr;           // skw_full_batch_rules: the rows' decoding constraints, per window (read by k_dec_constrain, which only constrained calls launch)
-    // skw_full_batch_grammar (include/skw_grammar.h): the rows' grammar records, per window (read and advanced by k_dec_grammar_state / k_dec_grammar, which only calls with a
-    // grammar launch); the text tokens' bytes on the device (offsets + bytes, built at the first such call: grammar_vocab_ensure); a small content-keyed cache of uploaded
-    // tables, so a node instance's grammar is uploaded once and not per segment (most recently used last; entries of the call in flight are never evicted); and the call's
-    // record per clip (next == nullptr: the clip has none)
-    SkwRowGrammar* row_gram = nullptr; int32_t* gr_voc_off = nullptr; uint8_t* gr_voc_bytes = nullptr;
-    struct GrammarImage { uint64_t hash; int n_states; std::vector<uint16_t> next; std::vector<uint8_t> accept; uint16_t* d_next; uint8_t* d_accept; long stamp; };
-    const int32_t* dbg_active = nullptr;      // skw_debug_sample_rows_grammar: rows the hook marks as finished (only inside that call)
-    std::vector<GrammarImage> gr_cache; long gr_stamp = 0, gr_uploads = 0; std::vector<SkwRowGrammar> gr_clip;
-    SkwSeqState* h_st = nullptr; SkwTokenOut* h_toks = nullptr; // pinned
-    int* h_row_live = nullptr; int* d_row_live = nullptr;      // per-row live flags in pinned host memory and their device-side address: k_dec_sample clears a row's flag itself,
-                                                               // so a step ends with no 4-byte copy kernel (4.2 us in the chain of every step) — the host reads the flags after the stream drains
-    int max_tok = 0;
-    // the prompt ([prev] + past text + sot / language / task) in one multi-row pass instead of one token per step; SKW_PROMPT_PASS=0 or skw_debug_set_prompt_pass(ctx, 0)
-    int prompt_pass_on = 1;
-    int prompt_xattn_mq_on = 1;      // the exact precision's prompt pass: the 16-queries-per-workgroup cross attention (skw_debug_set_prompt_xattn_mq; same bits either way)
-    int* pf_meta = nullptr; int pf_nseq = 0, pf_nq_max = 0;      // the pass's sequences on the device: [row0 | nq | slot] x max_batch (the multi-query cross attention of the f16_mfma prompt pass)
-    int rows_cap = 0; SkwSeqState* pf_st = nullptr;  // decode-step scratch rows (>= max_batch: the prompt pass runs one row per prompt token) and the prompt pass's per-token pseudo-states
-    int ln_stats_on = 1;                             // LayerNorm folded into the decode GEMMs (f16_mfma); SKW_DEC_LN_STATS=0 or skw_debug_set_ln_stats(ctx, 0): LayerNorm kernels
-    // profiling: rows of the step about to be launched that are still decoding (finished rows return at once in the attention kernels: their bytes are not booked)
-    int live_rows_hint = -1;
-    // the in-kernel launch clock of the decode step's cross attention (skw_ctx_kernel_clock): one SkwKClk per (row group, layer); cur_group: the group run_decoder_step is enqueuing
-    void* kclk = nullptr; int kclk_on = 0, kclk_khz = 0, cur_group = 0;
-    int* forced_dev = nullptr; SkwTraceStep* trace_dev = nullptr;   // [max_batch][max_tok], allocated by the first skw_full_batch_traced
-    skw_timing timing{};
-    int last_enc_B = 0;
-    // word timestamps (align_window, include/skw_align.h).  The workspace is allocated by the first call that aligns a clip (ensure_align_ws): P holds ONE layer's capture for a
-    // chunk of al_rows alignment rows — every head, n_audio_ctx keys, f32 — so its size does not depend on the batch; acc / x: the chunk's matrices (f64 sums, f32 result).
-    float* al_P = nullptr; double* al_acc = nullptr; float* al_x = nullptr; SkwAlignSeq* al_seqs = nullptr; int* al_times = nullptr; int al_rows = 0;      // al_times: jump | t0 | t1
-    // the alignment pass in flight (al_on: only inside align_window): what run_decoder_step's hook captures after an alignment layer's cross-query GEMM
-    bool al_on = false; const uint32_t* al_mask = nullptr;
-    const SkwAlignSeq* al_h_seqs = nullptr; int al_tap_base = 0, al_tap_next = 0;      // taps: the chunk's records on the host, the call's sequence numbering
-    int al_width = 7, al_nseq = 0, al_rows_now = 0, al_kw_max = 0, al_n_heads = 0, al_l_first = 0, al_l_last = 0;
-    struct WsEntry { const char* name; void** slot; size_t bytes; bool zero; bool is_float; };      // one workspace buffer: the field it fills and its size (skw_ctx_create)
-    std::vector<WsEntry> ws_table;
-};
+void skw_priv::poison_floats(void* p, size_t bytes) { if (g_alloc_poison && p) { (void)hipMemset(p, 0xFF, bytes); g_alloc_poisoned.fetch_add(1); } }
 struct SkwKClk;
 static SkwKClk* kclk_node(const skw_ctx* c, int g, int l);
 static int kclk_reset(skw_ctx* c);
-// name of the first workspace buffer whose pointer is null, or nullptr when every entry of the table is allocated
-static const char* ws_first_null(const skw_ctx* c) {
-    if (c->ws_table.empty()) return "(empty workspace table)";
-    for (const skw_ctx::WsEntry& e : c->ws_table) if (!*e.slot) return e.name;
-    return nullptr;
-}
-// every entry point that launches kernels starts here: a context whose table holds a null buffer never reaches a launch
-#define WS_READY(c) do { if (const char* nb_ = ws_first_null(c)) { snprintf((c)->errbuf, 512, "workspace buffer '%s' is not allocated", nb_); return -1; } } while (0)
 extern "C" const char* skw_ctx_last_error(const skw_ctx* c) { return c->errbuf; }
 // The q8 image of cross_kv = q8_0 (1.0625 bytes per element of cross K and V^T, every layer and slot) is allocated when it can first be used: the flag asks for q8_0 AND the
 // context runs f16_mfma — a context that stays in the exact precision, which ignores the flag, never pays for it.  Entered in the workspace table by name.
@@ -729,65 +235,10 @@ extern "C" void skw_ctx_free(skw_ctx* c) {
     delete c;
 }
 
-// ------------------------------------------------------------------ debug taps (encoder layer 0, natural layouts; enabled by skw_debug_enable)
-static std::map<std::string, std::vector<float>> g_taps; static bool g_taps_on = false;
-// host-side view of the fragment-order layouts (tests/test_cpu_layouts.py checks them without a GPU): element offset of the 16-byte chunk that holds (key, feat .. feat + 7) of cross K /
-// (feat, positions pos .. pos + 7) of cross V^T
-extern "C" long skw_layout_kfrag_off(int slot, int H, int Tpad, int key, int feat) { return skw_kfrag_off(slot, H, Tpad, key, feat); }
-extern "C" long skw_layout_vtfrag_off(int slot, int H, int Tpad, int feat, int pos) { return skw_vtfrag_off(slot, H, Tpad, feat, pos); }
-extern "C" int skw_layout_kperm(int k) { return skw_kperm(k); }
-// the q8 image of cross_kv = q8_0 (include/skw_kv8.h), in bytes: the int8 / the f16 block scale of K[key][feat] and of V[key][feat], and a slot's size
-extern "C" long skw_layout_kv8_kq_off(int slot, int H, int Tpad, int key, int feat) { return skw_kv8_kq_off(slot, H, Tpad, key, feat); }
-extern "C" long skw_layout_kv8_kd_off(int slot, int H, int Tpad, int key, int feat) { return skw_kv8_kd_off(slot, H, Tpad, key, feat); }
-extern "C" long skw_layout_kv8_vq_off(int slot, int H, int Tpad, int feat, int key) { return skw_kv8_vq_off(slot, H, Tpad, feat, key); }
-extern "C" long skw_layout_kv8_vd_off(int slot, int H, int Tpad, int feat, int key) { return skw_kv8_vd_off(slot, H, Tpad, feat, key); }
-extern "C" long skw_layout_kv8_slot_bytes(int H, int Tpad) { return skw_kv8_slot_bytes(H, Tpad); }
-extern "C" long skw_layout_afrag_off(int m, int p, int K) { return skw_afrag_off(m, p, K); }
-// tests: the fragment-order image of a host weight [N][K] (f16 bits), as the decode kernels read it (skw_make_wfrag)
-extern "C" int skw_debug_make_wfrag(const uint16_t* w_host, int N, int K, int perm, uint16_t* img_host) {
-    if (N <= 0 || K <= 0 || (K & 31)) return -1;
-    const size_t n_in = (size_t)N * K, n_out = (size_t)((N + 15) & ~15) * K;
-    half_t *dw = nullptr, *di = nullptr;
-    if (hipMalloc((void**)&dw, n_in * 2) != hipSuccess || hipMalloc((void**)&di, n_out * 2) != hipSuccess) { hipFree(dw); hipFree(di); return -2; }
-    int rc = 0;
-    if (hipMemcpy(dw, w_host, n_in * 2, hipMemcpyHostToDevice) != hipSuccess || hipMemset(di, 0xff, n_out * 2) != hipSuccess) rc = -3;
-    if (!rc) { skw_make_wfrag(dw, K, N & ~15, K, perm, di, nullptr);
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(img_host, di, (size_t)(N & ~15) * K * 2, hipMemcpyDeviceToHost) != hipSuccess) rc = -4; }
-    hipFree(dw); hipFree(di); return rc;
-}
-// tests: f16_mfma cross K / V^T as fragment-order images (one-pass cross attention) / as rows (two-phase kernel); takes effect at the next encoder pass
-extern "C" void skw_debug_set_kv_frag(skw_ctx* c, int on) { c->kv_frag_on = on != 0; }
-extern "C" void skw_debug_set_prompt_pass(skw_ctx* c, int on) { c->prompt_pass_on = on != 0; }     // tests: the prompt as one pass / one token per step
-// tests / tools: the exact precision's prompt pass with the multi-query cross attention (default) or the single-query kernel on every prompt row
-extern "C" void skw_debug_set_prompt_xattn_mq(skw_ctx* c, int on) { c->prompt_xattn_mq_on = on != 0; }
-extern "C" void skw_debug_set_ln_stats(skw_ctx* c, int on) { c->ln_stats_on = on != 0; }      // tests: the decode step with / without the LayerNorm launches (f16_mfma)
-extern "C" void skw_debug_enable(int on) { g_taps_on = on != 0; g_taps.clear(); }
-extern "C" long skw_debug_get(const char* name, float* out, size_t cap) {
-    auto it = g_taps.find(name); if (it == g_taps.end()) return -1; if (out && cap >= it->second.size()) memcpy(out, it->second.data(), it->second.size() * 4); return (long)it->second.size();
-}
+// the debug taps the phases below fill (tap() and the entry points that read them: with the test hooks at the end of this file)
 enum TapLayout { TAP_F32, TAP_F16_KPERM, TAP_HEADS, TAP_VT, TAP_F16_PLAIN };
-static void tap(skw_ctx* c, const char* name, const void* dev, int rows, int cols, TapLayout lay) {
-    if (!g_taps_on) return;
-    hipStreamSynchronize(c->stream);
-    std::vector<float>& o = g_taps[name]; o.assign((size_t)rows * cols, 0.f);
-    const int H = c->m->hp.n_audio_head, Tpad = c->Tpad;
-    if (lay == TAP_F32) { hipMemcpy(o.data(), dev, o.size() * 4, hipMemcpyDeviceToHost); return; }
-    if (lay == TAP_F16_PLAIN) {      // f16 rows in natural order; the tap holds the BIT PATTERNS as floats (exact: every value is below 2^16)
-        std::vector<uint16_t> h((size_t)rows * cols); hipMemcpy(h.data(), dev, h.size() * 2, hipMemcpyDeviceToHost);
-        for (size_t i = 0; i < h.size(); ++i) o[i] = (float)h[i];
-        return;
-    }
-    if (lay == TAP_F16_KPERM) {
-        std::vector<uint16_t> h((size_t)rows * cols); hipMemcpy(h.data(), dev, h.size() * 2, hipMemcpyDeviceToHost);
-        for (int r = 0; r < rows; ++r) for (int i = 0; i < cols; ++i) o[(size_t)r * cols + i] = skw_f16_to_f32(h[(size_t)r * cols + skw_kperm(i)]);
-    } else if (lay == TAP_HEADS) {   // [(h)*Tpad + i][kperm(d)] for batch 0
-        std::vector<uint16_t> h((size_t)H * Tpad * 64); hipMemcpy(h.data(), dev, h.size() * 2, hipMemcpyDeviceToHost);
-        for (int r = 0; r < rows; ++r) for (int n = 0; n < cols; ++n) o[(size_t)r * cols + n] = skw_f16_to_f32(h[((size_t)(n >> 6) * Tpad + r) * 64 + skw_kperm(n & 63)]);
-    } else {                          // V^T: [(h*64 + c)][kperm(key)] row stride Tpad
-        std::vector<uint16_t> h((size_t)H * 64 * Tpad); hipMemcpy(h.data(), dev, h.size() * 2, hipMemcpyDeviceToHost);
-        for (int r = 0; r < rows; ++r) for (int n = 0; n < cols; ++n) o[(size_t)r * cols + n] = skw_f16_to_f32(h[((size_t)n) * Tpad + skw_kperm(r)]);
-    }
-}
+static std::map<std::string, std::vector<float>> g_taps; static bool g_taps_on = false;
+static void tap(skw_ctx* c, const char* name, const void* dev, int rows, int cols, TapLayout lay);
 
 // ------------------------------------------------------------------ per-kernel-class profiling (HIP events on the engine stream)
 enum ProfClass { PC_GEMM = 0, PC_GEMM_SMALL, PC_ATTN_ENC, PC_LAYERNORM, PC_MEL, PC_DEC_ATTN, PC_DEC_SAMPLE, PC_OTHER, PC_DEC_XATTN, PC_DEC_CONSTRAIN, PC_ALIGN_QK,
@@ -2092,6 +1543,45 @@ extern "C" int skw_full_batch_traced(skw_ctx* c, const skw_full_params* p, const
                                      const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, skw_result* results) {
     return skw_full_batch_traced_context(c, p, pcm, n_samples, n_clips, pcm_on_device, forced_ids, n_forced, traces, nullptr, results);
 }
+extern "C" void skw_trace_free(skw_trace* t) { if (!t) return; free(t->steps); t->steps = nullptr; t->n = 0; }
+extern "C" void skw_result_free(skw_result* r) { if (!r) return; free(r->segments); free(r->tokens); free(r->text); memset(r, 0, sizeof *r); }
+
+// ================================================================== test and measurement hooks that drive the engine's own phases
+// (the hooks that run one kernel on caller-supplied operands are skw_hooks.hip's)
+// ------------------------------------------------------------------ debug taps (encoder layer 0, natural layouts; enabled by skw_debug_enable)
+// tests: f16_mfma cross K / V^T as fragment-order images (one-pass cross attention) / as rows (two-phase kernel); takes effect at the next encoder pass
+extern "C" void skw_debug_set_kv_frag(skw_ctx* c, int on) { c->kv_frag_on = on != 0; }
+extern "C" void skw_debug_set_prompt_pass(skw_ctx* c, int on) { c->prompt_pass_on = on != 0; }     // tests: the prompt as one pass / one token per step
+// tests / tools: the exact precision's prompt pass with the multi-query cross attention (default) or the single-query kernel on every prompt row
+extern "C" void skw_debug_set_prompt_xattn_mq(skw_ctx* c, int on) { c->prompt_xattn_mq_on = on != 0; }
+extern "C" void skw_debug_set_ln_stats(skw_ctx* c, int on) { c->ln_stats_on = on != 0; }      // tests: the decode step with / without the LayerNorm launches (f16_mfma)
+extern "C" void skw_debug_enable(int on) { g_taps_on = on != 0; g_taps.clear(); }
+extern "C" long skw_debug_get(const char* name, float* out, size_t cap) {
+    auto it = g_taps.find(name); if (it == g_taps.end()) return -1; if (out && cap >= it->second.size()) memcpy(out, it->second.data(), it->second.size() * 4); return (long)it->second.size();
+}
+static void tap(skw_ctx* c, const char* name, const void* dev, int rows, int cols, TapLayout lay) {
+    if (!g_taps_on) return;
+    hipStreamSynchronize(c->stream);
+    std::vector<float>& o = g_taps[name]; o.assign((size_t)rows * cols, 0.f);
+    const int H = c->m->hp.n_audio_head, Tpad = c->Tpad;
+    if (lay == TAP_F32) { hipMemcpy(o.data(), dev, o.size() * 4, hipMemcpyDeviceToHost); return; }
+    if (lay == TAP_F16_PLAIN) {      // f16 rows in natural order; the tap holds the BIT PATTERNS as floats (exact: every value is below 2^16)
+        std::vector<uint16_t> h((size_t)rows * cols); hipMemcpy(h.data(), dev, h.size() * 2, hipMemcpyDeviceToHost);
+        for (size_t i = 0; i < h.size(); ++i) o[i] = (float)h[i];
+        return;
+    }
+    if (lay == TAP_F16_KPERM) {
+        std::vector<uint16_t> h((size_t)rows * cols); hipMemcpy(h.data(), dev, h.size() * 2, hipMemcpyDeviceToHost);
+        for (int r = 0; r < rows; ++r) for (int i = 0; i < cols; ++i) o[(size_t)r * cols + i] = skw_f16_to_f32(h[(size_t)r * cols + skw_kperm(i)]);
+    } else if (lay == TAP_HEADS) {   // [(h)*Tpad + i][kperm(d)] for batch 0
+        std::vector<uint16_t> h((size_t)H * Tpad * 64); hipMemcpy(h.data(), dev, h.size() * 2, hipMemcpyDeviceToHost);
+        for (int r = 0; r < rows; ++r) for (int n = 0; n < cols; ++n) o[(size_t)r * cols + n] = skw_f16_to_f32(h[((size_t)(n >> 6) * Tpad + r) * 64 + skw_kperm(n & 63)]);
+    } else {                          // V^T: [(h*64 + c)][kperm(key)] row stride Tpad
+        std::vector<uint16_t> h((size_t)H * 64 * Tpad); hipMemcpy(h.data(), dev, h.size() * 2, hipMemcpyDeviceToHost);
+        for (int r = 0; r < rows; ++r) for (int n = 0; n < cols; ++n) o[(size_t)r * cols + n] = skw_f16_to_f32(h[((size_t)n) * Tpad + skw_kperm(r)]);
+    }
+}
+
 // Test hook (tests/test_gpu_logit_rules.py): K11 on its own.  n_rows decoders whose tokens sampled so far in their window are hist[r][0 .. n_hist[r]) meet
 // caller-supplied logits; ONE launch of the sampler (form 0: the one the decode step uses; form 1: the streaming kernel, which leaves the filtered row in
 // memory) makes each row's next decision.  has_ts / seek_delta / result_len are replayed from the history by the token loop's update rule, as
@@ -2233,8 +1723,6 @@ extern "C" int skw_debug_sample_rows_ex(skw_ctx* c, const skw_full_params* p, in
     if (!p || !ex) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_ex: params and ex are required"); return -1; }
     return debug_sample_rows_impl(c, p, per_row ? p : nullptr, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out, nullptr, ex);
 }
-extern "C" void skw_trace_free(skw_trace* t) { if (!t) return; free(t->steps); t->steps = nullptr; t->n = 0; }
-extern "C" void skw_result_free(skw_result* r) { if (!r) return; free(r->segments); free(r->tokens); free(r->text); memset(r, 0, sizeof *r); }
 
 // ------------------------------------------------------------------ stage taps
 __global__ void k_transpose_mel(const float* mel, int n_len, int n_mel, float* out) {   // [frame][mel] -> [mel][frame]
@@ -2318,794 +1806,6 @@ extern "C" int skw_decode_logits(skw_ctx* c, const int32_t* tokens, int n_tokens
     HIPCHK(hipMemcpyAsync(logits, c->logits, sizeof(float) * c->m->hp.n_vocab, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return 0;
 }
 
-// ------------------------------------------------------------------ arithmetic-contract probes (tests/test_gpu_math.py)
-__global__ void k_math_probe(int kind, const float* in, float* out, long n, const uint16_t* gelu_tab) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x; if (i >= n) return;
-    float x = in[i], y;
-    if (kind == 0) y = skw_expf(x);
-    else if (kind == 1) y = skw_logf(x);
-    else if (kind == 2) y = (float)((half_t)x);
-    else if (kind == 3) y = skw_round_f16(x);
-    else if (kind == 4) { if (x <= -10.0f) y = 0.0f; else if (x >= 10.0f) y = x; else { half_t h = (half_t)x; uint16_t b = __builtin_bit_cast(uint16_t, h);
-    uint16_t o = gelu_tab[b]; y = (float)__builtin_bit_cast(half_t, o); } }
-    else if (kind == 5) y = 1.0f / sqrtf(x + 1e-5f);
-    else if (kind == 6) y = (float)(1.0 / (double)x);
-    else y = (float)log10((double)x);
-    out[i] = y;
-}
-extern "C" int skw_debug_math(skw_ctx* c, int kind, const float* in, float* out, long n) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    float *di = nullptr, *dout = nullptr; HIPCHK(hipMalloc((void**)&di, n * 4)); HIPCHK(hipMalloc((void**)&dout, n * 4));
-    HIPCHK(hipMemcpy(di, in, n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_math_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, kind, di, dout, n, c->m->gelu_tab);
-    HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost)); hipFree(di); hipFree(dout); return 0;
-}
-
-// measurement hook (tools/gemm16_probe.py): one f16-MFMA GEMM of the given shape on scratch buffers, timed with HIP events on the engine stream.
-// probe: bit 0 no K-loop DMA, bit 1 no MFMAs, bit 2 no epilogue stores; epi: EPI_* of skw_kernels.h (n_ctx / H / Tpad taken from the model)
-extern "C" int skw_debug_gemm16(skw_ctx* c, int M, int N, int K, int epi, int probe, int iters, float* ms_per_launch) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    half_t *A = nullptr, *W = nullptr; void* C = nullptr; float *bias = nullptr, *res = nullptr;
-    const size_t cbytes = (size_t)M * N * 4 + (size_t)64 * c->Tpad * N;
-    // probe bits 12-19 = n (decode shapes): the launches walk n copies of W (n x N x K x 2 bytes > the 256 MB Infinity Cache: every launch finds its weights in HBM, as a decode step does)
-    const int wcycle = M <= 64 ? std::max(1, (probe >> 12) & 255) : 1; if (M <= 64) probe &= 0xfff;      // (big shapes: bits 10-16 are k_gemm16w's measurement hooks)
-    HIPCHK(hipMalloc((void**)&A, (size_t)M * K * 2)); HIPCHK(hipMalloc((void**)&W, (size_t)N * K * 2 * wcycle));
-    HIPCHK(hipMalloc(&C, cbytes)); HIPCHK(hipMalloc((void**)&bias, (size_t)std::max(M, N) * 4)); HIPCHK(hipMalloc((void**)&res, (size_t)M * N * 4));
-    { std::vector<uint16_t> h((size_t)std::max(M, N) * K); uint32_t x = 12345; for (auto& v : h) { x = x * 1664525u + 1013904223u; v = skw_f32_to_f16(((x >> 8) & 0xffff) / 65536.0f - 0.5f); }
-      HIPCHK(hipMemcpy(A, h.data(), (size_t)M * K * 2, hipMemcpyHostToDevice));
-      for (int w = 0; w < wcycle; ++w) HIPCHK(hipMemcpy(W + (size_t)w * N * K, h.data(), (size_t)N * K * 2, hipMemcpyHostToDevice)); }
-    HIPCHK(hipMemset(bias, 0, (size_t)std::max(M, N) * 4)); HIPCHK(hipMemset(res, 0, (size_t)M * N * 4));
-    SkwGemmArgs a{}; a.A = A; a.lda = K; a.W = W; a.ldw = K; a.M = M; a.N = N; a.K = K; a.C = C; a.ldc = N; a.bias = bias; a.epi = epi; a.scale = 1.0f; a.probe = probe;
-    a.gelu_tab = c->m->gelu_tab; a.pe = res; a.n_ctx = c->m->hp.n_audio_ctx; a.H = N / 64; a.Tpad = c->Tpad; if (epi == EPI_F32 && N < 8192) { a.res = res; a.ldres = N; }
-    if (N >= 8192) a.bias = nullptr;                               // the vocabulary projection: no bias, no residual
-    hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    const bool small = M <= 64;                                      // the decode-step form: a chain of dependent launches, so the figure includes the kernel boundary
-    if (small && epi == EPI_DEC_QKV) { a.C2 = res; a.C3 = res; a.ldc2 = N; a.n_ctx = N / 3; a.ldc = N / 3; }
-    if (small && (probe & 64) && !(M & 15)) { a.a_frag = 1; a.probe &= ~64; }      // probe bit 6 (decode shapes, timing only): the activations addressed as a fragment-order image
-    half_t* Wfrag = nullptr;      // probe bit 5 (decode shapes): the weights as fragment-order images (one per W copy of the cycle), what the step's launches read
-    if (small && (probe & 32) && !(N & 15)) { HIPCHK(hipMalloc((void**)&Wfrag, (size_t)N * K * 2 * wcycle));
-    for (int w = 0; w < wcycle; ++w) skw_make_wfrag(W + (size_t)w * N * K, K, N, K, epi == EPI_GELU_F16_KPERM, Wfrag + (size_t)w * N * K, c->stream);
-    a.Wf = Wfrag; a.probe &= ~32; }
-    // probe bit 9 (big shapes): the weights also as a fragment-order image and no measurement hooks — the launch takes k_gemm16w, as the encoder's do
-    if (!small && (probe & 512) && !(N & 15)) {
-        HIPCHK(hipMalloc((void**)&Wfrag, (size_t)N * K * 2));
-        skw_make_wfrag(W, K, N, K, epi == EPI_GELU_F16_KPERM || epi == EPI_HEADS_F16, Wfrag, c->stream);
-        a.Wf = Wfrag; a.probe = probe & ~1023;
-    }
-    for (int i = 0; i < 3; ++i) { if (small) skw_gemm16_small(a, c->stream); else skw_gemm16(a, c->stream); }
-    HIPCHK(hipEventRecord(e0, c->stream));
-    // (a launch that also touched the NEXT launch's copy of W — LDS-DMA into a scratch slab, so the bytes sit in the Infinity Cache when wanted — measured no gain:
-    //  7.63 vs 7.66 us for the QKV shape.  The cold-weight cost is the transfer into the consuming XCD's L2, ~1 us per 3.5 MB whether it starts in HBM or in the Infinity Cache.)
-    for (int i = 0; i < iters; ++i) { a.W = W + (size_t)(i % wcycle) * N * K;
-    if (Wfrag) a.Wf = Wfrag + (size_t)(i % wcycle) * N * K; if (small) skw_gemm16_small(a, c->stream); else skw_gemm16(a, c->stream); }
-    HIPCHK(hipEventRecord(e1, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_per_launch = ms / iters;
-    hipEventDestroy(e0); hipEventDestroy(e1); hipFree(A); hipFree(W); hipFree(Wfrag); hipFree(C); hipFree(bias); hipFree(res);
-    return 0;
-}
-
-// tests (tests/test_gpu_gemm16w.py; the regression cover of the round-4 k_gemm16w fault): ONE product on seeded operands through k_gemm16w — the encoder's GEMM, weights from a
-// fragment-order image, two memory queues counted by hand — and through k_gemm16 (both operands through LDS), every output byte compared.  epi: EPI_* of skw_kernels.h;
-// frag: EPI_F16_PLAIN / EPI_VT_F16 write the fragment-order cross K / V^T image; n_ctx / Tpad: rows per clip of the per-clip layouts (M must be a multiple of n_ctx for them);
-// ngroups: GEMM16W_NGROUPS for the k_gemm16w launch; with_res: EPI_F32 adds a residual.  Returns the number of differing bytes (0 = bit-identical), -2 when skw_gemm16 would not
-// take k_gemm16w for this geometry (nothing compared), -1 on error.
-extern "C" long skw_debug_gemm16_compare(skw_ctx* c, int M, int N, int K, int epi, int frag, int n_ctx, int Tpad, int ngroups, int with_res) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    if (M < 1 || N < 16 || (N & 15) || (K & 63) || n_ctx < 1 || (Tpad & 31) || Tpad < n_ctx) { snprintf(errbuf, 512, "skw_debug_gemm16_compare: bad geometry"); return -1; }
-    const bool per_clip = epi == EPI_HEADS_F16 || epi == EPI_VT_F16 || epi == EPI_GELU_F16_KPERM_ROWPAD || epi == EPI_CONV2 || frag;
-    if (per_clip && M % n_ctx) { snprintf(errbuf, 512, "skw_debug_gemm16_compare: M must be whole clips for this epilogue"); return -1; }
-    if ((epi == EPI_HEADS_F16 || epi == EPI_VT_F16 || frag) && (N & 63)) { snprintf(errbuf, 512, "skw_debug_gemm16_compare: N must be whole heads for this epilogue"); return -1; }
-    const size_t cbytes = ((size_t)(M / n_ctx + 2) * (Tpad + 2) * N + (size_t)M * N) * 4 + 4096;
-    half_t *A = nullptr, *W = nullptr, *Wf = nullptr; char *C1 = nullptr, *C2 = nullptr; float *bias = nullptr, *res = nullptr, *pe = nullptr;
-    auto cleanup = [&]() { hipFree(A); hipFree(W); hipFree(Wf); hipFree(C1); hipFree(C2); hipFree(bias); hipFree(res); hipFree(pe); };
-    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_gemm16_compare: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
-    if (!chk(hipMalloc((void**)&A, (size_t)M * K * 2)) || !chk(hipMalloc((void**)&W, (size_t)N * K * 2)) || !chk(hipMalloc((void**)&Wf, (size_t)N * K * 2)) || !chk(hipMalloc((void**)&C1, cbytes)) ||
-        !chk(hipMalloc((void**)&C2, cbytes)) || !chk(hipMalloc((void**)&bias, (size_t)std::max(M, N) * 4)) || !chk(hipMalloc((void**)&res, (size_t)M * N * 4)) ||
-        !chk(hipMalloc((void**)&pe, (size_t)n_ctx * N * 4))) return -1;
-    {   // seeded operands: values of order 1 / sqrt(K) so that sums stay well inside f16's range after the epilogue
-        uint32_t x = 0x9e3779b9u ^ (uint32_t)(M * 31 + N * 17 + K * 7 + epi);
-        auto rnd = [&]() { x = x * 1664525u + 1013904223u; return ((x >> 8) & 0xffff) / 65536.0f - 0.5f; };
-        const float sc = 2.0f / sqrtf((float)K);
-        std::vector<uint16_t> h((size_t)std::max(M, N) * K);
-        for (auto& v : h) v = skw_f32_to_f16(rnd() * sc);
-        if (!chk(hipMemcpy(A, h.data(), (size_t)M * K * 2, hipMemcpyHostToDevice))) return -1;
-        for (auto& v : h) v = skw_f32_to_f16(rnd() * 2.0f);
-        if (!chk(hipMemcpy(W, h.data(), (size_t)N * K * 2, hipMemcpyHostToDevice))) return -1;
-        std::vector<float> f((size_t)std::max((size_t)M * N, (size_t)n_ctx * N));
-        for (auto& v : f) v = rnd();
-        if (!chk(hipMemcpy(res, f.data(), (size_t)M * N * 4, hipMemcpyHostToDevice)) || !chk(hipMemcpy(pe, f.data(), (size_t)n_ctx * N * 4, hipMemcpyHostToDevice)) ||
-            !chk(hipMemcpy(bias, f.data(), (size_t)std::max(M, N) * 4, hipMemcpyHostToDevice))) return -1;
-    }
-    const bool perm = epi == EPI_F16_KPERM || epi == EPI_GELU_F16_KPERM || epi == EPI_GELU_F16_KPERM_ROWPAD || epi == EPI_HEADS_F16;
-    skw_make_wfrag(W, K, N, K, perm ? 1 : 0, Wf, c->stream);
-    SkwGemmArgs a{}; a.A = A; a.lda = K; a.W = W; a.ldw = K; a.Wf = Wf; a.M = M; a.N = N; a.K = K; a.ldc = N; a.bias = bias; a.epi = epi; a.scale = 0.125f;
-    a.has_scale = (epi == EPI_F16_KPERM || epi == EPI_HEADS_F16 || epi == EPI_F16_PLAIN) ? 1 : 0;
-    a.gelu_tab = c->m->gelu_tab; a.pe = pe; a.n_ctx = per_clip ? n_ctx : 0; a.H = N / 64; a.Tpad = Tpad; a.frag = frag;
-    if (epi == EPI_F32 && with_res) { a.res = res; a.ldres = N; }
-    if (!skw_gemm16_takes_w(a)) { cleanup(); return -2; }
-    (void)skw_sw(0);
-    const int ng_was = g_sw_val[SW_GEMM16W_NGROUPS], w_was = g_sw_val[SW_GEMM16W];
-    if (!chk(hipMemsetAsync(C1, 0xAB, cbytes, c->stream)) || !chk(hipMemsetAsync(C2, 0xAB, cbytes, c->stream))) return -1;
-    g_sw_val[SW_GEMM16W] = 1; g_sw_val[SW_GEMM16W_NGROUPS] = ngroups; a.C = C1; skw_gemm16(a, c->stream);
-    g_sw_val[SW_GEMM16W] = 0; a.C = C2; skw_gemm16(a, c->stream);
-    g_sw_val[SW_GEMM16W] = w_was; g_sw_val[SW_GEMM16W_NGROUPS] = ng_was;
-    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError())) return -1;
-    std::vector<char> h1(cbytes), h2(cbytes);
-    if (!chk(hipMemcpy(h1.data(), C1, cbytes, hipMemcpyDeviceToHost)) || !chk(hipMemcpy(h2.data(), C2, cbytes, hipMemcpyDeviceToHost))) return -1;
-    long diff = 0, written = 0;
-    for (size_t i = 0; i < cbytes; ++i) { diff += h1[i] != h2[i]; written += (unsigned char)h2[i] != 0xAB; }
-    cleanup();
-    if (written < (long)M * N) { snprintf(errbuf, 512, "skw_debug_gemm16_compare: only %ld bytes written for %d x %d outputs", written, M, N); return -1; }
-    return diff;
-}
-
-// tests (tests/test_gpu_mfma_model.py): P independent v_mfma_f32_16x16x32_f16 instructions — A: P x [16][32] f16 (row i, slot k), B: P x [32][16] f16 (slot k, column j), C / D: P x [16][16] f32 —
-// what the committed hardware vectors (tests/golden/mfma_f16_hw_vectors.npz) were taken with and are re-taken with on every GPU run
-__global__ void k_debug_mfma16x32(const half_t* A, const half_t* B, const float* C, float* D) {
-    const int p = blockIdx.x, l = threadIdx.x, r16 = l & 15, g = l >> 4;
-    const half_t* a = A + (size_t)p * 512; const half_t* b = B + (size_t)p * 512; const float* c = C + (size_t)p * 256; float* d = D + (size_t)p * 256;
-    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    f16x8 fa, fb;
-    for (int e = 0; e < 8; ++e) { fa[e] = a[r16 * 32 + 8 * g + e]; fb[e] = b[(8 * g + e) * 16 + r16]; }      // lane (row / column r16, group g) holds slots 8 g .. 8 g + 7
-    f32x4 acc; for (int r = 0; r < 4; ++r) acc[r] = c[(4 * g + r) * 16 + r16];
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa, fb, acc, 0, 0, 0);
-    for (int r = 0; r < 4; ++r) d[(4 * g + r) * 16 + r16] = acc[r];
-}
-extern "C" int skw_debug_mfma16x32(skw_ctx* c, long P, const uint16_t* A_host, const uint16_t* B_host, const float* C_host, float* D_host) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    if (P < 1 || P > (1 << 20)) { snprintf(errbuf, 512, "skw_debug_mfma16x32: bad problem count"); return -1; }
-    char* buf = nullptr;
-    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_mfma16x32: %s", hipGetErrorString(e)); hipFree(buf); return false; } return true; };
-    if (!chk(hipMalloc((void**)&buf, (size_t)P * 4096))) return -1;
-    half_t* A = (half_t*)buf; half_t* B = (half_t*)(buf + P * 1024); float* C = (float*)(buf + P * 2048); float* D = (float*)(buf + P * 3072);
-    if (!chk(hipMemcpy(A, A_host, P * 1024, hipMemcpyHostToDevice)) || !chk(hipMemcpy(B, B_host, P * 1024, hipMemcpyHostToDevice))) return -1;
-    if (!chk(hipMemcpy(C, C_host, P * 1024, hipMemcpyHostToDevice))) return -1;
-    hipLaunchKernelGGL(k_debug_mfma16x32, dim3((unsigned)P), dim3(64), 0, c->stream, A, B, C, D);
-    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(D_host, D, P * 1024, hipMemcpyDeviceToHost))) return -1;
-    hipFree(buf);
-    return 0;
-}
-// tests (tests/test_gpu_mfma_model.py): C = A . W^T through one of the f16_mfma GEMM kernels, plain f32 epilogue (no bias, no residual), operands given as f16 bit patterns in the
-// kernels' memory order ([M][K] and [N][K], K axis as the kernels load it) — to be compared bit for bit with oracle/'s restatement of the matrix cores (skwo_gemm_f16mfma).
-// kernel: 0 = k_gemm16w (weights from a fragment-order image), 1 = k_gemm16 (both operands through LDS), 2 = the decode step's product: k_gemm16_small (four waves split K) for N < 8192,
-// k_gemm16_vocab (one wave chains the whole K) from there on
-extern "C" int skw_debug_gemm16_out(skw_ctx* c, int kernel, int M, int N, int K, const uint16_t* A_host, const uint16_t* W_host, float* C_host) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    if (M < 1 || (N & 15) || (K & 127) || kernel < 0 || kernel > 2) { snprintf(errbuf, 512, "skw_debug_gemm16_out: bad geometry"); return -1; }
-    half_t *A = nullptr, *W = nullptr, *Wf = nullptr; float* C = nullptr;
-    auto cleanup = [&]() { hipFree(A); hipFree(W); hipFree(Wf); hipFree(C); };
-    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_gemm16_out: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
-    if (!chk(hipMalloc((void**)&A, (size_t)M * K * 2)) || !chk(hipMalloc((void**)&W, (size_t)N * K * 2)) || !chk(hipMalloc((void**)&Wf, (size_t)N * K * 2))) return -1;
-    if (!chk(hipMalloc((void**)&C, (size_t)M * N * 4)) || !chk(hipMemset(C, 0xAB, (size_t)M * N * 4))) return -1;
-    if (!chk(hipMemcpy(A, A_host, (size_t)M * K * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(W, W_host, (size_t)N * K * 2, hipMemcpyHostToDevice))) return -1;
-    skw_make_wfrag(W, K, N, K, 0, Wf, c->stream);
-    SkwGemmArgs a{}; a.A = A; a.lda = K; a.W = W; a.ldw = K; a.M = M; a.N = N; a.K = K; a.C = C; a.ldc = N; a.epi = EPI_F32; a.scale = 1.0f;
-    (void)skw_sw(0);
-    const int w_was = g_sw_val[SW_GEMM16W];
-    if (kernel == 2) { a.Wf = Wf; if (!skw_gemm16_small(a, c->stream)) { snprintf(errbuf, 512, "skw_debug_gemm16_out: k_gemm16_small does not take this geometry"); cleanup(); return -1; } }
-    else {
-        a.Wf = kernel == 0 ? Wf : nullptr; g_sw_val[SW_GEMM16W] = kernel == 0 ? 1 : 0;
-        if (kernel == 0 && !skw_gemm16_takes_w(a)) { g_sw_val[SW_GEMM16W] = w_was; snprintf(errbuf, 512, "skw_debug_gemm16_out: k_gemm16w does not take this geometry"); cleanup(); return -1; }
-        skw_gemm16(a, c->stream); g_sw_val[SW_GEMM16W] = w_was;
-    }
-    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(C_host, C, (size_t)M * N * 4, hipMemcpyDeviceToHost))) return -1;
-    cleanup();
-    return 0;
-}
-
-// The packing the attention hooks below share: natural-order f16 bit patterns -> what a kernel reads.  Q [n_slots][n_ctx][H*64] into per-head rows of stride Tpad (qheads; a plain
-// Q is copied as it stands, q.size() halves), K / V [n_slots][n_ctx][H*64] into per-head rows (kheads), the fragment-order images (kfrag / vfrag), plain rows (K otherwise; vrows) or
-// V^T per head in kperm key order (V otherwise).  q / k / v arrive sized and filled with the caller's pad patterns; only keys below fill_from[slot] are written.
-struct AttnHookLayout { int qheads, kheads, kfrag, vrows, vfrag; };
-static void attn_hook_pack(const AttnHookLayout& L, int H, int n_ctx, int n_slots, const uint16_t* Q_host, const uint16_t* K_host, const uint16_t* V_host, const int* fill_from,
-                           std::vector<uint16_t>& q, std::vector<uint16_t>& k, std::vector<uint16_t>& v) {
-    const int d = H * 64, Tpad = (n_ctx + 31) & ~31;
-    if (L.qheads) { for (int s = 0; s < n_slots; ++s) for (int i = 0; i < n_ctx; ++i) for (int n = 0; n < d; ++n)
-                        q[(((size_t)s * H + (n >> 6)) * Tpad + i) * 64 + skw_kperm(n & 63)] = Q_host[((size_t)s * n_ctx + i) * d + n]; }
-    else memcpy(q.data(), Q_host, q.size() * 2);
-    for (int s = 0; s < n_slots; ++s) for (int i = 0; i < fill_from[s]; ++i) for (int n = 0; n < d; ++n) {
-        const uint16_t kv = K_host[((size_t)s * n_ctx + i) * d + n], vv = V_host[((size_t)s * n_ctx + i) * d + n];
-        const int p = skw_kperm(i);
-        if (L.kheads) k[(((size_t)s * H + (n >> 6)) * Tpad + i) * 64 + skw_kperm(n & 63)] = kv;
-        else if (L.kfrag) k[skw_kfrag_off(s, H, Tpad, i, n & ~7) + (n & 7)] = kv;
-        else k[((size_t)s * n_ctx + i) * d + n] = kv;
-        if (L.vrows) v[((size_t)s * n_ctx + i) * d + n] = vv;
-        else if (L.vfrag) v[skw_vtfrag_off(s, H, Tpad, n, p & ~7) + (p & 7)] = vv;
-        else v[((size_t)s * d + n) * Tpad + p] = vv;
-    }
-}
-
-// tests (tests/test_gpu_attn16.py): one f16_mfma attention launcher on host-supplied operands, to be held to a float64 softmax(Q K^T) V kernel by kernel.  Q [rows][H*64], K / V
-// [slot][n_ctx][H*64] arrive as f16 bit patterns in NATURAL order; this packs them into what the kernel reads (per-head rows of stride Tpad, V^T, the fragment-order images), launches
-// through the public launcher (the template dispatch is part of what is tested) and returns the output un-permuted as f32 [rows][H*64].
-//   form 0  skw_attn_encoder16: Q is [slot][n_ctx][H*64]; slot_k null: out rows = n_slots * n_ctx; given: n_slots * out_rows (out_rows 0: n_ctx)
-//   form 1  skw_xattn_prefill16: n_seq sequences (row0, nq, slot), frag = flags & 1, ofrag = flags & 2, slot_k null or [n_slots]
-//   form 2  skw_dec_cross_attn_vt, pv16 = 2 (one pass over the fragment-order images), ofrag = flags & 2;   form 3  the same, pv16 = 1 (two phases over the row layouts)
-//           active / seq / count (= n_keys) are [rows] or null and reach the kernel as fields of a SkwSeqState array (its stride is the launchers' contract)
-//   form 4  skw_dec_self_attn, fastv = 1: K / V are the caches [slot][n_ctx = n_text_ctx][H*64], count = pos [rows] (required), ofrag = flags & 2
-// Pad: every K position of slot s from fill_from[s] up (to Tpad where the layout has a Tpad) holds the bit pattern k_pad, every V position v_pad — what the kernel must not use is the
-// caller's to poison.  The output buffer starts as `sentinel` in every half, so rows the kernel must leave alone (inactive, past nq, past a slot's queries) are visible.
-extern "C" int skw_debug_attn16(skw_ctx* c, int form, int H, int n_ctx, int n_slots, int rows, int flags, int out_rows, const uint16_t* Q_host, const uint16_t* K_host,
-                                const uint16_t* V_host, const int* fill_from, int k_pad, int v_pad, const int* slot_k, int n_seq, const int* row0, const int* nq, const int* slot,
-                                const int* active, const int* seq, const int* count, int sentinel, float* out_host) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_attn16: %s", what); return -1; };
-    if (form < 0 || form > 4 || H < 1 || H > 32 || n_ctx < 1 || n_ctx > 4096 || n_slots < 1 || n_slots > 64 || rows < 1 || rows > 65536 || !fill_from) return bad("bad geometry");
-    const int d = H * 64, Tpad = (n_ctx + 31) & ~31, frag = flags & 1, ofrag = (flags >> 1) & 1;
-    for (int s = 0; s < n_slots; ++s) if (fill_from[s] < 0 || fill_from[s] > n_ctx) return bad("fill_from outside [0, n_ctx]");
-    int orows = rows, nq_max = 0;
-    if (form == 0) {
-        orows = n_slots * (slot_k && out_rows ? out_rows : n_ctx);
-        if (slot_k) for (int s = 0; s < n_slots; ++s) if ((out_rows ? out_rows : n_ctx) < std::min(n_ctx, std::max(1, slot_k[s]))) return bad("out_rows below a slot's query count");
-        if (ofrag || frag) return bad("the encoder form has no frag / ofrag");
-    } else if (form == 1) {
-        if (n_seq < 1 || n_seq > 64 || !row0 || !nq || !slot) return bad("the prompt pass needs row0 / nq / slot");
-        for (int i = 0; i < n_seq; ++i) {
-            if (row0[i] < 0 || nq[i] < 0 || row0[i] + nq[i] > rows || slot[i] < 0 || slot[i] >= n_slots) return bad("a sequence's rows or slot lie outside the buffers");
-            nq_max = std::max(nq_max, nq[i]);
-        }
-        if (nq_max < 1) return bad("no queries");
-    } else {
-        if (form == 3 && n_ctx > 24 * 64) return bad("the two-phase kernel holds at most 1536 keys");
-        if (form == 4 && (n_ctx > 7 * 64 || !count)) return bad("the self-attention form needs pos and n_text_ctx <= 448");
-        if (form == 4 && !skw_sw(SW_DEC_ATTN_FASTV)) return bad("SKW_DEC_ATTN_FASTV is off: the launcher would not reach the FASTV form");
-        if (frag || (ofrag && form == 3)) return bad("flag does not apply to this form");
-        for (int b = 0; b < rows; ++b) {
-            const int s = seq ? seq[b] : b;
-            if (s < 0 || s >= n_slots) return bad("a row's sequence lies outside the slots");
-            if (form == 4 && (count[b] < 0 || count[b] >= n_ctx)) return bad("pos outside the cache");
-        }
-    }
-    const int kfrag = (form == 1 && frag) || form == 2, vfrag = kfrag, kheads = form == 0, vrows = form == 4;      // which layouts this form reads
-    const int kkeys = (kfrag || kheads) ? Tpad : n_ctx, vkeys = vrows ? n_ctx : Tpad;
-    const size_t nQ = form == 0 ? (size_t)n_slots * Tpad * d : (size_t)rows * d, nK = (size_t)n_slots * kkeys * d, nV = (size_t)n_slots * vkeys * d;
-    const size_t nO = (size_t)(ofrag ? (orows + 15) & ~15 : orows) * d;
-    std::vector<uint16_t> q(nQ, (uint16_t)k_pad), k(nK, (uint16_t)k_pad), v(nV, (uint16_t)v_pad), o(nO, (uint16_t)sentinel);
-    attn_hook_pack(AttnHookLayout{form == 0, kheads, kfrag, vrows, vfrag}, H, n_ctx, n_slots, Q_host, K_host, V_host, fill_from, q, k, v);
-    std::vector<SkwSeqState> st(rows); memset((void*)st.data(), 0, sizeof(SkwSeqState) * rows);
-    if (form >= 2) for (int b = 0; b < rows; ++b) {
-        st[b].active = active ? active[b] : 1; st[b].pad = seq ? seq[b] : b; st[b].cur_pos = form == 4 ? count[b] : 0; st[b].n_keys = (form != 4 && count) ? count[b] : 0;
-    }
-    half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr; SkwSeqState* dst = nullptr; int* dmeta = nullptr;
-    auto cleanup = [&]() { hipFree(dq); hipFree(dk); hipFree(dv); hipFree(dout); hipFree(dst); hipFree(dmeta); };
-    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_attn16: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
-    if (!chk(hipMalloc((void**)&dq, nQ * 2)) || !chk(hipMalloc((void**)&dk, nK * 2)) || !chk(hipMalloc((void**)&dv, nV * 2)) || !chk(hipMalloc((void**)&dout, nO * 2))) return -1;
-    if (!chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * rows)) || !chk(hipMalloc((void**)&dmeta, sizeof(int) * (3 * 64 + 64)))) return -1;
-    if (!chk(hipMemcpy(dq, q.data(), nQ * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dk, k.data(), nK * 2, hipMemcpyHostToDevice))) return -1;
-    if (!chk(hipMemcpy(dv, v.data(), nV * 2, hipMemcpyHostToDevice))) return -1;
-    if (!chk(hipMemcpy(dout, o.data(), nO * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * rows, hipMemcpyHostToDevice))) return -1;
-    int meta[4 * 64] = {0};      // row0 | nq | slot | slot_k
-    if (form == 1) for (int i = 0; i < n_seq; ++i) { meta[i] = row0[i]; meta[64 + i] = nq[i]; meta[128 + i] = slot[i]; }
-    if (slot_k) for (int s = 0; s < n_slots; ++s) meta[192 + s] = slot_k[s];
-    if (!chk(hipMemcpy(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice))) return -1;
-    const int* dslot_k = slot_k ? dmeta + 192 : nullptr;
-    if (form == 0) skw_attn_encoder16(dq, dk, dv, dout, d, n_slots, H, n_ctx, Tpad, c->stream, dslot_k, out_rows);
-    else if (form == 1) skw_xattn_prefill16(dq, dk, dv, dout, n_seq, nq_max, dmeta, dmeta + 64, dmeta + 128, H, d, n_ctx, Tpad, c->stream, frag, ofrag, dslot_k);
-    else if (form == 4) skw_dec_self_attn(dq, dk, dv, &dst[0].cur_pos, rows, H, d, n_ctx, dout, active ? &dst[0].active : nullptr, c->stream, 0, SkwQ8Out{nullptr, nullptr, nullptr, 0},
-                                          seq ? &dst[0].pad : nullptr, 1, ofrag);
-    else skw_dec_cross_attn_vt(dq, dk, dv, rows, H, d, n_ctx, Tpad, dout, active ? &dst[0].active : nullptr, c->stream, 0, form == 2 ? 2 : 1, seq ? &dst[0].pad : nullptr, nullptr, nullptr,
-                               ofrag, nullptr, count ? &dst[0].n_keys : nullptr);
-    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(o.data(), dout, nO * 2, hipMemcpyDeviceToHost))) return -1;
-    cleanup();
-    for (int r = 0; r < orows; ++r) for (int n = 0; n < d; ++n)
-        out_host[(size_t)r * d + n] = skw_f16_to_f32(o[ofrag ? (size_t)skw_afrag_off(r, skw_kperm(n), d) : (size_t)r * d + skw_kperm(n)]);
-    return 0;
-}
-
-// tests (tests/test_gpu_kv8.py): the two kernels of cross_kv = q8_0 on host-supplied operands, in the style of skw_debug_attn16 (whose packing, pads and sentinel these share).
-// K / V [slot][n_ctx][H*64] arrive as f16 bit patterns in natural order and become the f16 fragment-order images, pad patterns from fill_from[s] up; slot_k (null: n_ctx) are the
-// quantiser's key counts per slot.  The q8 image starts as the byte 0xEE, so what k_kv8_quantize does not write is visible.
-struct Kv8Hook { half_t *dk = nullptr, *dv = nullptr; uint8_t* img = nullptr; int* dslot_k = nullptr; size_t img_bytes = 0; ~Kv8Hook() { hipFree(dk); hipFree(dv); hipFree(img); hipFree(dslot_k); } };
-static const char* kv8_hook_quantize(skw_ctx* c, Kv8Hook& k8, int H, int n_ctx, int n_slots, const uint16_t* K_host, const uint16_t* V_host, const int* fill_from, int k_pad, int v_pad,
-                                     const int* slot_k) {
-    if (H < 1 || H > 32 || n_ctx < 1 || n_ctx > 4096 || n_slots < 1 || n_slots > 64 || !fill_from || !K_host || !V_host) return "bad geometry";
-    for (int s = 0; s < n_slots; ++s) if (fill_from[s] < 0 || fill_from[s] > n_ctx || (slot_k && (slot_k[s] < 1 || slot_k[s] > n_ctx))) return "fill_from / slot_k outside the slot";
-    const int d = H * 64, Tpad = (n_ctx + 31) & ~31; const size_t nKV = (size_t)n_slots * Tpad * d;
-    std::vector<uint16_t> q(1), k(nKV, (uint16_t)k_pad), v(nKV, (uint16_t)v_pad);
-    const uint16_t q0 = 0;
-    attn_hook_pack(AttnHookLayout{0, 0, 1, 0, 1}, H, n_ctx, n_slots, &q0, K_host, V_host, fill_from, q, k, v);
-    k8.img_bytes = (size_t)n_slots * skw_kv8_slot_bytes(H, Tpad);
-    if (hipMalloc((void**)&k8.dk, nKV * 2) != hipSuccess || hipMalloc((void**)&k8.dv, nKV * 2) != hipSuccess || hipMalloc((void**)&k8.img, k8.img_bytes) != hipSuccess ||
-        hipMalloc((void**)&k8.dslot_k, sizeof(int) * 64) != hipSuccess) return "device allocation failed";
-    int sk[64] = {0}; if (slot_k) for (int s = 0; s < n_slots; ++s) sk[s] = slot_k[s];
-    if (hipMemcpy(k8.dk, k.data(), nKV * 2, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(k8.dv, v.data(), nKV * 2, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(k8.img, 0xEE, k8.img_bytes) != hipSuccess || hipMemcpy(k8.dslot_k, sk, sizeof sk, hipMemcpyHostToDevice) != hipSuccess) return "copy to the device failed";
-    skw_kv8_quantize(k8.dk, k8.dv, k8.img, 0, n_slots, H, n_ctx, Tpad, slot_k ? k8.dslot_k : nullptr, c->stream);
-    return nullptr;
-}
-// -> img_host [n_slots * skw_layout_kv8_slot_bytes(H, Tpad)]: the image as the kernel wrote it
-extern "C" int skw_debug_kv8_quantize(skw_ctx* c, int H, int n_ctx, int n_slots, const uint16_t* K_host, const uint16_t* V_host, const int* fill_from, int k_pad, int v_pad,
-                                      const int* slot_k, uint8_t* img_host) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    Kv8Hook k8;
-    if (const char* what = kv8_hook_quantize(c, k8, H, n_ctx, n_slots, K_host, V_host, fill_from, k_pad, v_pad, slot_k)) { snprintf(errbuf, 512, "skw_debug_kv8_quantize: %s", what); return -1; }
-    HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(img_host, k8.img, k8.img_bytes, hipMemcpyDeviceToHost));
-    return 0;
-}
-// The quantise kernel, then skw_dec_cross_attn_kv8 through its launcher.  Q [rows][H*64]; active / seq / count (= n_keys) are [rows] or null and reach the kernel as fields of a
-// SkwSeqState array.  flags: 2 ofrag, 4 f32_out (the output rows unrounded), 8 raw.  out_host: f32 [rows][H*64] in natural order — rows the kernel leaves alone hold `sentinel`
-// (as f16; with f32_out the 32-bit pattern sentinel | sentinel << 16) — or, raw, the f32 scores [rows][H][n_ctx], NaN where nothing was written.
-extern "C" int skw_debug_attn_kv8(skw_ctx* c, int H, int n_ctx, int n_slots, int rows, int flags, const uint16_t* Q_host, const uint16_t* K_host, const uint16_t* V_host,
-                                  const int* fill_from, int k_pad, int v_pad, const int* slot_k, const int* active, const int* seq, const int* count, int sentinel, float* out_host) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_attn_kv8: %s", what); return -1; };
-    if (rows < 1 || rows > 65536 || !Q_host || !out_host) return bad("bad geometry");
-    const int ofrag = (flags >> 1) & 1, f32_out = (flags >> 2) & 1, raw = (flags >> 3) & 1;
-    if (ofrag && f32_out) return bad("ofrag and f32_out exclude each other");
-    Kv8Hook k8;
-    if (const char* what = kv8_hook_quantize(c, k8, H, n_ctx, n_slots, K_host, V_host, fill_from, k_pad, v_pad, slot_k)) return bad(what);
-    const int d = H * 64, Tpad = (n_ctx + 31) & ~31;
-    for (int b = 0; b < rows; ++b) {
-        const int s = seq ? seq[b] : b;
-        if (s < 0 || s >= n_slots) return bad("a row's sequence lies outside the slots");
-        if (count && (count[b] < 0 || count[b] > (slot_k ? slot_k[s] : n_ctx))) return bad("a row's key count lies beyond what its slot was quantised with");
-    }
-    const size_t nO = (size_t)(ofrag ? (rows + 15) & ~15 : rows) * d * (f32_out ? 2 : 1), nR = raw ? (size_t)rows * H * n_ctx : 1;
-    std::vector<uint16_t> o(nO, (uint16_t)sentinel);
-    std::vector<SkwSeqState> st(rows); memset((void*)st.data(), 0, sizeof(SkwSeqState) * rows);
-    for (int b = 0; b < rows; ++b) { st[b].active = active ? active[b] : 1; st[b].pad = seq ? seq[b] : b; st[b].n_keys = count ? count[b] : 0; }
-    half_t *dq = nullptr, *dout = nullptr; SkwSeqState* dst = nullptr; float* draw = nullptr;
-    auto cleanup = [&]() { hipFree(dq); hipFree(dout); hipFree(dst); hipFree(draw); };
-    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_attn_kv8: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
-    if (!chk(hipMalloc((void**)&dq, (size_t)rows * d * 2)) || !chk(hipMalloc((void**)&dout, nO * 2)) || !chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * rows))) return -1;
-    if (!chk(hipMalloc((void**)&draw, nR * 4)) || !chk(hipMemset(draw, 0xFF, nR * 4))) return -1;
-    if (!chk(hipMemcpy(dq, Q_host, (size_t)rows * d * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dout, o.data(), nO * 2, hipMemcpyHostToDevice))) return -1;
-    if (!chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * rows, hipMemcpyHostToDevice))) return -1;
-    skw_dec_cross_attn_kv8(dq, k8.img, rows, H, d, n_ctx, Tpad, dout, active ? &dst[0].active : nullptr, c->stream, f32_out, seq ? &dst[0].pad : nullptr, nullptr, nullptr, ofrag, nullptr,
-                           count ? &dst[0].n_keys : nullptr, raw ? draw : nullptr);
-    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError())) return -1;
-    if (raw) { if (!chk(hipMemcpy(out_host, draw, nR * 4, hipMemcpyDeviceToHost))) return -1; cleanup(); return 0; }
-    if (!chk(hipMemcpy(o.data(), dout, nO * 2, hipMemcpyDeviceToHost))) return -1;
-    cleanup();
-    if (f32_out) memcpy(out_host, o.data(), (size_t)rows * d * 4);
-    else for (int r = 0; r < rows; ++r) for (int n = 0; n < d; ++n)
-        out_host[(size_t)r * d + n] = skw_f16_to_f32(o[ofrag ? (size_t)skw_afrag_off(r, skw_kperm(n), d) : (size_t)r * d + skw_kperm(n)]);
-    return 0;
-}
-
-// tests (tests/test_gpu_attn_exact.py): the two exact-precision attention launchers that skw_debug_xattn_exact does not reach, on host-supplied operands, to be held bit for bit to
-// the numpy restatement of the contract (tests/attn_exact_ref_lib.py).  Operands, fill_from, k_pad / v_pad and the sentinel are skw_debug_attn16's (whose packing this shares).
-//   form 0  skw_attn_encoder — the launcher, so its choice between k_attn_encoder and k_attn_encoder_v3 is part of what is tested; *kernel_id is what skw_attn_encoder_kernel, the
-//           function the launcher branches on, answers for the launch.  Q is [slot][n_ctx][H*64]; slot_k null: out rows = n_slots * n_ctx; given ([n_slots], each in 1 .. n_ctx):
-//           n_slots * out_rows (out_rows 0: n_ctx)
-//   form 1  skw_dec_self_attn, fastv = 0, no q8 output (k_dec_attn<7>): Q [rows][H*64], K / V the caches [slot][n_ctx = n_text_ctx][H*64]; pos [rows] (required), active / seq
-//           [rows] or null, reaching the kernel as fields of a SkwSeqState array; *kernel_id = -1
-// out: orows x H*64 elements of 2 bytes (f16 bits), or 4 (f32_out: the kernel's unrounded f32 rows).  raw: the f16 rows as the kernel leaves them (kperm order); otherwise un-permuted.
-extern "C" int skw_debug_attn_exact(skw_ctx* c, int form, int H, int n_ctx, int n_slots, int rows, int f32_out, int raw, int out_rows, const uint16_t* Q_host, const uint16_t* K_host,
-                                    const uint16_t* V_host, const int* fill_from, int k_pad, int v_pad, const int* slot_k, const int* active, const int* seq, const int* pos, int sentinel,
-                                    void* out_host, int* kernel_id) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_attn_exact: %s", what); return -1; };
-    if (form < 0 || form > 1 || H < 1 || H > 32 || n_ctx < 1 || n_ctx > 4096 || n_slots < 1 || n_slots > 64 || rows < 1 || rows > 4096 || !fill_from || !Q_host || !K_host || !V_host ||
-        !out_host || !kernel_id) return bad("bad geometry");
-    const int d = H * 64, Tpad = (n_ctx + 31) & ~31, esz = f32_out ? 2 : 1;      // (output element size in halves)
-    for (int s = 0; s < n_slots; ++s) if (fill_from[s] < 0 || fill_from[s] > n_ctx) return bad("fill_from outside [0, n_ctx]");
-    int orows = rows;
-    if (form == 0) {
-        if (slot_k) for (int s = 0; s < n_slots; ++s) if (slot_k[s] < 1 || slot_k[s] > n_ctx || (out_rows && out_rows < slot_k[s])) return bad("slot_k outside [1, n_ctx] or above out_rows");
-        if (!slot_k && out_rows && out_rows != n_ctx) return bad("out_rows needs slot_k");
-        if (out_rows < 0 || out_rows > 4096) return bad("out_rows outside [0, 4096]");
-        orows = n_slots * (out_rows ? out_rows : n_ctx);
-    } else {
-        if (n_ctx > 7 * 64 || !pos) return bad("the self-attention form needs pos and n_text_ctx <= 448");
-        for (int b = 0; b < rows; ++b) {
-            const int s = seq ? seq[b] : b;
-            if (s < 0 || s >= n_slots || pos[b] < 0 || pos[b] >= n_ctx) return bad("a row's sequence or pos lies outside the caches");
-        }
-    }
-    const size_t nQ = form == 0 ? (size_t)n_slots * Tpad * d : (size_t)rows * d, nK = (size_t)n_slots * (form == 0 ? Tpad : n_ctx) * d, nV = nK, nO = (size_t)orows * d * esz;
-    std::vector<uint16_t> q(nQ, (uint16_t)k_pad), k(nK, (uint16_t)k_pad), v(nV, (uint16_t)v_pad), o(nO, (uint16_t)sentinel);
-    attn_hook_pack(AttnHookLayout{form == 0, form == 0, 0, form == 1, 0}, H, n_ctx, n_slots, Q_host, K_host, V_host, fill_from, q, k, v);
-    std::vector<SkwSeqState> st(rows); memset((void*)st.data(), 0, sizeof(SkwSeqState) * rows);
-    if (form == 1) for (int b = 0; b < rows; ++b) { st[b].active = active ? active[b] : 1; st[b].pad = seq ? seq[b] : b; st[b].cur_pos = pos[b]; }
-    half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr; SkwSeqState* dst = nullptr; int* dmeta = nullptr;
-    auto cleanup = [&]() { hipFree(dq); hipFree(dk); hipFree(dv); hipFree(dout); hipFree(dst); hipFree(dmeta); };
-    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_attn_exact: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
-    if (!chk(hipMalloc((void**)&dq, nQ * 2)) || !chk(hipMalloc((void**)&dk, nK * 2)) || !chk(hipMalloc((void**)&dv, nV * 2)) || !chk(hipMalloc((void**)&dout, nO * 2))) return -1;
-    if (!chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * rows)) || !chk(hipMalloc((void**)&dmeta, sizeof(int) * 64))) return -1;
-    if (!chk(hipMemcpy(dq, q.data(), nQ * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dk, k.data(), nK * 2, hipMemcpyHostToDevice))) return -1;
-    if (!chk(hipMemcpy(dv, v.data(), nV * 2, hipMemcpyHostToDevice))) return -1;
-    if (!chk(hipMemcpy(dout, o.data(), nO * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * rows, hipMemcpyHostToDevice))) return -1;
-    int meta[64] = {0};
-    if (slot_k) for (int s = 0; s < n_slots; ++s) meta[s] = slot_k[s];
-    if (!chk(hipMemcpy(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice))) return -1;
-    *kernel_id = -1;
-    if (form == 0) {
-        *kernel_id = skw_attn_encoder_kernel(n_ctx, Tpad, false, slot_k != nullptr);
-        skw_attn_encoder(dq, dk, dv, dout, d, n_slots, H, n_ctx, Tpad, c->stream, nullptr, nullptr, f32_out ? 1 : 0, slot_k ? dmeta : nullptr, out_rows);
-    } else skw_dec_self_attn(dq, dk, dv, &dst[0].cur_pos, rows, H, d, n_ctx, dout, active ? &dst[0].active : nullptr, c->stream, f32_out ? 1 : 0, SkwQ8Out{nullptr, nullptr, nullptr, 0},
-                             seq ? &dst[0].pad : nullptr, 0, 0);
-    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(o.data(), dout, nO * 2, hipMemcpyDeviceToHost))) return -1;
-    cleanup();
-    if (f32_out || raw) memcpy(out_host, o.data(), nO * 2);
-    else for (int r = 0; r < orows; ++r) for (int n = 0; n < d; ++n) ((uint16_t*)out_host)[(size_t)r * d + n] = o[(size_t)r * d + skw_kperm(n)];
-    return 0;
-}
-
-// tests (tests/test_gpu_q8.py): one product of ggml's arithmetic for quantised files on host-supplied operands, through everything the engine itself goes through — the model
-// loader's repack of the file's blocks (host_q / up_q), skw_q8_quantize on the f32 rows A [M][lda], then skw_gemm_q8 (so the dispatch is part of what is tested; *kernel_id is what
-// skw_gemm_q8_kernel — the function the launcher branches on — answers for the launch's arguments).  The output buffers are the caller's: C (c_bytes; ldc elements per row where the
-// epilogue has rows) and, for EPI_DEC_QKV, C2 / C3 (c2_bytes each, ldc2) are uploaded as given — a sentinel pattern with a margin past M and N is the caller's to lay down — and read
-// back after the launch.  res_alias (EPI_F32): the residual is C itself, as the engine calls it, so C's first M x N region holds the residual on entry.  pos (EPI_DEC_QKV): [M], reaches
-// the kernel as the cur_pos fields of a SkwSeqState array.  Every index the epilogue can form is checked against the buffer sizes here, before anything is launched.
-extern "C" int skw_debug_gemm_q8(skw_ctx* c, int type, const uint8_t* blocks_host, int N, int K, const float* A_host, long lda, int M, int segmented, int epi,
-                                 int n_ctx, int H, int Tpad, const float* bias_host, int res_alias, float scale, int has_scale, const int* pos,
-                                 void* C_host, long c_bytes, long ldc, void* C2_host, void* C3_host, long c2_bytes, long ldc2, int* kernel_id) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_gemm_q8: %s", what); return -1; };
-    const int form = skw_ggml_dot_form(type);
-    if (!form || M < 1 || M > 65536 || N < 1 || N > 65536 || K < 32 || K > 8192 || (K & 31) || lda < K || (lda & 3) || !blocks_host || !A_host || !C_host || !kernel_id) return bad("bad geometry");
-    if (segmented && ((K & 127) || M > 4096)) return bad("the segmented form needs K % 128 == 0 and M <= 4096");
-    const long MN_last = (long)(M - 1) * ldc + N;
-    switch (epi) {
-        case EPI_F32: case EPI_GELU_F32: if (ldc < N || MN_last * 4 > c_bytes) return bad("C too small"); break;
-        case EPI_F16_PLAIN: if (ldc < N || MN_last * 2 > c_bytes) return bad("C too small"); break;
-        case EPI_HEADS_F16: case EPI_VT_F16:
-            if (n_ctx < 1 || M % n_ctx || (N & 63) || H != N / 64 || Tpad < n_ctx || (Tpad & 31) || (long)(M / n_ctx) * H * Tpad * 64 * 2 > c_bytes) return bad("heads / V^T geometry");
-            break;
-        case EPI_DEC_QKV:
-            if (N % 3 || n_ctx != N / 3 || !pos || !C2_host || !C3_host || ldc < n_ctx || ((long)(M - 1) * ldc + n_ctx) * 2 > c_bytes) return bad("q|k|v geometry");
-            for (int m = 0; m < M; ++m) if (pos[m] < 0 || ((long)m * ldc2 + (long)(pos[m] + 1) * n_ctx) * 2 > c2_bytes) return bad("a row's cache position lies outside C2 / C3");
-            break;
-        default: return bad("an epilogue skw_gemm_q8 does not take");
-    }
-    if (res_alias && epi != EPI_F32) return bad("res_alias is EPI_F32's");
-    HostQ hq; host_q(type, blocks_host, N, K, &hq);
-    DevLin L; const size_t allocs_before = c->m->allocs.size();
-    const bool up = up_q(c->m, hq, type, &L);
-    const int nb = K / 32;
-    float *dA = nullptr, *dd = nullptr, *ds = nullptr, *dbias = nullptr; int8_t* dq = nullptr; void *dC = nullptr, *dC2 = nullptr, *dC3 = nullptr; SkwSeqState* dst = nullptr;
-    auto cleanup = [&]() {
-        hipFree(dA); hipFree(dd); hipFree(ds); hipFree(dbias); hipFree(dq); hipFree(dC); hipFree(dC2); hipFree(dC3); hipFree(dst);
-        while (c->m->allocs.size() > allocs_before) { hipFree(c->m->allocs.back()); c->m->allocs.pop_back(); }      // the repacked weight is this call's, not the model's
-    };
-    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_gemm_q8: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
-    if (!up) { cleanup(); return bad("device allocation failed for the weight"); }
-    if (!chk(hipMalloc((void**)&dA, (size_t)M * lda * 4)) || !chk(hipMalloc((void**)&dq, (size_t)M * K)) || !chk(hipMalloc((void**)&dd, (size_t)M * nb * 4)) ||
-        !chk(hipMalloc((void**)&ds, (size_t)M * nb * 4)) || !chk(hipMalloc(&dC, (size_t)c_bytes))) return -1;
-    if (!chk(hipMemcpy(dA, A_host, (size_t)M * lda * 4, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dC, C_host, (size_t)c_bytes, hipMemcpyHostToDevice))) return -1;
-    if (bias_host && (!chk(hipMalloc((void**)&dbias, (size_t)N * 4)) || !chk(hipMemcpy(dbias, bias_host, (size_t)N * 4, hipMemcpyHostToDevice)))) return -1;
-    SkwGemmArgs a{}; a.M = M; a.N = N; a.K = K; a.C = dC; a.ldc = ldc; a.epi = epi; a.scale = scale; a.has_scale = has_scale; a.bias = dbias; a.n_ctx = n_ctx; a.H = H; a.Tpad = Tpad;
-    a.gelu_tab = c->m->gelu_tab;
-    if (res_alias) { a.res = (const float*)dC; a.ldres = ldc; }
-    if (epi == EPI_DEC_QKV) {
-        std::vector<SkwSeqState> st(M); memset((void*)st.data(), 0, sizeof(SkwSeqState) * M);
-        for (int m = 0; m < M; ++m) { st[m].active = 1; st[m].cur_pos = pos[m]; }
-        if (!chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * M)) || !chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * M, hipMemcpyHostToDevice))) return -1;
-        if (!chk(hipMalloc(&dC2, (size_t)c2_bytes)) || !chk(hipMalloc(&dC3, (size_t)c2_bytes))) return -1;
-        if (!chk(hipMemcpy(dC2, C2_host, (size_t)c2_bytes, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dC3, C3_host, (size_t)c2_bytes, hipMemcpyHostToDevice))) return -1;
-        a.C2 = dC2; a.C3 = dC3; a.ldc2 = ldc2; a.pos_ptr = &dst[0].cur_pos; a.pos_stride = (int)(sizeof(SkwSeqState) / sizeof(int));
-    }
-    skw_q8_quantize(dA, lda, M, K, dq, dd, ds, c->stream);
-    SkwQ8Args qa{dq, dd, ds, L.qw, L.dwT, L.mwT, L.n_pad, L.qform, segmented ? 1 : 0};
-    *kernel_id = skw_gemm_q8_kernel(a, qa);
-    if (!skw_gemm_q8(a, qa, c->stream)) { cleanup(); return bad("skw_gemm_q8 refused the arguments"); }
-    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(C_host, dC, (size_t)c_bytes, hipMemcpyDeviceToHost))) return -1;
-    if (epi == EPI_DEC_QKV && (!chk(hipMemcpy(C2_host, dC2, (size_t)c2_bytes, hipMemcpyDeviceToHost)) || !chk(hipMemcpy(C3_host, dC3, (size_t)c2_bytes, hipMemcpyDeviceToHost)))) return -1;
-    cleanup();
-    return 0;
-}
-// tests (tests/test_gpu_gemm16_epi.py): one product of the f16_mfma precision on host-supplied operands through the public launchers, so that the dispatch is part of what is tested,
-// with EVERY argument of the epilogues in the caller's hands — to be compared bit for bit with tests/gemm16_ref_lib.py.  Modelled on skw_debug_gemm_q8: the output buffers are the
-// caller's (C, and C2 / C3 for EPI_DEC_QKV: uploaded as given — the caller's sentinel with its margins — and read back after the launch), every index the launch can form is checked
-// against the buffer sizes here, BEFORE anything is launched (-1 and a message otherwise), kernel_id is what the launcher itself branches on (SkwGemm16Kernel), and -2 means the
-// launcher refuses the geometry (so a case never silently tests another kernel).
-//   launcher 0 / 1: skw_gemm16 with GEMM16W forced 1 / 0 in-process (k_gemm16w / k_gemm16), restored afterwards; 2: skw_gemm16_small; 3: skw_gemm16_small_lnA
-//   A: f16 bits, a_halves of them (rows at lda, or a_rows_per_batch / a_batch_stride; a_frag: the fragment-order image, pad rows M .. ceil16(M) included); launcher 3: ln_x [M][K],
-//   ln_w, ln_b [K] f32 instead.  W: [N][K] f16 bits in the order the kernel reads k; use_wf: the entry builds the fragment-order image itself (perm as the engine picks it: the
-//   kperm'ed-output epilogues).  res: separate [M][ldres] f32, or res_alias: C itself.  pos [M] (EPI_DEC_QKV) reaches the kernel as SkwSeqState::cur_pos with the real stride.
-//   force_small: probe bit 4 of the launcher — k_gemm16_small where the vocabulary kernel would apply.
-struct skw_gemm16_epi_args {
-    int32_t launcher, M, N, K, epi;
-    const uint16_t* A; int64_t a_halves, lda; int32_t a_rows_per_batch; int64_t a_batch_stride; int32_t a_frag;
-    const float *ln_x, *ln_w, *ln_b;
-    const uint16_t* W; int32_t use_wf;
-    const float* bias; const float* res; int64_t ldres; int32_t res_alias;
-    float scale; int32_t has_scale;
-    const float* pe; int32_t n_ctx, H, Tpad, frag, c_frag;
-    const int32_t* pos; int32_t force_small;
-    void* C; int64_t c_bytes, ldc; void* C2; void* C3; int64_t c2_bytes, ldc2;
-    int32_t kernel_id;      // out
-};
-extern "C" int skw_debug_gemm16_epi(skw_ctx* c, skw_gemm16_epi_args* p) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_gemm16_epi: %s", what); return -1; };
-    if (!p) return bad("no arguments");
-    const int M = p->M, N = p->N, K = p->K, epi = p->epi, L = p->launcher; const long ldc = p->ldc;
-    p->kernel_id = SKW_G16K_NONE;
-    if (L < 0 || L > 3 || M < 1 || M > 65536 || N < 1 || N > 65536 || K < 64 || K > 8192 || !p->W || !p->C || p->c_bytes < 1) return bad("bad geometry");
-    const bool big = L <= 1, lna = L == 3;
-    const bool f32out = epi == EPI_F32 || epi == EPI_CONV2;
-    const bool permo = epi == EPI_F16_KPERM || epi == EPI_GELU_F16_KPERM || epi == EPI_GELU_F16_KPERM_ROWPAD || epi == EPI_HEADS_F16;      // features stored in kperm order
-    const bool per_clip = epi == EPI_HEADS_F16 || epi == EPI_VT_F16 || epi == EPI_GELU_F16_KPERM_ROWPAD || epi == EPI_CONV2 || p->frag;
-    const long esz = f32out ? 4 : 2;
-    // ---- operands
-    if (big) {
-        if ((K & 63) || (N & 15) || (permo && (N & 31))) return bad("the big kernels take K % 64 == 0, N % 16 == 0 (N % 32 == 0 for kperm'ed outputs)");
-        if (p->a_frag || p->c_frag || p->ln_x || p->force_small || epi == EPI_DEC_QKV) return bad("a decode kernels' argument on a big-kernel launch");
-        if (!p->A || p->lda < 8 || (p->lda & 7) || (p->a_rows_per_batch ? (p->a_rows_per_batch < 1 || (p->a_batch_stride & 7) || p->a_batch_stride < 0) : p->lda < K)) return bad("A rows");
-        const long last = p->a_rows_per_batch ? (long)((M - 1) / p->a_rows_per_batch) * p->a_batch_stride + (long)std::min(M - 1, p->a_rows_per_batch - 1) * p->lda : (long)(M - 1) * p->lda;
-        if (last + K > p->a_halves) return bad("A too small for its rows");
-        if (ldc & (f32out ? 3 : 7)) return bad("ldc must keep 16-byte chunks aligned");
-    } else {
-        if ((K & 127)) return bad("the decode kernels take K % 128 == 0");
-        if (p->frag || p->a_rows_per_batch || per_clip) return bad("a big kernels' argument on a decode launch");
-        if (epi != EPI_F32 && epi != EPI_F16_PLAIN && epi != EPI_GELU_F16_KPERM && epi != EPI_DEC_QKV) return bad("an epilogue the decode kernels do not take");
-        if (epi != EPI_F32 && ((N & 15) || (ldc & 3))) return bad("the f16 epilogues store 8-byte groups: N % 16 == 0, ldc % 4 == 0");
-        if (epi == EPI_GELU_F16_KPERM && (N & 31)) return bad("kperm'ed outputs need N % 32 == 0");
-        if (p->c_frag && epi != EPI_GELU_F16_KPERM) return bad("c_frag is EPI_GELU_F16_KPERM's");
-        if (lna) {
-            if (!p->ln_x || !p->ln_w || !p->ln_b || p->a_frag || p->A) return bad("launcher 3 takes ln_x / ln_w / ln_b and no A");
-        } else {
-            if (!p->A || p->ln_x) return bad("launcher 2 takes A");
-            if (p->a_frag ? (long)((M + 15) & ~15) * K > p->a_halves : (p->lda < K || (p->lda & 7) || (long)(M - 1) * p->lda + K > p->a_halves)) return bad("A too small for its rows");
-        }
-    }
-    if (p->use_wf && ((N & 15) || (K & 31)) && big) return bad("a fragment-order image holds whole strips");
-    // ---- outputs: the last element each epilogue can reach
-    if (p->res_alias && (epi != EPI_F32 || p->res)) return bad("res_alias is EPI_F32's, and excludes a separate residual");
-    if (p->res && ((epi != EPI_F32 && !lna) || p->ldres < N || (big && (p->ldres & 3)))) return bad("residual rows");      // (launcher 3 takes none: given one, it must refuse)
-    const long B = (per_clip && p->n_ctx > 0) ? M / p->n_ctx : 0;
-    if (per_clip && (p->n_ctx < 1 || M % p->n_ctx)) return bad("M must be whole clips for this epilogue");
-    if (epi == EPI_HEADS_F16 || epi == EPI_VT_F16 || p->frag) {
-        if ((N & 63) || p->H != N / 64 || p->Tpad < p->n_ctx || (p->Tpad & 31) || B * p->H * p->Tpad * 64 * 2 > p->c_bytes) return bad("heads / V^T / fragment-order geometry");
-        if (p->frag && epi != EPI_F16_PLAIN && epi != EPI_VT_F16) return bad("frag is EPI_F16_PLAIN's and EPI_VT_F16's");
-    } else if (epi == EPI_GELU_F16_KPERM_ROWPAD) {
-        if (ldc < N || ((B * (p->n_ctx + 2) - 2) * ldc + N) * 2 > p->c_bytes) return bad("C too small for the padded rows");
-    } else if (epi == EPI_DEC_QKV) {
-        const int d = p->n_ctx;
-        if (d < 16 || (d & 15) || N != 3 * d || !p->pos || !p->C2 || !p->C3 || ldc < d || ((long)(M - 1) * ldc + d) * 2 > p->c_bytes || (p->ldc2 & 3) || !p->has_scale) return bad("q|k|v geometry");
-        for (int m = 0; m < M; ++m) if (p->pos[m] < 0 || ((long)m * p->ldc2 + (long)(p->pos[m] + 1) * d) * 2 > p->c2_bytes) return bad("a row's cache position lies outside C2 / C3");
-    } else if (p->c_frag) {
-        if ((long)((M + 15) & ~15) * N * 2 > p->c_bytes) return bad("C too small for the fragment-order image");
-    } else {
-        if (epi != EPI_F32 && epi != EPI_CONV2 && epi != EPI_F16_PLAIN && epi != EPI_F16_KPERM && epi != EPI_GELU_F16_KPERM) return bad("an epilogue skw_gemm16 does not take");
-        if (ldc < N || ((long)(M - 1) * ldc + N) * esz > p->c_bytes) return bad("C too small");
-    }
-    if (epi == EPI_CONV2 && (!p->pe || !p->bias)) return bad("EPI_CONV2 needs pe [n_ctx][N] and a bias");
-    if (p->res_alias && (ldc < N)) return bad("res_alias: C rows");
-    // ---- device copies
-    const bool perm = permo;                                  // the image's strip rows in the order of the epilogue that consumes the product, as the model loader picks it
-    half_t *dA = nullptr, *dW = nullptr, *dWf = nullptr; float *dx = nullptr, *dg = nullptr, *db = nullptr, *dbias = nullptr, *dres = nullptr, *dpe = nullptr;
-    void *dC = nullptr, *dC2 = nullptr, *dC3 = nullptr; SkwSeqState* dst = nullptr;
-    auto cleanup = [&]() {
-        hipFree(dA); hipFree(dW); hipFree(dWf); hipFree(dx); hipFree(dg); hipFree(db); hipFree(dbias); hipFree(dres); hipFree(dpe); hipFree(dC); hipFree(dC2); hipFree(dC3); hipFree(dst);
-    };
-    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_gemm16_epi: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
-    auto up = [&](auto** d, const void* h, size_t bytes) { return chk(hipMalloc((void**)d, bytes)) && chk(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice)); };
-    if (p->A && !up(&dA, p->A, (size_t)p->a_halves * 2)) return -1;
-    if (!up(&dW, p->W, (size_t)N * K * 2)) return -1;
-    if (lna && (!up(&dx, p->ln_x, (size_t)M * K * 4) || !up(&dg, p->ln_w, (size_t)K * 4) || !up(&db, p->ln_b, (size_t)K * 4))) return -1;
-    if (p->bias && !up(&dbias, p->bias, (size_t)N * 4)) return -1;
-    if (p->res && !up(&dres, p->res, (size_t)((long)(M - 1) * p->ldres + N) * 4)) return -1;
-    if (p->pe && !up(&dpe, p->pe, (size_t)p->n_ctx * N * 4)) return -1;
-    if (!up(&dC, p->C, (size_t)p->c_bytes)) return -1;
-    SkwGemmArgs a{}; a.A = dA; a.lda = p->lda; a.a_rows_per_batch = p->a_rows_per_batch; a.a_batch_stride = p->a_batch_stride; a.W = dW; a.ldw = K; a.M = M; a.N = N; a.K = K;
-    a.C = dC; a.ldc = ldc; a.bias = dbias; a.scale = p->scale; a.has_scale = p->has_scale; a.gelu_tab = c->m->gelu_tab; a.pe = dpe; a.n_ctx = p->n_ctx; a.H = p->H; a.Tpad = p->Tpad;
-    a.epi = epi; a.c_frag = p->c_frag; a.a_frag = p->a_frag; a.frag = p->frag; a.probe = p->force_small ? 16 : 0; a.ln_x = dx; a.ln_w = dg; a.ln_b = db;
-    if (p->res) { a.res = dres; a.ldres = p->ldres; }
-    if (p->res_alias) { a.res = (const float*)dC; a.ldres = ldc; }
-    if (epi == EPI_DEC_QKV) {
-        std::vector<SkwSeqState> st(M); memset((void*)st.data(), 0, sizeof(SkwSeqState) * M);
-        for (int m = 0; m < M; ++m) { st[m].active = 1; st[m].cur_pos = p->pos[m]; }
-        if (!up(&dst, st.data(), sizeof(SkwSeqState) * M) || !up(&dC2, p->C2, (size_t)p->c2_bytes) || !up(&dC3, p->C3, (size_t)p->c2_bytes)) return -1;
-        a.C2 = dC2; a.C3 = dC3; a.ldc2 = p->ldc2; a.pos_ptr = &dst[0].cur_pos; a.pos_stride = (int)(sizeof(SkwSeqState) / sizeof(int));
-    }
-    if (p->use_wf && !(N & 15)) {
-        if (!chk(hipMalloc((void**)&dWf, (size_t)N * K * 2))) return -1;
-        skw_make_wfrag(dW, K, N, K, perm ? 1 : 0, dWf, c->stream); a.Wf = dWf;
-    } else if (p->use_wf) {      // N % 16 != 0: no image exists for such a weight; a non-null Wf shows the launcher's refusal (the buffer is never read)
-        if (!chk(hipMalloc((void**)&dWf, (size_t)((N + 15) & ~15) * K * 2)) || !chk(hipMemset(dWf, 0, (size_t)((N + 15) & ~15) * K * 2))) return -1;
-        a.Wf = dWf;
-    }
-    (void)skw_sw(0);
-    bool ran = true;
-    if (big) {
-        const int w_was = g_sw_val[SW_GEMM16W];
-        g_sw_val[SW_GEMM16W] = L == 0 ? 1 : 0;
-        if (L == 0 && !skw_gemm16_takes_w(a)) ran = false;
-        else { p->kernel_id = skw_gemm16_kernel(a); skw_gemm16(a, c->stream); }
-        g_sw_val[SW_GEMM16W] = w_was;
-    } else if (L == 2) { p->kernel_id = skw_gemm16_small_kernel(a); ran = skw_gemm16_small(a, c->stream); }
-    else { p->kernel_id = skw_gemm16_small_lnA_kernel(a); ran = skw_gemm16_small_lnA(a, c->stream); }
-    if (!ran) { cleanup(); snprintf(errbuf, 512, "skw_debug_gemm16_epi: the launcher refuses these arguments"); return -2; }
-    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(p->C, dC, (size_t)p->c_bytes, hipMemcpyDeviceToHost))) return -1;
-    if (epi == EPI_DEC_QKV && (!chk(hipMemcpy(p->C2, dC2, (size_t)p->c2_bytes, hipMemcpyDeviceToHost)) || !chk(hipMemcpy(p->C3, dC3, (size_t)p->c2_bytes, hipMemcpyDeviceToHost)))) return -1;
-    cleanup();
-    return 0;
-}
-// tests: k_q8_quantize on host rows x [M][ldx] (ldx >= K, a multiple of 4): q int8 [M][K], dT / sT f32 [K/32][M]
-extern "C" int skw_debug_q8_quantize(skw_ctx* c, const float* x_host, long ldx, int M, int K, int8_t* q, float* dT, float* sT) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    if (M < 1 || M > 65536 || K < 32 || K > 8192 || (K & 31) || ldx < K || (ldx & 3) || !x_host || !q || !dT || !sT) { snprintf(errbuf, 512, "skw_debug_q8_quantize: bad geometry"); return -1; }
-    const int nb = K / 32; float *dx = nullptr, *dd = nullptr, *ds = nullptr; int8_t* dq = nullptr;
-    auto cleanup = [&]() { hipFree(dx); hipFree(dd); hipFree(ds); hipFree(dq); };
-    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_q8_quantize: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
-    if (!chk(hipMalloc((void**)&dx, (size_t)M * ldx * 4)) || !chk(hipMalloc((void**)&dq, (size_t)M * K))) return -1;
-    if (!chk(hipMalloc((void**)&dd, (size_t)M * nb * 4)) || !chk(hipMalloc((void**)&ds, (size_t)M * nb * 4))) return -1;
-    if (!chk(hipMemcpy(dx, x_host, (size_t)M * ldx * 4, hipMemcpyHostToDevice))) return -1;
-    skw_q8_quantize(dx, ldx, M, K, dq, dd, ds, c->stream);
-    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError())) return -1;
-    if (!chk(hipMemcpy(q, dq, (size_t)M * K, hipMemcpyDeviceToHost)) || !chk(hipMemcpy(dT, dd, (size_t)M * nb * 4, hipMemcpyDeviceToHost))) return -1;
-    if (!chk(hipMemcpy(sT, ds, (size_t)M * nb * 4, hipMemcpyDeviceToHost))) return -1;
-    cleanup();
-    return 0;
-}
-// tests: the decoder's self attention (the exact form of k_dec_attn) twice on the same operands — once with f32_out = 1 (out_f32 [rows][H*64]), once leaving its rows as q8 blocks
-// (SkwQ8Out: q int8 [rows][H*64], dT / sT f32 [H*2][rows]) — so that the in-kernel quantiser can be held to quantize_rows of the first launch's rows.  Q [rows][H*64], K / V
-// [rows][n_text_ctx][H*64] f16 bit patterns (row b reads the cache of sequence seq[b], or b); pos / active / seq: [rows] (the last two may be null), reaching the kernel as fields of a
-// SkwSeqState array.  All four output buffers are uploaded as the caller filled them (a sentinel), so what an inactive row leaves is visible.
-extern "C" int skw_debug_self_attn_q8(skw_ctx* c, int H, int n_text_ctx, int rows, const uint16_t* Q_host, const uint16_t* K_host, const uint16_t* V_host, const int* pos, const int* active,
-                                      const int* seq, float* out_f32, int8_t* q, float* dT, float* sT) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_self_attn_q8: %s", what); return -1; };
-    if (H < 1 || H > 32 || n_text_ctx < 1 || n_text_ctx > 7 * 64 || rows < 1 || rows > 4096 || !Q_host || !K_host || !V_host || !pos || !out_f32 || !q || !dT || !sT) return bad("bad geometry");
-    for (int b = 0; b < rows; ++b) if (pos[b] < 0 || pos[b] >= n_text_ctx || (seq && (seq[b] < 0 || seq[b] >= rows))) return bad("pos or seq outside the caches");
-    const int d = H * 64; const size_t nQ = (size_t)rows * d, nKV = (size_t)rows * n_text_ctx * d, nS = (size_t)2 * H * rows;
-    std::vector<SkwSeqState> st(rows); memset((void*)st.data(), 0, sizeof(SkwSeqState) * rows);
-    for (int b = 0; b < rows; ++b) { st[b].active = active ? active[b] : 1; st[b].pad = seq ? seq[b] : b; st[b].cur_pos = pos[b]; }
-    half_t *dq16 = nullptr, *dk = nullptr, *dv = nullptr; float *dout = nullptr, *dd = nullptr, *ds = nullptr; int8_t* dq8 = nullptr; SkwSeqState* dst = nullptr;
-    auto cleanup = [&]() { hipFree(dq16); hipFree(dk); hipFree(dv); hipFree(dout); hipFree(dd); hipFree(ds); hipFree(dq8); hipFree(dst); };
-    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_self_attn_q8: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
-    if (!chk(hipMalloc((void**)&dq16, nQ * 2)) || !chk(hipMalloc((void**)&dk, nKV * 2)) || !chk(hipMalloc((void**)&dv, nKV * 2)) || !chk(hipMalloc((void**)&dout, nQ * 4))) return -1;
-    if (!chk(hipMalloc((void**)&dq8, nQ)) || !chk(hipMalloc((void**)&dd, nS * 4)) || !chk(hipMalloc((void**)&ds, nS * 4)) || !chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * rows))) return -1;
-    if (!chk(hipMemcpy(dq16, Q_host, nQ * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dk, K_host, nKV * 2, hipMemcpyHostToDevice))) return -1;
-    if (!chk(hipMemcpy(dv, V_host, nKV * 2, hipMemcpyHostToDevice))) return -1;
-    if (!chk(hipMemcpy(dout, out_f32, nQ * 4, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dq8, q, nQ, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dd, dT, nS * 4, hipMemcpyHostToDevice))) return -1;
-    if (!chk(hipMemcpy(ds, sT, nS * 4, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * rows, hipMemcpyHostToDevice))) return -1;
-    const int* act = active ? &dst[0].active : nullptr; const int* sq = seq ? &dst[0].pad : nullptr;
-    skw_dec_self_attn(dq16, dk, dv, &dst[0].cur_pos, rows, H, d, n_text_ctx, (half_t*)dout, act, c->stream, 1, SkwQ8Out{nullptr, nullptr, nullptr, 0}, sq);
-    skw_dec_self_attn(dq16, dk, dv, &dst[0].cur_pos, rows, H, d, n_text_ctx, nullptr, act, c->stream, 0, SkwQ8Out{dq8, dd, ds, rows}, sq);
-    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError())) return -1;
-    if (!chk(hipMemcpy(out_f32, dout, nQ * 4, hipMemcpyDeviceToHost)) || !chk(hipMemcpy(q, dq8, nQ, hipMemcpyDeviceToHost)) || !chk(hipMemcpy(dT, dd, nS * 4, hipMemcpyDeviceToHost)) ||
-        !chk(hipMemcpy(sT, ds, nS * 4, hipMemcpyDeviceToHost))) return -1;
-    cleanup();
-    return 0;
-}
-
-// Test hook (tests/test_gpu_xattn_mq_exact.py): the exact precision's two prompt-pass cross attentions on caller-supplied operands, in the style of skw_debug_attn16.
-//   Q [rows][H*64] f16 bit patterns, plain order; K / V [n_slots][n_ctx][H*64] f16 bit patterns in natural order (the hook lays them out as the exact precision keeps them: K rows,
-//   V^T per head in kperm key order); every K / V position of slot s from fill_from[s] up holds k_pad / v_pad when the kernel runs, and so do the pad keys n_ctx .. Tpad of V^T.
-//   n_seq sequences (row0, nq, slot); slot_k null or [n_slots].  mq = 0: skw_dec_cross_attn_vt (pv16 = 0), one row per query, `seq` / `nkeys` built from the same description;
-//   mq = 1: skw_xattn_prefill_exact.  The output buffer starts as `sentinel` in every 16-bit half; out: the raw buffer, rows x H*64 x (f32_out ? 4 : 2) bytes (f16 rows in kperm order).
-extern "C" int skw_debug_xattn_exact(skw_ctx* c, int mq, int H, int n_ctx, int n_slots, int rows, int f32_out, const uint16_t* Q_host, const uint16_t* K_host, const uint16_t* V_host,
-                                     const int* fill_from, int k_pad, int v_pad, const int* slot_k, int n_seq, const int* row0, const int* nq, const int* slot, int sentinel, void* out_host) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_xattn_exact: %s", what); return -1; };
-    if (H < 1 || H > 32 || n_ctx < 1 || n_ctx > SKW_XATTN_MQ_MAX_CTX || n_slots < 1 || n_slots > 64 || rows < 1 || rows > 65536 || !fill_from) return bad("bad geometry");
-    if (n_seq < 1 || n_seq > 64 || !row0 || !nq || !slot) return bad("the prompt pass needs row0 / nq / slot");
-    const int d = H * 64, Tpad = (n_ctx + 31) & ~31; int nq_max = 0;
-    for (int s = 0; s < n_slots; ++s) if (fill_from[s] < 0 || fill_from[s] > n_ctx) return bad("fill_from outside [0, n_ctx]");
-    std::vector<SkwSeqState> st(rows); memset((void*)st.data(), 0, sizeof(SkwSeqState) * rows);      // rows outside every sequence stay inactive: the single-query kernel skips them
-    for (int i = 0; i < n_seq; ++i) {
-        if (row0[i] < 0 || nq[i] < 0 || row0[i] + nq[i] > rows || slot[i] < 0 || slot[i] >= n_slots) return bad("a sequence's rows or slot lie outside the buffers");
-        nq_max = std::max(nq_max, nq[i]);
-        for (int r = row0[i]; r < row0[i] + nq[i]; ++r) { if (st[r].active) return bad("sequences overlap"); st[r].active = 1; st[r].pad = slot[i]; st[r].n_keys = slot_k ? slot_k[slot[i]] : 0; }
-    }
-    if (nq_max < 1) return bad("no queries");
-    const size_t nQ = (size_t)rows * d, nK = (size_t)n_slots * n_ctx * d, nV = (size_t)n_slots * Tpad * d, nO = (size_t)rows * d * (f32_out ? 2 : 1);
-    std::vector<uint16_t> k(nK, (uint16_t)k_pad), v(nV, (uint16_t)v_pad), o(nO, (uint16_t)sentinel);
-    for (int s = 0; s < n_slots; ++s) for (int i = 0; i < fill_from[s]; ++i) for (int n = 0; n < d; ++n) {
-        k[((size_t)s * n_ctx + i) * d + n] = K_host[((size_t)s * n_ctx + i) * d + n];
-        v[((size_t)s * d + n) * Tpad + skw_kperm(i)] = V_host[((size_t)s * n_ctx + i) * d + n];
-    }
-    half_t *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr; SkwSeqState* dst = nullptr; int* dmeta = nullptr;
-    auto cleanup = [&]() { hipFree(dq); hipFree(dk); hipFree(dv); hipFree(dout); hipFree(dst); hipFree(dmeta); };
-    auto chk = [&](hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "skw_debug_xattn_exact: %s", hipGetErrorString(e)); cleanup(); return false; } return true; };
-    if (!chk(hipMalloc((void**)&dq, nQ * 2)) || !chk(hipMalloc((void**)&dk, nK * 2)) || !chk(hipMalloc((void**)&dv, nV * 2)) || !chk(hipMalloc((void**)&dout, nO * 2))) return -1;
-    if (!chk(hipMalloc((void**)&dst, sizeof(SkwSeqState) * rows)) || !chk(hipMalloc((void**)&dmeta, sizeof(int) * 4 * 64))) return -1;
-    if (!chk(hipMemcpy(dq, Q_host, nQ * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dk, k.data(), nK * 2, hipMemcpyHostToDevice))) return -1;
-    if (!chk(hipMemcpy(dv, v.data(), nV * 2, hipMemcpyHostToDevice))) return -1;
-    if (!chk(hipMemcpy(dout, o.data(), nO * 2, hipMemcpyHostToDevice)) || !chk(hipMemcpy(dst, st.data(), sizeof(SkwSeqState) * rows, hipMemcpyHostToDevice))) return -1;
-    int meta[4 * 64] = {0};      // row0 | nq | slot | slot_k
-    for (int i = 0; i < n_seq; ++i) { meta[i] = row0[i]; meta[64 + i] = nq[i]; meta[128 + i] = slot[i]; }
-    if (slot_k) for (int s = 0; s < n_slots; ++s) meta[192 + s] = slot_k[s];
-    if (!chk(hipMemcpy(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice))) return -1;
-    if (mq) {
-        if (!skw_xattn_prefill_exact(dq, dk, dv, dout, n_seq, nq_max, dmeta, dmeta + 64, dmeta + 128, H, d, n_ctx, Tpad, c->stream, f32_out, slot_k ? dmeta + 192 : nullptr)) {
-            cleanup(); return bad("the multi-query launcher refused the geometry"); }
-    } else skw_dec_cross_attn_vt(dq, dk, dv, rows, H, d, n_ctx, Tpad, dout, &dst[0].active, c->stream, f32_out, 0, &dst[0].pad, nullptr, nullptr, 0, nullptr, slot_k ? &dst[0].n_keys : nullptr);
-    if (!chk(hipStreamSynchronize(c->stream)) || !chk(hipGetLastError()) || !chk(hipMemcpy(out_host, dout, nO * 2, hipMemcpyDeviceToHost))) return -1;
-    cleanup();
-    return 0;
-}
-
-// Test hooks (tests/test_gpu_align_kernels.py): the three word-timestamp kernels on caller-supplied arrays, each held by its test to the evaluator of include/skw_align.h.
-// Sequences are described by parallel arrays and laid out back to back: sequence i's rows are prow0 = n[0] + .. + n[i-1] onwards, its matrix starts at cell sum of n[j] * kw[j].
-struct AlignHookBufs {
-    std::vector<void*> dev; char* errbuf; const char* who;
-    bool ok(hipError_t e) { if (e != hipSuccess) { snprintf(errbuf, 512, "%s: %s", who, hipGetErrorString(e)); return false; } return true; }
-    template <typename T> T* up(const T* host, size_t n) {      // a device copy of host[0 .. n); null on failure
-        void* p = nullptr; if (!ok(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)))) return nullptr;
-        dev.push_back(p);
-        if (n && !ok(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice))) return nullptr;
-        return (T*)p;
-    }
-    ~AlignHookBufs() { for (void* p : dev) hipFree(p); }
-};
-static bool align_hook_seqs(std::vector<SkwAlignSeq>& sq, int n_seq, const int* n, const int* kw, long* rows_total, long* cells) {
-    long r = 0, x = 0;
-    for (int i = 0; i < n_seq; ++i) {
-        if (n[i] < 1 || n[i] > SKW_ALIGN_MAX_ROWS || kw[i] < 1) return false;
-        sq[i].n = n[i]; sq[i].kw = kw[i]; sq[i].prow0 = (int)r; sq[i].xoff = x;
-        r += n[i]; x += (long)n[i] * kw[i];
-    }
-    *rows_total = r; *cells = x;
-    return true;
-}
-// step 1.  Q [q_rows][H*64], K [n_slots][n_ctx][H*64] f16 bit patterns, natural order (frag: the hook lays K out as the fragment-order image, Tpad rows, pad keys k_pad).
-// Sequence i: alignment rows qrow0[i] .. + n[i] of Q, slot[i], n_keys[i] (0: n_ctx).  P: [heads of head_mask][rows_total][n_ctx] f32, uploaded as the caller filled it
-// (a sentinel), so what the kernel leaves alone — keys past n_keys — is visible.
-extern "C" int skw_debug_align_qk(skw_ctx* c, int H, int n_ctx, int n_slots, int q_rows, int frag, const uint16_t* Q_host, const uint16_t* K_host, int k_pad, unsigned head_mask,
-                                  int n_seq, const int* qrow0, const int* n, const int* slot, const int* n_keys, float* P_host) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_align_qk: %s", what); return -1; };
-    if (H < 1 || H > 32 || n_ctx < 1 || n_ctx > SKW_XATTN_MQ_MAX_CTX || n_slots < 1 || n_slots > 64 || q_rows < 1 || n_seq < 1 || n_seq > 4096 || !head_mask) return bad("bad geometry");
-    const int d = H * 64, Tpad = (n_ctx + 31) & ~31, nh = skw_align_popcount(head_mask);
-    std::vector<SkwAlignSeq> sq(n_seq); memset((void*)sq.data(), 0, sizeof(SkwAlignSeq) * n_seq);
-    std::vector<int> kw(n_seq, 1); long rows_total = 0, cells = 0;
-    if (!align_hook_seqs(sq, n_seq, n, kw.data(), &rows_total, &cells)) return bad("a sequence's row count lies outside [1, 256]");
-    for (int i = 0; i < n_seq; ++i) {
-        if (qrow0[i] < 0 || qrow0[i] + n[i] > q_rows || slot[i] < 0 || slot[i] >= n_slots || n_keys[i] < 0 || n_keys[i] > n_ctx) return bad("a sequence's rows, slot or keys lie outside the buffers");
-        sq[i].qrow0 = qrow0[i]; sq[i].slot = slot[i]; sq[i].n_keys = n_keys[i];
-    }
-    const size_t nK = (size_t)n_slots * (frag ? Tpad : n_ctx) * d, nP = (size_t)nh * rows_total * n_ctx;
-    std::vector<uint16_t> k(nK, (uint16_t)k_pad);
-    for (int s = 0; s < n_slots; ++s) for (int i = 0; i < n_ctx; ++i) for (int f = 0; f < d; ++f)
-        k[frag ? (size_t)skw_kfrag_off(s, H, Tpad, i, f & ~7) + (f & 7) : ((size_t)s * n_ctx + i) * d + f] = K_host[((size_t)s * n_ctx + i) * d + f];
-    AlignHookBufs b{{}, errbuf, "skw_debug_align_qk"};
-    const half_t* dq = (const half_t*)b.up(Q_host, (size_t)q_rows * d); const half_t* dk = (const half_t*)b.up(k.data(), nK);
-    SkwAlignSeq* dsq = b.up(sq.data(), (size_t)n_seq); float* dP = b.up(P_host, nP);
-    if (!dq || !dk || !dsq || !dP) return -1;
-    if (!skw_align_qk(dq, d, dk, dsq, n_seq, (int)rows_total, head_mask, H, n_ctx, Tpad, frag, dP, rows_total, n_ctx, c->stream)) return bad("the launcher refused the geometry");
-    if (!b.ok(hipStreamSynchronize(c->stream)) || !b.ok(hipGetLastError()) || !b.ok(hipMemcpy(P_host, dP, nP * 4, hipMemcpyDeviceToHost))) return -1;
-    return 0;
-}
-// steps 2-5.  P_host: the layers' captures back to back, layer l = [nh[l]][rows_total][p_stride] f32; one launch per layer in ascending order, the first starting and the last
-// finishing the sums.  x_host: [cells] f32, uploaded as the caller filled it.
-extern "C" int skw_debug_align_reduce(skw_ctx* c, int n_layers, const int* nh, const float* P_host, int p_stride, int width, int n_seq, const int* n, const int* kw, float* x_host) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_align_reduce: %s", what); return -1; };
-    if (n_layers < 1 || n_layers > SKW_ALIGN_MAX_LAYERS || p_stride < 1 || n_seq < 1 || n_seq > 4096) return bad("bad geometry");
-    std::vector<SkwAlignSeq> sq(n_seq); memset((void*)sq.data(), 0, sizeof(SkwAlignSeq) * n_seq);
-    long rows_total = 0, cells = 0; int kw_max = 0, n_heads = 0;
-    if (!align_hook_seqs(sq, n_seq, n, kw, &rows_total, &cells)) return bad("a sequence's row count lies outside [1, 256], or its crop below 1");
-    for (int i = 0; i < n_seq; ++i) { if (kw[i] > p_stride) return bad("a crop beyond the capture's keys"); kw_max = std::max(kw_max, kw[i]); }
-    for (int l = 0; l < n_layers; ++l) { if (nh[l] < 1 || nh[l] > 32) return bad("a layer without heads"); n_heads += nh[l]; }
-    AlignHookBufs b{{}, errbuf, "skw_debug_align_reduce"};
-    const float* dP = b.up(P_host, (size_t)n_heads * rows_total * p_stride); SkwAlignSeq* dsq = b.up(sq.data(), (size_t)n_seq); float* dx = b.up(x_host, (size_t)cells);
-    double* dacc = nullptr; { std::vector<double> nanfill((size_t)cells, (double)NAN); dacc = b.up(nanfill.data(), (size_t)cells); }      // (no launch may read a sum it did not start)
-    if (!dP || !dsq || !dx || !dacc) return -1;
-    size_t off = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        const bool launched = skw_align_reduce(dP + off, rows_total, p_stride, dsq, n_seq, kw_max, nh[l], width, l == 0, l == n_layers - 1, n_heads, dacc, dx, c->stream);
-        if (!launched) return bad("the launcher refused the geometry");
-        off += (size_t)nh[l] * rows_total * p_stride;
-    }
-    if (!b.ok(hipStreamSynchronize(c->stream)) || !b.ok(hipGetLastError()) || !b.ok(hipMemcpy(x_host, dx, (size_t)cells * 4, hipMemcpyDeviceToHost))) return -1;
-    return 0;
-}
-// steps 6-7, one launch for all n_seq problems.  x_host: the matrices back to back; jump / t0 / t1: [rows_total] int32, uploaded as the caller filled them.
-extern "C" int skw_debug_align_dtw(skw_ctx* c, int n_seq, const int* n, const int* kw, const int* seek_cs, const float* x_host, int32_t* jump, int32_t* t0, int32_t* t1) {
-    char* errbuf = c->errbuf; HIPCHK(hipSetDevice(c->m->device));
-    auto bad = [&](const char* what) { snprintf(errbuf, 512, "skw_debug_align_dtw: %s", what); return -1; };
-    if (n_seq < 1 || n_seq > 4096) return bad("bad geometry");
-    std::vector<SkwAlignSeq> sq(n_seq); memset((void*)sq.data(), 0, sizeof(SkwAlignSeq) * n_seq);
-    long rows_total = 0, cells = 0; int kw_max = 0, n_max = 0;
-    if (!align_hook_seqs(sq, n_seq, n, kw, &rows_total, &cells)) return bad("a sequence's row count lies outside [1, 256], or its crop below 1");
-    for (int i = 0; i < n_seq; ++i) { sq[i].seek_cs = seek_cs[i]; kw_max = std::max(kw_max, kw[i]); n_max = std::max(n_max, n[i]); }
-    AlignHookBufs b{{}, errbuf, "skw_debug_align_dtw"};
-    const float* dx = b.up(x_host, (size_t)cells); SkwAlignSeq* dsq = b.up(sq.data(), (size_t)n_seq);
-    int *dj = b.up(jump, (size_t)rows_total), *d0 = b.up(t0, (size_t)rows_total), *d1 = b.up(t1, (size_t)rows_total);
-    if (!dx || !dsq || !dj || !d0 || !d1) return -1;
-    if (!skw_align_dtw(dx, dsq, n_seq, n_max, kw_max, dj, d0, d1, c->stream)) return bad("the launcher refused the geometry");
-    if (!b.ok(hipStreamSynchronize(c->stream)) || !b.ok(hipGetLastError())) return -1;
-    if (!b.ok(hipMemcpy(jump, dj, (size_t)rows_total * 4, hipMemcpyDeviceToHost)) || !b.ok(hipMemcpy(t0, d0, (size_t)rows_total * 4, hipMemcpyDeviceToHost)) ||
-        !b.ok(hipMemcpy(t1, d1, (size_t)rows_total * 4, hipMemcpyDeviceToHost))) return -1;
-    return 0;
-}
 // a clip's alignment record checked the way the entry points will check it (include/skw_align.h): 0 good; -1 bad, skw_ctx_last_error names the clip.  Needs no device.
 extern "C" int skw_align_params_check(skw_ctx* c, const skw_align_params* p, int clip) {
     return skw_align_check_params(p, c->m->hp.n_text_layer, c->m->hp.n_text_head, clip, c->errbuf, 512) ? 0 : -1;
@@ -3246,181 +1946,3 @@ extern "C" int skw_debug_xattn(skw_ctx* c, int B, int layers, int probe, int ite
     return 0;
 }
 
-// ------------------------------------------------------------------ resampler front end (R1-R3), model-free device context
-struct skw_dsp { int device = 0; hipStream_t stream = nullptr;
-char errbuf[512] = {0}; float *d_in = nullptr, *d_out = nullptr, *d_frac = nullptr, *d_coef = nullptr;
-int* d_pos = nullptr; int* d_n = nullptr; double* d_li = nullptr;
-                 size_t cap_in = 0, cap_out = 0; int coef_L = 0, coef_M = 0;
-                 double* d_start = nullptr; int *d_count = nullptr, *d_offset = nullptr, *d_flag = nullptr; size_t cap_chunks = 0; int last_flags[2] = {0, 0}; bool host_walk_last = false; };
-extern "C" skw_dsp* skw_dsp_create(int device, char* err, size_t errlen) {
-    int ndev = skw_device_count();
-    if (ndev <= 0) { set_err(err, errlen, "no HIP device available: the resampler kernels require an MI355X (gfx950); there is no CPU fallback"); return nullptr; }
-    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "gpu_device %d out of range (%d devices)", device, ndev); return nullptr; }
-    skw_dsp* d = new skw_dsp(); d->device = device;
-    if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&d->d_n, sizeof(int)) != hipSuccess || hipMalloc((void**)&d->d_li,
-        sizeof(double)) != hipSuccess) { set_err(err, errlen, "device allocation failed");
-    delete d; return nullptr; }
-    return d;
-}
-extern "C" void skw_dsp_free(skw_dsp* d) { if (!d) return; hipSetDevice(d->device); hipStreamSynchronize(d->stream); hipFree(d->d_in); hipFree(d->d_out);
-hipFree(d->d_frac); hipFree(d->d_pos); hipFree(d->d_coef); hipFree(d->d_n); hipFree(d->d_li); hipFree(d->d_start); hipFree(d->d_count); hipFree(d->d_offset);
-hipFree(d->d_flag); hipStreamDestroy(d->stream); delete d; }
-extern "C" const char* skw_dsp_last_error(const skw_dsp* d) { return d->errbuf; }
-static int dsp_reserve(skw_dsp* d, size_t n_in, size_t n_out) {
-    char* errbuf = d->errbuf;
-    if (n_in > d->cap_in) {
-        hipFree(d->d_in); d->cap_in = n_in * 2; HIPCHK(hipMalloc((void**)&d->d_in, d->cap_in * sizeof(float))); poison_floats(d->d_in, d->cap_in * sizeof(float));
-    }
-    if (n_out > d->cap_out) { hipFree(d->d_out); hipFree(d->d_frac);
-    hipFree(d->d_pos); d->cap_out = n_out * 2; HIPCHK(hipMalloc((void**)&d->d_out, d->cap_out * sizeof(float)));
-    HIPCHK(hipMalloc((void**)&d->d_frac, d->cap_out * sizeof(float))); HIPCHK(hipMalloc((void**)&d->d_pos, d->cap_out * sizeof(int)));
-    poison_floats(d->d_out, d->cap_out * sizeof(float)); poison_floats(d->d_frac, d->cap_out * sizeof(float)); }
-    return 0;
-}
-extern "C" void skw_resampler_init(skw_resampler_state* st, double ratio, int chunk_frames, int channels) {
-    memset(st, 0, sizeof *st); st->last_index = -4.0; st->ratio = ratio; st->chunk_frames = chunk_frames; st->channels = channels;   // -(POLYNOMIAL_LEN/2), zero history
-}
-// n_chunks full chunks of interleaved input -> interleaved output frames; state (history + fractional index) carried like rubato's
-extern "C" int skw_resample_linear(skw_dsp* d, skw_resampler_state* st, const float* in, int n_chunks, float* out, int out_cap_frames, int* out_frames) {
-    char* errbuf = d->errbuf; HIPCHK(hipSetDevice(d->device));
-    const int ch = st->channels, chunk = st->chunk_frames; *out_frames = 0;
-    if (ch < 1 || ch > 2 || chunk < 1 || n_chunks < 1 || (chunk < 16 && n_chunks != 1)) { snprintf(errbuf, 512, "resampler: unsupported geometry (channels %d, chunk_frames %d)", ch, chunk);
-    return -1; }
-    const size_t n_in = (size_t)(16 + (size_t)n_chunks * chunk) * ch;
-    if (dsp_reserve(d, n_in, (size_t)out_cap_frames * ch)) return -1;
-    HIPCHK(hipMemcpyAsync(d->d_in, st->hist, sizeof(float) * 16 * ch, hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipMemcpyAsync(d->d_in + 16 * ch, in, sizeof(float) * (size_t)n_chunks * chunk * ch, hipMemcpyHostToDevice, d->stream));
-    if ((size_t)n_chunks + 1 > d->cap_chunks) {
-        hipFree(d->d_start); hipFree(d->d_count); hipFree(d->d_offset); d->cap_chunks = ((size_t)n_chunks + 1) * 2;
-        HIPCHK(hipMalloc((void**)&d->d_start, d->cap_chunks * sizeof(double))); HIPCHK(hipMalloc((void**)&d->d_count, d->cap_chunks * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&d->d_offset, d->cap_chunks * sizeof(int)));
-        if (!d->d_flag) HIPCHK(hipMalloc((void**)&d->d_flag, 2 * sizeof(int)));
-    }
-    // The chunk starts are one sequential f64 recurrence over the whole call (rubato's idx += t_ratio).  When every addition of it is exact (48 / 32 / 96 / 8 kHz
-    // sources: t_ratio has a handful of mantissa bits) a closed form gives them on the device.  When it is not (the 44.1 kHz family) and the call is long, the
-    // recurrence is what a CPU core is for — ~480 k dependent additions per 30 s, 0.6 ms at four cycles each, against 7.5 ms for one GPU lane stepping binades —
-    // so the host walks it, the device proves every chunk against it in parallel (k_resample_walk) and does the data path.  Short calls (a streaming packet or
-    // two) keep the device's own proposals.  Same IEEE additions either way: the result is rubato's, bit for bit.
-    const double t_ratio = 1.0 / st->ratio;
-    const bool t_exact = chunk <= 4096 && ldexp(t_ratio, 36) == floor(ldexp(t_ratio, 36));
-    const bool host_walk = !t_exact && n_chunks >= 8 && !skw_sw(SW_RESAMPLE_NO_HOST_WALK);
-    if (host_walk) {
-        std::vector<double> hs((size_t)n_chunks + 1); std::vector<int> hc((size_t)n_chunks + 1, 0), ho((size_t)n_chunks + 1);
-        const double end_idx = (double)(chunk - 9) - ceil(t_ratio); double s = st->last_index; int off = 0;
-        for (int cix = 0; cix < n_chunks; ++cix) { double x = s; int n = 0; while (x < end_idx) { x += t_ratio; n++; } hs[cix] = s; hc[cix] = n; ho[cix] = off; off += n; s = x - (double)chunk; }
-        hs[n_chunks] = s; ho[n_chunks] = off;
-        HIPCHK(hipMemcpyAsync(d->d_start, hs.data(), sizeof(double) * hs.size(), hipMemcpyHostToDevice, d->stream));
-        HIPCHK(hipMemcpyAsync(d->d_count, hc.data(), sizeof(int) * hc.size(), hipMemcpyHostToDevice, d->stream));
-        HIPCHK(hipMemcpyAsync(d->d_offset, ho.data(), sizeof(int) * ho.size(), hipMemcpyHostToDevice, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));      // (the vectors are locals)
-    }
-    d->host_walk_last = host_walk;
-    skw_resample_linear_launch(d->d_in, ch, st->last_index, t_ratio, chunk, n_chunks, d->d_pos, d->d_frac, d->d_n, d->d_li, d->d_out, out_cap_frames,
-                               d->d_start, d->d_count, d->d_offset, d->d_flag, d->stream, host_walk);
-    int n = 0; double li = 0;
-    HIPCHK(hipMemcpyAsync(&n, d->d_n, sizeof(int), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipMemcpyAsync(&li, d->d_li, sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipMemcpyAsync(d->last_flags, d->d_flag, 2 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    if (n > out_cap_frames) { snprintf(errbuf, 512, "resampler: output capacity %d too small for %d frames", out_cap_frames, n); return -1; }
-    HIPCHK(hipMemcpyAsync(out, d->d_out, sizeof(float) * (size_t)n * ch, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-    {   // buffer.copy_within(chunk.., 0): the 16 frames that precede the next chunk (a chunk shorter than 16 frames shifts the old history)
-        const size_t fresh = (size_t)n_chunks * chunk;
-        if (fresh >= 16) memcpy(st->hist, in + (fresh - 16) * ch, sizeof(float) * 16 * ch);
-        else { memmove(st->hist, st->hist + fresh * ch, sizeof(float) * (16 - fresh) * ch); memcpy(st->hist + (16 - fresh) * ch, in, sizeof(float) * fresh * ch); }
-    }
-    st->last_index = li; *out_frames = n; return 0;
-}
-// quality mode: Kaiser-windowed sinc, 32 taps x decimation factor per phase (mono or interleaved stereo)
-static int dsp_polyphase_coefs(skw_dsp* d, int in_rate, int out_rate, int* L_o, int* M_o, int* T_o) {
-    char* errbuf = d->errbuf;
-    auto gcd = [](long a, long b) { while (b) { long t = a % b; a = b; b = t; } return a; };
-    const long g = gcd(in_rate, out_rate); const int L = (int)(out_rate / g), M = (int)(in_rate / g);
-    if (L > 4096 || M > 4096) { snprintf(errbuf, 512, "resampler: ratio %d/%d needs %d phases / a decimation of %d (> 4096)", out_rate, in_rate, L, M); return -1; }
-    const int T = 32 * std::max(1, (M + L - 1) / L);     // span 32 samples of the slower rate
-    *L_o = L; *M_o = M; *T_o = T;
-    if (d->coef_L == L && d->coef_M == M) return 0;
-    std::vector<float> h((size_t)L * T);
-    const double fc = 0.5 * std::min(1.0, (double)L / M) * 0.90, beta = 8.6;   // cutoff (cycles per input sample), a little below Nyquist of the narrower side
-    auto bessel0 = [](double x) { double s = 1, t = 1; for (int k = 1; k < 40; ++k) { t *= (x / (2 * k)) * (x / (2 * k)); s += t; } return s; };
-    for (int ph = 0; ph < L; ++ph) {
-        double sum = 0; std::vector<double> row(T);
-        for (int t = 0; t < T; ++t) {
-            const double xpos = (double)(t - (T / 2 - 1)) - (double)ph / L;     // distance (in input samples) from the output instant
-            const double w = std::fabs(xpos) >= T / 2 ? 0.0 : bessel0(beta * std::sqrt(1.0 - (xpos / (T / 2)) * (xpos / (T / 2)))) / bessel0(beta);
-            const double arg = 2.0 * M_PI * fc * xpos; const double sinc = std::fabs(arg) < 1e-12 ? 1.0 : std::sin(arg) / arg;
-            row[t] = 2.0 * fc * sinc * w; sum += row[t];
-        }
-        for (int t = 0; t < T; ++t) h[(size_t)ph * T + t] = (float)(row[t] / sum);   // unity DC gain per phase
-    }
-    hipFree(d->d_coef); d->d_coef = nullptr; HIPCHK(hipMalloc((void**)&d->d_coef, h.size() * sizeof(float))); HIPCHK(hipMemcpy(d->d_coef, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    d->coef_L = L; d->coef_M = M; return 0;
-}
-// whole buffer at once
-extern "C" int skw_resample_polyphase(skw_dsp* d, const float* in, long n_in_frames, int channels, int in_rate, int out_rate, float* out, long out_cap_frames, long* out_frames) {
-    char* errbuf = d->errbuf; HIPCHK(hipSetDevice(d->device));
-    int L, M, T; if (dsp_polyphase_coefs(d, in_rate, out_rate, &L, &M, &T)) return -1;
-    if (channels < 1 || channels > 2) { snprintf(errbuf, 512, "resampler: unsupported channel count %d", channels); return -1; }
-    const long n_out = (n_in_frames * L + M - 1) / M;
-    if (n_out > out_cap_frames) { snprintf(errbuf, 512, "resampler: output capacity too small"); return -1; }
-    if (dsp_reserve(d, (size_t)n_in_frames * channels, (size_t)n_out * channels)) return -1;
-    HIPCHK(hipMemcpyAsync(d->d_in, in, sizeof(float) * (size_t)n_in_frames * channels, hipMemcpyHostToDevice, d->stream));
-    skw_resample_polyphase_launch(d->d_in, 0, n_in_frames, n_in_frames, channels, d->d_coef, L, M, T, d->d_out, 0, n_out, d->stream);
-    HIPCHK(hipGetLastError());      // a refused launch (LDS request) must surface as an error, not as stale output
-    HIPCHK(hipMemcpyAsync(out, d->d_out, sizeof(float) * (size_t)n_out * channels, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-    *out_frames = n_out; return 0;
-}
-extern "C" int skw_dsp_last_scan_fallback(const skw_dsp* d) { return d->last_flags[1] ? 2 : ((d->last_flags[0] || d->host_walk_last) ? 1 : 0); }
-
-// streaming polyphase: the input tail the later outputs still need stays on the device; a push uploads only the new frames and
-// computes only the outputs whose filter support has arrived (all remaining ones when `final`).  Identical to the whole-buffer result.
-struct skw_pp_stream { skw_dsp* d; int ch, in_rate, out_rate, L, M, T; float* d_buf = nullptr; size_t cap_frames = 0; long base = 0, total = 0, next = 0; float* d_o = nullptr; size_t cap_o = 0; };
-extern "C" skw_pp_stream* skw_polyphase_stream_create(skw_dsp* d, int channels, int in_rate, int out_rate) {
-    if (hipSetDevice(d->device) != hipSuccess) return nullptr;
-    int L, M, T; if (channels < 1 || channels > 2) { snprintf(d->errbuf, 512, "resampler: unsupported channel count %d", channels); return nullptr; }
-    if (dsp_polyphase_coefs(d, in_rate, out_rate, &L, &M, &T)) return nullptr;
-    skw_pp_stream* p = new skw_pp_stream(); p->d = d; p->ch = channels; p->in_rate = in_rate; p->out_rate = out_rate; p->L = L; p->M = M; p->T = T; return p;
-}
-extern "C" void skw_polyphase_stream_free(skw_pp_stream* p) { if (!p) return; hipSetDevice(p->d->device); hipStreamSynchronize(p->d->stream); hipFree(p->d_buf); hipFree(p->d_o); delete p; }
-extern "C" int skw_polyphase_stream_push(skw_pp_stream* p, const float* in, long n_frames, int final_call, float* out, long out_cap_frames, long* out_frames) {
-    skw_dsp* d = p->d; char* errbuf = d->errbuf; HIPCHK(hipSetDevice(d->device)); *out_frames = 0;
-    int L, M, T; if (dsp_polyphase_coefs(d, p->in_rate, p->out_rate, &L, &M, &T)) return -1;       // the context's table may have served another ratio since
-    const long ch = p->ch;
-    if (n_frames > 0) {
-        const size_t have = (size_t)(p->total - p->base), need = have + (size_t)n_frames;
-        if (need > p->cap_frames) {       // grow (rare: the buffer holds one packet + the retained tail)
-            float* nb = nullptr; const size_t cap = need * 2 + 4096; HIPCHK(hipMalloc((void**)&nb, cap * ch * sizeof(float)));
-            if (have) HIPCHK(hipMemcpyAsync(nb, p->d_buf, have * ch * sizeof(float), hipMemcpyDeviceToDevice, d->stream));
-            HIPCHK(hipStreamSynchronize(d->stream)); hipFree(p->d_buf); p->d_buf = nb; p->cap_frames = cap;
-        }
-        HIPCHK(hipMemcpyAsync(p->d_buf + have * ch, in, (size_t)n_frames * ch * sizeof(float), hipMemcpyHostToDevice, d->stream));
-        p->total += n_frames;
-    }
-    // output m sits at input position floor(m*M/L) and reads frames [pos - (T/2 - 1), pos + T/2]
-    long m_hi;
-    if (final_call) m_hi = (p->total * L + M - 1) / M;
-    else { const long last_pos = p->total - 1 - T / 2; m_hi = last_pos < 0 ? 0 : ((last_pos + 1) * L + M - 1) / M; }
-    const long n_new = m_hi - p->next;
-    if (n_new > 0) {
-        if (n_new > out_cap_frames) { snprintf(errbuf, 512, "resampler: output capacity too small"); return -1; }
-        if ((size_t)n_new > p->cap_o) { hipFree(p->d_o); p->cap_o = (size_t)n_new * 2; HIPCHK(hipMalloc((void**)&p->d_o, p->cap_o * ch * sizeof(float))); }
-        skw_resample_polyphase_launch(p->d_buf, p->base, p->total - p->base, final_call ? p->total : p->total, (int)ch, d->d_coef, L, M, T, p->d_o, p->next, n_new, d->stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out, p->d_o, (size_t)n_new * ch * sizeof(float), hipMemcpyDeviceToHost, d->stream));
-        p->next = m_hi; *out_frames = n_new;
-    }
-    // drop what no later output reads: keep from the support start of output `next`
-    long keep_from = (p->next * M) / L - (T / 2 - 1); if (keep_from < p->base) keep_from = p->base; if (keep_from > p->total) keep_from = p->total;
-    if (keep_from > p->base) {
-        const size_t keep = (size_t)(p->total - keep_from);
-        if (keep) {   // overlapping move on one stream: stage through the output scratch when the ranges overlap
-            if ((size_t)(keep_from - p->base) >= keep) HIPCHK(hipMemcpyAsync(p->d_buf, p->d_buf + (size_t)(keep_from - p->base) * ch, keep * ch * sizeof(float), hipMemcpyDeviceToDevice, d->stream));
-            else {
-                float* tmp = nullptr; HIPCHK(hipMalloc((void**)&tmp, keep * ch * sizeof(float)));
-                HIPCHK(hipMemcpyAsync(tmp, p->d_buf + (size_t)(keep_from - p->base) * ch, keep * ch * sizeof(float), hipMemcpyDeviceToDevice, d->stream));
-                HIPCHK(hipMemcpyAsync(p->d_buf, tmp, keep * ch * sizeof(float), hipMemcpyDeviceToDevice, d->stream)); HIPCHK(hipStreamSynchronize(d->stream)); hipFree(tmp);
-            }
-        }
-        p->base = keep_from;
-    }
-    HIPCHK(hipStreamSynchronize(d->stream));
-    return 0;
-}

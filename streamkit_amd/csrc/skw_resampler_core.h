@@ -34,7 +34,7 @@ struct ResamplerCore {
         while (output_buffer.size() - off >= fs) { if (!sink(output_buffer.data() + off, fs, err)) return false; off += fs; }
         output_buffer.erase(output_buffer.begin(), output_buffer.begin() + off); return true;
     }
-    // frames each of the next n_chunks chunks will produce: the index recurrence of rubato's FastFixedIn (the engine walks the same IEEE additions on long calls, skw_engine.hip
+    // frames each of the next n_chunks chunks will produce: the index recurrence of rubato's FastFixedIn (the engine walks the same IEEE additions on long calls, skw_dsp.hip
     // skw_resample_linear) replayed on the host from the state BEFORE the call — so that a batched GPU call can still be handed on chunk by chunk
     static void chunk_counts(const skw_resampler_state& s, int n_chunks, std::vector<int>* counts) {
         const double t_ratio = 1.0 / s.ratio, end_idx = (double)(s.chunk_frames - 9) - std::ceil(t_ratio); double x0 = s.last_index;

@@ -348,7 +348,7 @@ def _times_out(tt):
     return out
 
 
-class Gemm16EpiArgs(C.Structure):      # struct skw_gemm16_epi_args (skw_engine.hip)
+class Gemm16EpiArgs(C.Structure):      # struct skw_gemm16_epi_args (skw_hooks.hip)
     _fields_ = [("launcher", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("epi", C.c_int32),
                 ("A", C.c_void_p), ("a_halves", C.c_int64), ("lda", C.c_int64), ("a_rows_per_batch", C.c_int32), ("a_batch_stride", C.c_int64), ("a_frag", C.c_int32),
                 ("ln_x", C.c_void_p), ("ln_w", C.c_void_p), ("ln_b", C.c_void_p),
@@ -803,7 +803,7 @@ class Context:
 
     def attn16(self, form, H, n_ctx, Q, K, V, fill_from, k_pad=0x7E00, v_pad=0x7E00, frag=0, ofrag=0, slot_k=None, out_rows=0, row0=None, nq=None, slot=None,
                active=None, seq=None, count=None, sentinel=0x5A5A):
-        """One f16_mfma attention launcher on caller-supplied operands (skw_debug_attn16, skw_engine.hip).  Q [rows][H*64], K / V [slots][n_ctx][H*64] as float16 (or their
+        """One f16_mfma attention launcher on caller-supplied operands (skw_debug_attn16, skw_hooks.hip).  Q [rows][H*64], K / V [slots][n_ctx][H*64] as float16 (or their
         uint16 bit patterns) in natural order; every K / V position of slot s from fill_from[s] up holds the bit pattern k_pad / v_pad when the kernel runs; the output buffer
         starts as `sentinel` in every half.  form: "encoder" (slot_k, out_rows), "prefill" (row0, nq, slot per sequence; frag, ofrag, slot_k), "cross16" / "cross2p" (the one-pass
         and the two-phase decode kernels; active, seq, count = n_keys per row; ofrag) or "self" (count = pos per row; active, seq; ofrag).  -> f32 [rows][H*64], natural order."""
@@ -888,7 +888,7 @@ class Context:
 
     def attn_exact(self, form, H, n_ctx, Q, K, V, fill_from, f32_out=False, raw=False, k_pad=0x7E00, v_pad=0x7E00, slot_k=None, out_rows=0, active=None, seq=None, pos=None,
                    sentinel=0x5A5A):
-        """The exact precision's encoder attention or decoder self attention on caller-supplied operands (skw_debug_attn_exact, skw_engine.hip), through the public launcher.
+        """The exact precision's encoder attention or decoder self attention on caller-supplied operands (skw_debug_attn_exact, skw_hooks.hip), through the public launcher.
         Operands, fill_from, the pads and the sentinel as attn16.  form "encoder": Q [slots][n_ctx][H*64] (slot_k, out_rows); "self": Q [rows][H*64], K / V the caches
         [slots][n_text_ctx][H*64], pos per row (active, seq).  -> (out, kernel): out uint16 [rows][H*64] (f16 bits; kperm order when raw, else natural) or, f32_out, uint32
         [rows][H*64] (the f32 rows' bits); kernel: the encoder kernel the launcher chose (ATTN_ENC_KERNELS), None for "self"."""
@@ -918,7 +918,7 @@ class Context:
 
     def gemm_q8(self, qtype, blocks, N, K, A, segmented, epi, C_buf, ldc=0, bias=None, res_alias=False, scale=1.0, has_scale=0, n_ctx=0, H=0, Tpad=0, pos=None,
                 C2_buf=None, C3_buf=None, ldc2=0):
-        """One product of ggml's arithmetic for quantised files on caller-supplied operands (skw_debug_gemm_q8, skw_engine.hip): `blocks` (bytes: N rows of K / 32 blocks of ggml
+        """One product of ggml's arithmetic for quantised files on caller-supplied operands (skw_debug_gemm_q8, skw_hooks.hip): `blocks` (bytes: N rows of K / 32 blocks of ggml
         type qtype) go through the model loader's repack, A (f32 [M][lda >= K]: the first K columns are the rows) through skw_q8_quantize, then skw_gemm_q8 — the public
         launchers, dispatch included.  C_buf (and C2_buf / C3_buf for EPI_DEC_QKV) are flat arrays holding what the output buffers hold BEFORE the launch: the caller's sentinel
         with its margin (res_alias: the residual in C's M x N region); they are not modified.  -> (kernel id, C, C2, C3): the buffers after the launch."""
@@ -938,7 +938,7 @@ class Context:
 
     def gemm16_epi(self, launcher, N, K, epi, W, C_buf, A=None, lda=0, a_rows_per_batch=0, a_batch_stride=0, a_frag=False, M=None, ln=None, use_wf=False, bias=None, res=None,
                    res_alias=False, scale=1.0, has_scale=0, pe=None, n_ctx=0, H=0, Tpad=0, frag=False, c_frag=False, pos=None, force_small=False, ldc=0, C2_buf=None, C3_buf=None, ldc2=0):
-        """One f16_mfma product on caller-supplied operands through the public launchers (skw_debug_gemm16_epi, skw_engine.hip).  launcher: 0 skw_gemm16 as k_gemm16w, 1 as k_gemm16,
+        """One f16_mfma product on caller-supplied operands through the public launchers (skw_debug_gemm16_epi, skw_hooks.hip).  launcher: 0 skw_gemm16 as k_gemm16w, 1 as k_gemm16,
         2 skw_gemm16_small, 3 skw_gemm16_small_lnA.  A: flat uint16 array of f16 bits (rows at lda, the batch-strided rows of conv2, or the fragment-order image) or, launcher 3,
         ln = (x f32 [M][K], gain [K], bias [K]); W uint16 [N][K].  C_buf (C2_buf / C3_buf) hold what the output buffers hold BEFORE the launch — the caller's sentinel with its
         margins, the residual when res_alias — and are not modified.  -> (rc, kernel id, C, C2, C3): rc 0, or -2 when the launcher refuses the arguments; -1 raises."""

@@ -1,7 +1,7 @@
 """The f16_mfma attention kernels, each on its own against a float64 softmax(scale Q K^T) V under a derived bound (tests/attn_ref_lib.py has the reference, the bound, the operands
 and the case list; tests/test_cpu_attn_cases.py shows on the CPU that an off-by-one in the key count cannot pass these cases).
 
-What runs, through the public launchers (skw_debug_attn16, skw_engine.hip): k_attn_encoder16 in its encoder, prompt-pass (XP) and per-clip (VARK) forms, k_dec_cross_attn16<3,3> and
+What runs, through the public launchers (skw_debug_attn16, skw_hooks.hip): k_attn_encoder16 in its encoder, prompt-pass (XP) and per-clip (VARK) forms, k_dec_cross_attn16<3,3> and
 <3,3,true>, the two-phase k_dec_cross_attn<24,4,3,true> and the FASTV form of k_dec_attn — at the real strides (n_ctx 1500, Tpad 1504) with key counts on either side of every block
 edge, H = 4 (a cross-attention workgroup's third head slot is invalid) and H = 6 (the self attention's four-head block is ragged), inactive rows, rows mapped to another sequence.
 Every K / V position a kernel must not use is poisoned: NaN in K; NaN in V where the kernel promises to replace it, 1000.0 where it relies on p = 0.

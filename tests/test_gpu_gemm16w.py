@@ -2,7 +2,7 @@
 vector-memory queues counted by hand (`s_waitcnt vmcnt(8)` / `vmcnt(4)`) — held BIT FOR BIT to k_gemm16 (both operands through LDS, compiler-counted waits) on seeded operands,
 for every epilogue, ragged and whole tile counts, short and long contractions, and every feature-split tile walk.  This is the regression cover of the round-4 memory fault
 (look-ahead weight loads still in flight when their registers were reused: `skw_kernels_f16.hip`, the final wait of the K loop): a later edit that miscounts a queue changes bits
-here before it faults anywhere.  One product per case through `skw_debug_gemm16_compare` (streamkit_amd/csrc/skw_engine.hip), which launches both kernels and compares every byte."""
+here before it faults anywhere.  One product per case through `skw_debug_gemm16_compare` (streamkit_amd/csrc/skw_hooks.hip), which launches both kernels and compares every byte."""
 import ctypes as C
 
 import numpy as np
