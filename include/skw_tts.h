@@ -69,6 +69,31 @@ long skw_tts_debug_get(skw_tts*, int what, float* out, long cap);
 void skw_tts_debug_conv_mode(int mode);
 /* which LSTM kernel: 0 automatic, 1 one workgroup per direction, 2 H / 32 workgroups per direction with the recurrent weights resident in LDS (bit-identical, asserted by a test) */
 void skw_tts_debug_lstm_mode(int mode);
+/* which tile every LDS-tiled launch takes: (0, 0) automatic, otherwise k_tts_conv_t<mt, nt> for (1,2), (1,4), (1,8) or (2,8); any other pair is refused (-1) and changes nothing.
+ * With conv mode 0 a launch that would be untiled stays untiled; with conv mode 2 every launch goes through the forced tile.  Same chain: bit-identical. */
+int skw_tts_debug_conv_tile(int mt, int nt);
+/* host-side launch counters since the last reset (process-wide, like the switches): [0] k_tts_conv, [1] k_tts_conv_t<1,2>, [2] <1,4>, [3] <1,8>, [4] <2,8>, [5] k_tts_convtr (direct form),
+ * [6] ConvTranspose1d calls run per phase on the conv kernels, [7] their per-phase launches (also counted in [0..4]), [8] k_tts_lstm, [9] k_tts_lstm_mw,
+ * [10] the most workgroups per direction a k_tts_lstm_mw launch had.  Copies min(n, count) values, returns the count; reset != 0 zeroes them afterwards. */
+int skw_tts_debug_launch_counts(long* out, int n, int reset);
+/* the multi-workgroup LSTM's launch epoch (20 bits; the next launch takes epoch + 1, and 2^20 wraps to 1 after clearing the exchange words), its current value, and the
+ * engine's own error word (0 unless a wait of a model call timed out) */
+void skw_tts_debug_lstm_epoch(skw_tts*, unsigned epoch);
+unsigned skw_tts_debug_lstm_epoch_get(skw_tts*);
+int skw_tts_debug_lstm_error(skw_tts*);
+/* ---- one operator at a time, from host arrays (include/skw_kokoro_ops.h generates these and the checker's skwo_kokoro_op_* from one text): the weights get the device images a
+ * model's get, the result is copied back (min(count, cap) floats) and everything uploaded is freed.  Activations are row-major [T][C]; the engine lends its stream and arena and is
+ * otherwise left as found.  Returns the result's element count, -1 on a device failure, -2 for impossible arguments, -3 when the LSTM's workgroups timed out. ---- */
+long skw_tts_debug_op_conv(skw_tts*, const float* x, int T, int Ci, const float* w /* [Co][Ci][K] */, int Co, int K, const float* bias /* or NULL */, int stride, int dil, int pad,
+                           float* out, long cap);
+long skw_tts_debug_op_convtr(skw_tts*, const float* x, int T, const float* w /* [Ci][Co][K]; depthwise [C][1][K] */, int Ci, int Co, int K, const float* bias, int stride, int pad, int out_pad,
+                             int depthwise, float* out, long cap);
+long skw_tts_debug_op_layernorm(skw_tts*, const float* x, int T, int C, const float* gamma, const float* beta, float eps, float* out, long cap);
+long skw_tts_debug_op_ada_ln(skw_tts*, const float* x, int T, int C, const float* gb /* [2 C] gamma | beta */, float* out, long cap);
+long skw_tts_debug_op_ada_in_act(skw_tts*, const float* x, int T, int C, const float* gb, int act /* 0..2 LeakyReLU 0.2 / 0.1 / 0.01, 3 gelu_new */, float* out, long cap);
+long skw_tts_debug_op_attention(skw_tts*, const float* q, const float* k, const float* v, int T, int heads /* x 64 channels */, float* out, long cap);
+/* ws[8]: per direction weight_ih [4H][In], weight_hh [4H][H], bias_ih [4H], bias_hh [4H]; H <= 256 and independent of the loaded model's (own exchange and error words) */
+long skw_tts_debug_op_lstm_bi(skw_tts*, const float* x, int T, int In, int H, const float* const* ws, float* out, long cap);
 /* timing of the last generate (GPU events): milliseconds */
 float skw_tts_last_ms(const skw_tts*);
 

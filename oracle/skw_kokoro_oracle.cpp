@@ -7,6 +7,7 @@
  * vector; the architecture is the published one as recalled (header of skw_kokoro_net.h).  Only tests/ may load this.
  */
 #include "../include/skw_kokoro_net.h"
+#include "../include/skw_kokoro_ops.h"
 #include "../include/skw_math.h"
 #include <algorithm>
 #include <cstring>
@@ -247,7 +248,21 @@ struct CpuBackend {
         return y;
     }
 };
+/* the checker's side of include/skw_kokoro_ops.h: host arrays are the backend's buffers already, and a weight needs nothing attached */
+struct CpuOpSide {
+    CpuBackend b;
+    explicit CpuOpSide(const void*) {}
+    CpuBackend& be() { return b; }
+    CpuBackend::Buf in(const float* p, int T, int C) { CpuBackend::Buf x = CpuBackend::make(T, C); memcpy(x.data(), p, sizeof(float) * (size_t)T * C); return x; }
+    bool attach(Tensor&, Role) { return true; }
+    long out(const CpuBackend::Buf& o, float* dst, long cap) { const long n = (long)o.T * o.C; if (dst) memcpy(dst, o.data(), sizeof(float) * (size_t)std::min(n, cap)); return n; }
+    bool begin_lstm(int) { return true; }
+    void end_lstm() {}
+};
 }  // namespace
+
+/* one operator at a time (tests/kokoro_ops_lib.py): skwo_kokoro_op_conv, _convtr, _layernorm, _ada_ln, _ada_in_act, _attention, _lstm_bi */
+SKW_KOKORO_OP_EXPORTS(skwo_kokoro_op_, const void*, CpuOpSide)
 
 extern "C" {
 typedef struct { const char* name; const float* data; int32_t n_dims; int64_t dims[4]; } skwo_tts_tensor;

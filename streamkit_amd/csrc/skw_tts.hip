@@ -12,6 +12,7 @@
 // What differs between the two backends is the platform's sin / cos / atan2 (Snake, source, STFT): a few ulps, bounded by the tests' waveform tolerance.
 #include "../../include/skw_tts.h"
 #include "../../include/skw_kokoro_net.h"
+#include "../../include/skw_kokoro_ops.h"
 #include "../../include/skw_math.h"
 #include "skw_silero.h"      // the ONNX initializer reader (skw::onnx)
 #include "skw_tts_text.h"
@@ -21,6 +22,7 @@
 #include <cstdarg>
 #include <cstring>
 #include <mutex>
+#include <stdexcept>
 
 using namespace skw::kokoro;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -428,7 +430,21 @@ __global__ void k_tts_istft(const float* o, int P, float* y, long n_out) {
 // ------------------------------------------------------------------ engine
 static int g_conv_mode = 0;      // skw_tts_debug_conv_mode: 0 automatic, 1 the untiled kernel, 2 the tiled one
 static int g_lstm_mode = 0;      // skw_tts_debug_lstm_mode: 0 automatic, 1 one workgroup per direction, 2 H / 32 workgroups per direction
+static int g_conv_mt = 0, g_conv_nt = 0;      // skw_tts_debug_conv_tile: (0, 0) automatic, otherwise the k_tts_conv_t<MT, NT> every tiled launch takes
+// skw_tts_debug_launch_counts: host-side launch counters (tests prove with them that a forced run ran what it forced).  Plain integers bumped where the launch is chosen.
+enum { CNT_CONV = 0, CNT_T12, CNT_T14, CNT_T18, CNT_T28, CNT_CONVTR_DIRECT, CNT_CONVTR_PHASED, CNT_CONVTR_PHASE_LAUNCHES, CNT_LSTM, CNT_LSTM_MW, CNT_LSTM_MW_MAX_WG, CNT_N };
+static long g_counts[CNT_N] = {0};
 extern "C" void skw_tts_debug_conv_mode(int mode) { g_conv_mode = mode; }
+extern "C" int skw_tts_debug_conv_tile(int mt, int nt) {
+    const bool ok = (mt == 0 && nt == 0) || (mt == 1 && (nt == 2 || nt == 4 || nt == 8)) || (mt == 2 && nt == 8);
+    if (ok) { g_conv_mt = mt; g_conv_nt = nt; }
+    return ok ? 0 : -1;
+}
+extern "C" int skw_tts_debug_launch_counts(long* out, int n, int reset) {
+    for (int i = 0; out && i < n && i < CNT_N; ++i) out[i] = g_counts[i];
+    if (reset) for (int i = 0; i < CNT_N; ++i) g_counts[i] = 0;
+    return CNT_N;
+}
 extern "C" void skw_tts_debug_lstm_mode(int mode) { g_lstm_mode = mode; }
 struct skw_tts {
     int device = 0; hipStream_t stream = nullptr; std::mutex mu; char errbuf[512] = {0};
@@ -438,6 +454,8 @@ struct skw_tts {
     // scratch arena: chunks kept for the engine's life, bump-allocated per call (a call's buffers are all live until it ends)
     struct Chunk { char* p; size_t cap; }; std::vector<Chunk> chunks; size_t cur_chunk = 0, cur_off = 0; bool arena_failed = false;
     unsigned long long* lstm_sync = nullptr; unsigned lstm_epoch = 0;      // [4 H] tagged h exchange words (two step parities x two directions) | [1] error flag (low half of a word)
+    int lstm_H = 0; unsigned long long* own_sync = nullptr;      // the H lstm_sync is laid out for: the model's (own_sync == lstm_sync), except while an operator hook has swapped in its own
+    unsigned long long* hook_sync = nullptr; int hook_H = 0;     // skw_tts_debug_op_lstm_bi: exchange words + error word for the widest H a hook has run, kept across hook calls
     bool taps_on = false; std::vector<float> dbg[9]; float last_ms = 0.0f;
 };
 static void* dev_upload(skw_tts* t, const void* h, size_t bytes) {
@@ -486,15 +504,28 @@ struct GpuBackend {
     // 0 = tiled when the launch is long enough to fill tiles
     template <int MT, int NT> void launch_conv_t(const float* x, int T, int Ci, const float* wp, int Co, int Co16, const float* bias, int K, int stride, int dil,
         int pad, int To, float* out, int os, int oo) {
+        ++g_counts[MT == 2 ? CNT_T28 : NT == 8 ? CNT_T18 : NT == 4 ? CNT_T14 : CNT_T12];
         hipLaunchKernelGGL((k_tts_conv_t<MT, NT>), dim3((To + 16 * NT - 1) / (16 * NT), (Co16 + 64 * MT - 1) / (64 * MT)), dim3(256), 0, s, x, T, Ci, wp, Co, Co16, bias,
             K, stride, dil, pad, To, out, os, oo);
     }
     void launch_conv(const float* x, int T, int Ci, const float* wp, int Co, const float* bias, int K, int stride, int dil, int pad, int To, float* out, int os = 1, int oo = 0) {
         const int Co16 = (Co + 15) & ~15, mode = g_conv_mode;
         const bool tiled = mode == 2 || (mode != 1 && To >= 32 && (long)K * Ci >= 32);
-        if (!tiled) { hipLaunchKernelGGL(k_tts_conv, dim3((To + 63) / 64, (Co16 + 63) / 64), dim3(256), 0, s, x, T, Ci, wp, Co, Co16, bias, K, stride, dil, pad, To, out, os, oo); return; }
+        if (!tiled) {
+            ++g_counts[CNT_CONV];
+            hipLaunchKernelGGL(k_tts_conv, dim3((To + 63) / 64, (Co16 + 63) / 64), dim3(256), 0, s, x, T, Ci, wp, Co, Co16, bias, K, stride, dil, pad, To, out, os, oo);
+            return;
+        }
         // the largest tile that still gives the 256 CUs a workgroup each (the chain does not allow splitting k, so a short launch can only spread by smaller tiles)
         auto wgs = [&](int mt, int nt) { return (long)((To + 16 * nt - 1) / (16 * nt)) * ((Co16 + 64 * mt - 1) / (64 * mt)); };
+        const int fmt = g_conv_mt, fnt = g_conv_nt;      // a forced tile (skw_tts_debug_conv_tile) replaces the choice below, nothing else
+        if (fmt) {
+            if (fmt == 2) launch_conv_t<2, 8>(x, T, Ci, wp, Co, Co16, bias, K, stride, dil, pad, To, out, os, oo);
+            else if (fnt == 8) launch_conv_t<1, 8>(x, T, Ci, wp, Co, Co16, bias, K, stride, dil, pad, To, out, os, oo);
+            else if (fnt == 4) launch_conv_t<1, 4>(x, T, Ci, wp, Co, Co16, bias, K, stride, dil, pad, To, out, os, oo);
+            else launch_conv_t<1, 2>(x, T, Ci, wp, Co, Co16, bias, K, stride, dil, pad, To, out, os, oo);
+            return;
+        }
         if (Co16 > 64 && wgs(2, 8) >= 256) launch_conv_t<2, 8>(x, T, Ci, wp, Co, Co16, bias, K, stride, dil, pad, To, out, os, oo);
         else if (wgs(1, 8) >= 256) launch_conv_t<1, 8>(x, T, Ci, wp, Co, Co16, bias, K, stride, dil, pad, To, out, os, oo);
         else if (wgs(1, 4) >= 256) launch_conv_t<1, 4>(x, T, Ci, wp, Co, Co16, bias, K, stride, dil, pad, To, out, os, oo);
@@ -516,14 +547,17 @@ struct GpuBackend {
         const float* bp = bias ? dev(*bias) : nullptr;
         if (depthwise) { hipLaunchKernelGGL(k_tts_convtr_dw, dim3(blocks((long)To * Co)), dim3(256), 0, s, x.p, x.T, Ci, dev(w), bp, K, stride, pad, To, o.p); return o; }
         if (g_conv_mode == 1 || !w.packed2 || K != 2 * stride) {
+            ++g_counts[CNT_CONVTR_DIRECT];
             hipLaunchKernelGGL(k_tts_convtr, dim3(blocks((long)To * Co)), dim3(256), 0, s, x.p, x.T, Ci, (const float*)w.packed, Co, bp, K, stride, pad, To, o.p);
             return o;
         }
+        ++g_counts[CNT_CONVTR_PHASED];
         const int Co16 = (Co + 15) & ~15, taps = K / stride; const size_t img = (size_t)((taps * Ci + 3) / 4) * Co16 * 4;
         for (int f = 0; f < stride; ++f) {
             const int q0 = (pad - f + stride - 1) / stride > 0 ? (pad - f + stride - 1) / stride : 0;      // first q with u = q stride + f - pad >= 0
             const int u0 = q0 * stride + f - pad; if (u0 >= To) continue;
             const int rows = (To - 1 - u0) / stride + 1;
+            ++g_counts[CNT_CONVTR_PHASE_LAUNCHES];
             launch_conv(x.p, x.T, Ci, (const float*)w.packed2 + (size_t)f * img, Co, bp, taps, 1, -1, -q0, rows, o.p, stride, u0);
         }
         return o;
@@ -584,14 +618,20 @@ struct GpuBackend {
         }
         if (!o.p || !xp[0].p || !xp[1].p) return o;
         const bool multi = H % 32 == 0 && x.T < 4096 && (g_lstm_mode == 2 || (g_lstm_mode != 1 && x.T >= 8));
-        if (!multi)
+        if (!multi) {
+            ++g_counts[CNT_LSTM];
             hipLaunchKernelGGL(k_tts_lstm, dim3(2), dim3(1024), sizeof(float) * 5 * H, s, xp[0].p, xp[1].p, (const float*)ws[1]->packed, (const float*)ws[5]->packed,
                 dev(*ws[3]), dev(*ws[7]), x.T, H, o.p);
-        else {
+        } else {
+            ++g_counts[CNT_LSTM_MW]; g_counts[CNT_LSTM_MW_MAX_WG] = std::max<long>(g_counts[CNT_LSTM_MW_MAX_WG], H / 32);
             t->lstm_epoch = (t->lstm_epoch + 1) & 0xFFFFFu;      // 20 bits of launch epoch + 12 bits of step in a word's tag (T <= TTS_MAX_FRAMES < 4096)
-            if (t->lstm_epoch == 0) { hipMemsetAsync(t->lstm_sync, 0, sizeof(unsigned long long) * 4 * t->g.H, s); t->lstm_epoch = 1; }
+            if (t->lstm_epoch == 0) {      // the epoch wrapped: words tagged in the engine's early life must not match again (the hooks' words share the epoch counter)
+                hipMemsetAsync(t->own_sync, 0, sizeof(unsigned long long) * 4 * t->g.H, s);
+                if (t->hook_sync) hipMemsetAsync(t->hook_sync, 0, sizeof(unsigned long long) * 4 * t->hook_H, s);
+                t->lstm_epoch = 1;
+            }
             hipLaunchKernelGGL(k_tts_lstm_mw, dim3(2 * (H / 32)), dim3(128), sizeof(float) * ((size_t)H * 128 + H + 128), s, xp[0].p, xp[1].p, (const float*)ws[1]->packed,
-                (const float*)ws[5]->packed, dev(*ws[3]), dev(*ws[7]), x.T, H, o.p, t->lstm_sync, t->lstm_epoch, (int*)(t->lstm_sync + 4 * t->g.H));
+                (const float*)ws[5]->packed, dev(*ws[3]), dev(*ws[7]), x.T, H, o.p, t->lstm_sync, t->lstm_epoch, (int*)(t->lstm_sync + 4 * t->lstm_H));
         }
         return o;
     }
@@ -623,39 +663,47 @@ struct GpuBackend {
 };
 
 // weights to the device: every tensor as it is, plus the image its consumer reads — conv / linear weights [Co][Ci][K] as the MFMA's first operand
-// [k / 4][Co padded to 16][4] (k = tap * Ci + ci), ConvTranspose1d weights [Ci][Co][K] as [tap][ci][co], recurrent LSTM weights [4H][H] transposed
-static bool upload_weights(skw_tts* t, std::string* err) {
-    for (auto& kv : t->w) {
-        Tensor& w = kv.second; const std::string& n = kv.first;
-        w.dev = dev_upload(t, w.host.data(), w.host.size() * sizeof(float));
-        if (!w.dev) { *err = "device allocation failed for '" + n + "'"; return false; }
-        const bool is_tr = n.find("generator.ups.") != std::string::npos && n.size() > 7 && n.compare(n.size() - 7, 7, ".weight") == 0;
-        const bool is_hh = n.find("weight_hh_l0") != std::string::npos;
-        const bool is_pool = n.find("pool.weight") != std::string::npos;
-        std::vector<float> img;
-        if (is_tr && w.dims[2] % 2 == 0) {      // the matrix-core form: one image per output phase, stride = K / 2 (Kokoro's up-sampling layers: k = 2 x stride)
-            const int64_t Ci = w.dims[0], Co = w.dims[1], K = w.dims[2], st = K / 2, Co16 = (Co + 15) & ~15, nk4 = (2 * Ci + 3) / 4;
-            std::vector<float> ph((size_t)(st * nk4 * Co16 * 4), 0.0f);
-            for (int64_t f = 0; f < st; ++f) for (int64_t m = 0; m < 2; ++m) for (int64_t ci = 0; ci < Ci; ++ci) for (int64_t co = 0; co < Co; ++co) {
-                const int64_t kk = m * Ci + ci; ph[(size_t)(((f * nk4 + (kk >> 2)) * Co16 + co) * 4 + (kk & 3))] = w.host[(size_t)((ci * Co + co) * K + f + m * st)]; }
-            w.packed2 = dev_upload(t, ph.data(), ph.size() * sizeof(float));
-            if (!w.packed2) { *err = "device allocation failed for '" + n + "'"; return false; }
-        }
-        if (is_tr) {
-            const int64_t Ci = w.dims[0], Co = w.dims[1], K = w.dims[2]; img.resize(w.host.size());
-            for (int64_t ci = 0; ci < Ci; ++ci) for (int64_t co = 0; co < Co; ++co) for (int64_t k = 0; k < K; ++k) img[(size_t)((k * Ci + ci) * Co + co)] = w.host[(size_t)((ci * Co + co) * K + k)];
-        } else if (is_hh) {
-            const int64_t G4 = w.dims[0], H = w.dims[1]; img.resize(w.host.size());
-            for (int64_t gi = 0; gi < G4; ++gi) for (int64_t k = 0; k < H; ++k) img[(size_t)(k * G4 + gi)] = w.host[(size_t)(gi * H + k)];
-        } else if (!is_pool && (w.dims.size() == 3 || (w.dims.size() == 2 && n.size() > 7 && n.compare(n.size() - 7, 7, ".weight") == 0
-            && n.find("embeddings.") == std::string::npos && n.find(".embedding.") == std::string::npos) || n.find("weight_ih_l0") != std::string::npos)) {
-            const int64_t Co = w.dims[0], Ci = w.dims[1], K = w.dims.size() == 3 ? w.dims[2] : 1, Co16 = (Co + 15) & ~15, Kt = K * Ci, nk4 = (Kt + 3) / 4;
-            img.assign((size_t)(nk4 * Co16 * 4), 0.0f);
-            for (int64_t co = 0; co < Co; ++co) for (int64_t ci = 0; ci < Ci; ++ci) for (int64_t k = 0; k < K; ++k) {
-                const int64_t kk = k * Ci + ci; img[(size_t)(((kk >> 2) * Co16 + co) * 4 + (kk & 3))] = w.host[(size_t)((co * Ci + ci) * K + k)]; }
-        }
-        if (!img.empty()) { w.packed = dev_upload(t, img.data(), img.size() * sizeof(float)); if (!w.packed) { *err = "device allocation failed for '" + n + "'"; return false; } }
+// [k / 4][Co padded to 16][4] (k = tap * Ci + ci), ConvTranspose1d weights [Ci][Co][K] as [tap][ci][co], recurrent LSTM weights [4H][H] transposed.
+// Which image follows from the tensor's name (role_of); attach_images builds it — for upload_weights and for the operator hooks (skw_tts_debug_op_*) alike.
+static Role role_of(const std::string& n, const Tensor& w) {
+    const bool is_weight = n.size() > 7 && n.compare(n.size() - 7, 7, ".weight") == 0;
+    if (n.find("generator.ups.") != std::string::npos && is_weight) return ROLE_CONVTR;
+    if (n.find("weight_hh_l0") != std::string::npos) return ROLE_HH;
+    if (n.find("pool.weight") != std::string::npos) return ROLE_PLAIN;
+    if (w.dims.size() == 3 || (w.dims.size() == 2 && is_weight && n.find("embeddings.") == std::string::npos && n.find(".embedding.") == std::string::npos)
+        || n.find("weight_ih_l0") != std::string::npos) return ROLE_CONV;
+    return ROLE_PLAIN;
+}
+static bool attach_images(skw_tts* t, Tensor& w, Role role) {
+    w.dev = dev_upload(t, w.host.data(), w.host.size() * sizeof(float));
+    if (!w.dev) return false;
+    std::vector<float> img;
+    if (role == ROLE_CONVTR && w.dims[2] % 2 == 0) {      // the matrix-core form: one image per output phase, stride = K / 2 (Kokoro's up-sampling layers: k = 2 x stride)
+        const int64_t Ci = w.dims[0], Co = w.dims[1], K = w.dims[2], st = K / 2, Co16 = (Co + 15) & ~15, nk4 = (2 * Ci + 3) / 4;
+        std::vector<float> ph((size_t)(st * nk4 * Co16 * 4), 0.0f);
+        for (int64_t f = 0; f < st; ++f) for (int64_t m = 0; m < 2; ++m) for (int64_t ci = 0; ci < Ci; ++ci) for (int64_t co = 0; co < Co; ++co) {
+            const int64_t kk = m * Ci + ci; ph[(size_t)(((f * nk4 + (kk >> 2)) * Co16 + co) * 4 + (kk & 3))] = w.host[(size_t)((ci * Co + co) * K + f + m * st)]; }
+        w.packed2 = dev_upload(t, ph.data(), ph.size() * sizeof(float));
+        if (!w.packed2) return false;
     }
+    if (role == ROLE_CONVTR) {
+        const int64_t Ci = w.dims[0], Co = w.dims[1], K = w.dims[2]; img.resize(w.host.size());
+        for (int64_t ci = 0; ci < Ci; ++ci) for (int64_t co = 0; co < Co; ++co) for (int64_t k = 0; k < K; ++k) img[(size_t)((k * Ci + ci) * Co + co)] = w.host[(size_t)((ci * Co + co) * K + k)];
+    } else if (role == ROLE_HH) {
+        const int64_t G4 = w.dims[0], H = w.dims[1]; img.resize(w.host.size());
+        for (int64_t gi = 0; gi < G4; ++gi) for (int64_t k = 0; k < H; ++k) img[(size_t)(k * G4 + gi)] = w.host[(size_t)(gi * H + k)];
+    } else if (role == ROLE_CONV) {
+        const int64_t Co = w.dims[0], Ci = w.dims[1], K = w.dims.size() == 3 ? w.dims[2] : 1, Co16 = (Co + 15) & ~15, Kt = K * Ci, nk4 = (Kt + 3) / 4;
+        img.assign((size_t)(nk4 * Co16 * 4), 0.0f);
+        for (int64_t co = 0; co < Co; ++co) for (int64_t ci = 0; ci < Ci; ++ci) for (int64_t k = 0; k < K; ++k) {
+            const int64_t kk = k * Ci + ci; img[(size_t)(((kk >> 2) * Co16 + co) * 4 + (kk & 3))] = w.host[(size_t)((co * Ci + ci) * K + k)]; }
+    }
+    if (!img.empty()) { w.packed = dev_upload(t, img.data(), img.size() * sizeof(float)); if (!w.packed) return false; }
+    return true;
+}
+static bool upload_weights(skw_tts* t, std::string* err) {
+    for (auto& kv : t->w)
+        if (!attach_images(t, kv.second, role_of(kv.first, kv.second))) { *err = "device allocation failed for '" + kv.first + "'"; return false; }
     return true;
 }
 
@@ -683,6 +731,7 @@ static skw_tts* create_impl(const skw_tts_config* cfg, char* err, size_t errlen)
         std::vector<unsigned long long> z((size_t)4 * t->g.H + 1, 0ull);
         t->lstm_sync = (unsigned long long*)dev_upload(t, z.data(), z.size() * sizeof(unsigned long long));
         if (!t->lstm_sync) return fail("device allocation failed for the LSTM exchange buffers");
+        t->own_sync = t->lstm_sync; t->lstm_H = t->g.H;
         if (hipFuncSetAttribute((const void*)k_tts_lstm_mw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * ((size_t)t->g.H * 128 + t->g.H + 128))) != hipSuccess)
             return fail("hipFuncSetAttribute failed for the LSTM kernel");
     }
@@ -702,6 +751,7 @@ extern "C" void skw_tts_destroy(skw_tts* t) {
     if (!t) return; hipSetDevice(t->device);
     if (t->stream) { hipStreamSynchronize(t->stream); hipStreamDestroy(t->stream); }
     for (void* p : t->allocs) hipFree(p);
+    if (t->hook_sync) hipFree(t->hook_sync);
     for (auto& c : t->chunks) hipFree(c.p);
     delete t;
 }
@@ -752,8 +802,8 @@ static const skw_tts_audio* generate_impl(skw_tts* t, const char* text, int32_t 
         || hipGetLastError() != hipSuccess) {
         free(host); return fail("synthesis kernels failed"); }
     hipEventElapsedTime(&t->last_ms, ev.a, ev.b);
-    {   int lstm_err = 0; hipMemcpy(&lstm_err, t->lstm_sync + 4 * t->g.H, sizeof(int), hipMemcpyDeviceToHost);
-        if (lstm_err) { hipMemset(t->lstm_sync + 4 * t->g.H, 0, sizeof(int)); free(host); return fail("LSTM workgroups timed out waiting for each other (GPU oversubscribed?)"); } }
+    {   int lstm_err = 0; hipMemcpy(&lstm_err, t->lstm_sync + 4 * t->lstm_H, sizeof(int), hipMemcpyDeviceToHost);
+        if (lstm_err) { hipMemset(t->lstm_sync + 4 * t->lstm_H, 0, sizeof(int)); free(host); return fail("LSTM workgroups timed out waiting for each other (GPU oversubscribed?)"); } }
     if (t->taps_on) {      // stage taps for the parity tests (skw_tts_debug_enable): 0 durations, 1 F0, 2 N, 3 decoder output, 4 spectrum + phase, 5 bert, 6 d_en, 7 t_en, 8 source STFT
         auto grab = [&](int k, const GpuBackend::Buf& b) { t->dbg[k].resize((size_t)b.T * b.C); hipMemcpy(t->dbg[k].data(), b.p, sizeof(float) * t->dbg[k].size(), hipMemcpyDeviceToHost); };
         t->dbg[0].assign(out.dur.begin(), out.dur.end());
@@ -772,3 +822,68 @@ extern "C" const skw_tts_audio* skw_tts_generate_ids(skw_tts* t, const int32_t* 
     try { return generate_impl(t, nullptr, sid, speed, ids, n_ids); } catch (const std::exception& e) { snprintf(t->errbuf, sizeof t->errbuf, "skw_tts_generate_ids: %s", e.what()); return nullptr; }
 }
 extern "C" void skw_tts_destroy_audio(const skw_tts_audio* a) { if (!a) return; free((void*)a->samples); free((void*)a); }
+
+// ------------------------------------------------------------------ operator hooks for the tests (include/skw_kokoro_ops.h; tests/test_gpu_kokoro_ops.py)
+// One GpuBackend operator on host inputs and host weights: the weights get the device images upload_weights gives a model's (attach_images), the inputs go to the arena, the result
+// comes back, and whatever was uploaded is freed.  Outputs are arena buffers and are NOT cleared first: with allocation poisoning on, the whole arena is NaNs again before every
+// hook call, so an element the operator left unwritten shows.
+static size_t lstm_mw_lds(int H) { return sizeof(float) * ((size_t)H * 128 + H + 128); }
+struct GpuOpSide {
+    typedef GpuBackend::Buf Buf;
+    static skw_tts* need(skw_tts* t) { if (!t) throw std::runtime_error("null engine"); return t; }
+    skw_tts* t; std::unique_lock<std::mutex> lock; GpuBackend b; size_t mark; bool ok = true, in_lstm = false;
+    unsigned long long* saved_sync = nullptr; int saved_H = 0;
+    explicit GpuOpSide(skw_tts* t_) : t(need(t_)), lock(t_->mu), b(t_), mark(t_->allocs.size()) {
+        hipSetDevice(t->device); t->cur_chunk = 0; t->cur_off = 0; t->arena_failed = false;
+        if (g_tts_alloc_poison) for (auto& c : t->chunks) hipMemsetAsync(c.p, 0xFF, c.cap, t->stream);
+    }
+    ~GpuOpSide() {
+        hipStreamSynchronize(t->stream); end_lstm();
+        while (t->allocs.size() > mark) { hipFree(t->allocs.back()); t->allocs.pop_back(); }
+    }
+    GpuBackend& be() { return b; }
+    Buf in(const float* p, int T, int C) {
+        Buf x = b.make(T, C);
+        if (!x.p || hipMemcpyAsync(x.p, p, sizeof(float) * (size_t)T * C, hipMemcpyHostToDevice, t->stream) != hipSuccess) ok = false;
+        return x;
+    }
+    bool attach(Tensor& w, Role role) { return attach_images(t, w, role); }
+    long out(const Buf& o, float* dst, long cap) {
+        if (!ok || !o.p || t->arena_failed) { hipStreamSynchronize(t->stream); return -1; }
+        const long n = (long)o.T * o.C;
+        if (dst && cap > 0 && hipMemcpyAsync(dst, o.p, sizeof(float) * (size_t)std::min(n, cap), hipMemcpyDeviceToHost, t->stream) != hipSuccess) return -1;
+        if (hipStreamSynchronize(t->stream) != hipSuccess || hipGetLastError() != hipSuccess) return -1;
+        if (in_lstm) {      // the hook's own error word (the engine's is untouched)
+            int e = 0; hipMemcpy(&e, t->lstm_sync + 4 * t->lstm_H, sizeof(int), hipMemcpyDeviceToHost);
+            if (e) { hipMemset(t->lstm_sync + 4 * t->lstm_H, 0, sizeof(int)); return -3; }
+        }
+        return n;
+    }
+    // k_tts_lstm_mw at the hook's H: exchange words and an error word of the hook's own (kept across hook calls, so that consecutive launches meet each other's stale tags as
+    // the engine's do), the dynamic-LDS limit for this H; end_lstm puts the engine's back
+    bool begin_lstm(int H) {
+        if (H > t->hook_H) {
+            unsigned long long* p = nullptr; const size_t bytes = sizeof(unsigned long long) * ((size_t)4 * H + 1);
+            if (hipMalloc((void**)&p, bytes) != hipSuccess) return false;
+            if (hipMemset(p, 0, bytes) != hipSuccess) { hipFree(p); return false; }
+            if (t->hook_sync) hipFree(t->hook_sync);
+            t->hook_sync = p; t->hook_H = H;
+        }
+        if (H % 32 == 0 && hipFuncSetAttribute((const void*)k_tts_lstm_mw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lstm_mw_lds(H)) != hipSuccess) return false;
+        saved_sync = t->lstm_sync; saved_H = t->lstm_H; t->lstm_sync = t->hook_sync; t->lstm_H = t->hook_H; in_lstm = true;
+        return true;
+    }
+    void end_lstm() {
+        if (!in_lstm) return;
+        t->lstm_sync = saved_sync; t->lstm_H = saved_H; in_lstm = false;
+        (void)hipFuncSetAttribute((const void*)k_tts_lstm_mw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lstm_mw_lds(t->g.H));
+    }
+};
+SKW_KOKORO_OP_EXPORTS(skw_tts_debug_op_, skw_tts*, GpuOpSide)
+extern "C" void skw_tts_debug_lstm_epoch(skw_tts* t, unsigned epoch) { std::lock_guard<std::mutex> l(t->mu); t->lstm_epoch = epoch & 0xFFFFFu; }
+extern "C" unsigned skw_tts_debug_lstm_epoch_get(skw_tts* t) { std::lock_guard<std::mutex> l(t->mu); return t->lstm_epoch; }
+extern "C" int skw_tts_debug_lstm_error(skw_tts* t) {
+    std::lock_guard<std::mutex> l(t->mu); int e = -1;
+    if (hipSetDevice(t->device) != hipSuccess || hipMemcpy(&e, t->own_sync + 4 * t->g.H, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return e;
+}

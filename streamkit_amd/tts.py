@@ -42,7 +42,79 @@ def tts_lib():
     L.skw_tts_last_ms.restype = C.c_float; L.skw_tts_last_ms.argtypes = [C.c_void_p]
     L.skw_tts_generate_ids.restype = C.POINTER(_Audio); L.skw_tts_generate_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float]
     L.skw_tts_debug_enable.argtypes = [C.c_void_p, C.c_int]; L.skw_tts_debug_conv_mode.argtypes = [C.c_int]; L.skw_tts_debug_lstm_mode.argtypes = [C.c_int]
+    L.skw_tts_debug_conv_tile.argtypes = [C.c_int, C.c_int]; L.skw_tts_debug_launch_counts.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.skw_tts_debug_lstm_epoch.argtypes = [C.c_void_p, C.c_uint]; L.skw_tts_debug_lstm_epoch_get.argtypes = [C.c_void_p]; L.skw_tts_debug_lstm_epoch_get.restype = C.c_uint
+    L.skw_tts_debug_lstm_error.argtypes = [C.c_void_p]
     return L
+
+
+COUNTERS = ("conv", "t12", "t14", "t18", "t28", "convtr_direct", "convtr_phased", "convtr_phase_launches", "lstm", "lstm_mw", "lstm_mw_max_wg")
+TILES = {(1, 2): "t12", (1, 4): "t14", (1, 8): "t18", (2, 8): "t28"}
+ACTS = {"leaky02": 0, "leaky01": 1, "leaky001": 2, "gelu": 3}
+
+
+def launch_counts(L, reset=False):
+    """skw_tts_debug_launch_counts as a dict keyed by COUNTERS"""
+    v = (C.c_long * len(COUNTERS))()
+    n = L.skw_tts_debug_launch_counts(v, len(COUNTERS), 1 if reset else 0)
+    assert n == len(COUNTERS), n
+    return dict(zip(COUNTERS, [int(x) for x in v]))
+
+
+class KokoroOps:
+    """One Kokoro operator at a time, from numpy arrays (include/skw_kokoro_ops.h): the product's skw_tts_debug_op_* (prefix, an engine handle) and the checker's skwo_kokoro_op_*
+    (its own prefix, no handle) have the same seven signatures.  Activations are [T][C] float32."""
+
+    def __init__(self, lib, prefix, handle=None):
+        self.h = handle; P, F, I, L_ = C.c_void_p, C.c_float, C.c_int, C.c_long
+        sig = {"conv": [P, P, I, I, P, I, I, P, I, I, I, P, L_], "convtr": [P, P, I, P, I, I, I, P, I, I, I, I, P, L_], "layernorm": [P, P, I, I, P, P, F, P, L_],
+               "ada_ln": [P, P, I, I, P, P, L_], "ada_in_act": [P, P, I, I, P, I, P, L_], "attention": [P, P, P, P, I, I, P, L_], "lstm_bi": [P, P, I, I, I, P, P, L_]}
+        self.f = {}
+        for name, args in sig.items():
+            f = getattr(lib, prefix + name); f.restype = L_; f.argtypes = args; self.f[name] = f
+
+    @staticmethod
+    def _a(x):
+        return None if x is None else np.ascontiguousarray(x, np.float32)
+
+    def _run(self, name, n_out, shape, *args):
+        out = np.full(n_out, np.nan, np.float32); keep = [self._a(a) if isinstance(a, np.ndarray) else a for a in args]
+        n = self.f[name](self.h, *[a.ctypes.data if isinstance(a, np.ndarray) else a for a in keep], out.ctypes.data, out.size)
+        if n != n_out:
+            raise RuntimeError("%s: returned %d, expected %d elements" % (name, n, n_out))
+        return out.reshape(shape)
+
+    def conv(self, x, w, bias, stride=1, dil=1, pad=0):
+        (T, Ci), (Co, Ci2, K) = x.shape, w.shape; assert Ci == Ci2
+        To = (T + 2 * pad - dil * (K - 1) - 1) // stride + 1
+        return self._run("conv", To * Co, (To, Co), self._a(x), T, Ci, self._a(w), Co, K, self._a(bias), stride, dil, pad)
+
+    def convtr(self, x, w, bias, stride, pad, out_pad=0, depthwise=False):
+        T, Ci = x.shape; K = w.shape[2]; Co = Ci if depthwise else w.shape[1]; assert w.shape[0] == Ci
+        To = (T - 1) * stride - 2 * pad + K + out_pad
+        return self._run("convtr", To * Co, (To, Co), self._a(x), T, self._a(w), Ci, Co, K, self._a(bias), stride, pad, out_pad, 1 if depthwise else 0)
+
+    def layernorm(self, x, gamma, beta, eps):
+        T, Cn = x.shape
+        return self._run("layernorm", T * Cn, (T, Cn), self._a(x), T, Cn, self._a(gamma), self._a(beta), float(eps))
+
+    def ada_ln(self, x, gb):
+        T, Cn = x.shape; assert gb.size == 2 * Cn
+        return self._run("ada_ln", T * Cn, (T, Cn), self._a(x), T, Cn, self._a(gb))
+
+    def ada_in_act(self, x, gb, act):
+        T, Cn = x.shape; assert gb.size == 2 * Cn
+        return self._run("ada_in_act", T * Cn, (T, Cn), self._a(x), T, Cn, self._a(gb), ACTS[act])
+
+    def attention(self, q, k, v, heads):
+        T, Cn = q.shape; assert Cn == 64 * heads and k.shape == q.shape == v.shape
+        return self._run("attention", T * Cn, (T, Cn), self._a(q), self._a(k), self._a(v), T, heads)
+
+    def lstm_bi(self, x, ws):
+        """ws: 8 arrays, per direction weight_ih [4H][In], weight_hh [4H][H], bias_ih [4H], bias_hh [4H]"""
+        T, In = x.shape; H = ws[1].shape[1]; keep = [self._a(w) for w in ws]
+        ptrs = (C.c_void_p * 8)(*[w.ctypes.data for w in keep])
+        return self._run("lstm_bi", T * 2 * H, (T, 2 * H), self._a(x), T, In, H, ptrs)
 
 
 class Tts:
@@ -81,6 +153,10 @@ class Tts:
         n = self.L.skw_tts_debug_get(self.h, what, None, 0)
         out = np.zeros(n, np.float32); self.L.skw_tts_debug_get(self.h, what, out.ctypes.data, n)
         return out
+
+    def ops(self):
+        """the product's operator hooks on this engine's stream and arena"""
+        return KokoroOps(self.L, "skw_tts_debug_op_", self.h)
 
     def last_ms(self):
         return self.L.skw_tts_last_ms(self.h)
