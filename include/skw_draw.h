@@ -1,5 +1,5 @@
 /*
- * skw_draw.h — the two SERIAL chains of the sampler's workgroup-wide draw (block_discrete_draw, streamkit_amd/csrc/skw_kernels.hip), host and device.
+ * skw_draw.h — the two SERIAL chains of the sampler's workgroup-wide draw (block_discrete_draw, streamkit_amd/csrc/skw_kernels_sample.hip), host and device.
  *
  * std::discrete_distribution as libstdc++ implements it is sequential: sum = p_0 + p_1 + ... in f64, q_i = p_i / sum, cp_i = q_0 + ... + q_i with the last forced to 1.0,
  * the first i with cp_i >= u.  The kernel stages the row through LDS in chunks of SKW_DRAW_CHUNK doubles, with the largest element of every SKW_DRAW_BLOCK of them beside

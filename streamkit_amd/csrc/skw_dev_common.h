@@ -1,11 +1,20 @@
-// skw_dev_common.h — device helpers shared by the exact (skw_kernels.hip) and the f16-MFMA (skw_kernels_f16.hip) kernels:
-// conversions with pinned rounding, ggml's GELU table lookup, and the GEMM epilogues (identical in both precisions: only the
-// contraction differs).
+// skw_dev_common.h — device helpers shared by the exact (skw_kernels_gemm.hip, _attn_enc, _dec, _sample) and the f16-MFMA (skw_kernels_f16.hip)
+// kernels: conversions with pinned rounding, ggml's GELU table lookup, wave- and block-wide reductions, the packed exponential, and the GEMM
+// epilogues (identical in both precisions: only the contraction differs).
 #pragma once
 #define SKW_WINDOW_RULES_DEVICE_PART      // (kernel files: skw_window_rules.h without its host rules)
 #include "skw_kernels.h"
+#include <hip/hip_ext.h>
 #include "../../include/skw_math.h"
 #include "../../include/skw_ggml_quant.h"
+
+// A launch that stamps ev_start / ev_stop itself when they are given: hipExtLaunchKernelGGL stamps them at the kernel's own begin and end — the
+// duration rocprofv3 reports — instead of an event pair around the launch, which adds the dispatch gap.  Without events: the plain launch.
+template <typename... KArgs, typename... Args>
+static inline void skw_launch_ev(void (*kernel)(KArgs...), dim3 grid, dim3 blk, size_t lds, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, Args... args) {
+    if (ev_start) hipExtLaunchKernelGGL(kernel, grid, blk, lds, s, ev_start, ev_stop, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, blk, lds, s, args...);
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -85,6 +94,46 @@ __device__ __forceinline__ float skw_wave_max_f32(float v) {
     const float r0 = __int_as_float(__builtin_amdgcn_readlane(b, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(b, 16)),
                 r2 = __int_as_float(__builtin_amdgcn_readlane(b, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(b, 48));
     return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+}
+// Block-wide forms (every thread of the block calls; sh: one slot per wave): the waves' results meet in LDS and combine in ascending wave order.
+__device__ __forceinline__ float block_max(float v, float* sh) {
+    v = skw_wave_max_f32(v);
+    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if ((threadIdx.x & 63) == 0) sh[w] = v;
+    __syncthreads();
+    float r = sh[0]; for (int i = 1; i < nw; ++i) r = fmaxf(r, sh[i]);
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
+    v = skw_wave_sum_f64(v);
+    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if ((threadIdx.x & 63) == 0) sh[w] = v;
+    __syncthreads();
+    double r = 0.0; for (int i = 0; i < nw; ++i) r += sh[i];
+    __syncthreads();
+    return r;
+}
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+// skw_expf for a pair of non-positive arguments: same operations as include/skw_math.h (the x > 88.7 and n > 127 branches cannot
+// trigger for x <= 0; y * 2^n == ldexp(y, n) exactly while the result is normal, which x >= -86 guarantees)
+__device__ __forceinline__ f32x2 expf_nonpos_x2(f32x2 x) {
+    f32x2 t = x * (f32x2){1.44269504088896341f, 1.44269504088896341f};
+    f32x2 n = {__builtin_rintf(t[0]), __builtin_rintf(t[1])};
+    f32x2 r = __builtin_elementwise_fma(n, (f32x2){-0.693359375f, -0.693359375f}, x);
+    r = __builtin_elementwise_fma(n, (f32x2){2.12194440e-4f, 2.12194440e-4f}, r);
+    f32x2 p = {1.9875691500e-4f, 1.9875691500e-4f};
+    p = __builtin_elementwise_fma(p, r, (f32x2){1.3981999507e-3f, 1.3981999507e-3f});
+    p = __builtin_elementwise_fma(p, r, (f32x2){8.3334519073e-3f, 8.3334519073e-3f});
+    p = __builtin_elementwise_fma(p, r, (f32x2){4.1665795894e-2f, 4.1665795894e-2f});
+    p = __builtin_elementwise_fma(p, r, (f32x2){1.6666665459e-1f, 1.6666665459e-1f});
+    p = __builtin_elementwise_fma(p, r, (f32x2){5.0000001201e-1f, 5.0000001201e-1f});
+    f32x2 r2 = r * r;
+    f32x2 y = __builtin_elementwise_fma(p, r2, r) + (f32x2){1.0f, 1.0f};
+    f32x2 o;
+    o[0] = (x[0] >= -86.0f) ? __builtin_ldexpf(y[0], (int)n[0]) : 0.0f;
+    o[1] = (x[1] >= -86.0f) ? __builtin_ldexpf(y[1], (int)n[1]) : 0.0f;
+    return o;
 }
 // NC slots of 64 elements per row: 12 covers d <= 768 with half the instructions (same operations on the live elements); FULL: d == 64 NC, no tail predicates
 template <int R, int NC = 24, bool FULL = false>

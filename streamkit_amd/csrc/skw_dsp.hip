@@ -1,5 +1,5 @@
 // skw_dsp.hip — the resampler front end of libskw_engine.so: a model-free device context (skw_dsp), the linear and polyphase resamplers and the streaming polyphase
-// form.  Uses neither skw_model nor skw_ctx; the kernels are skw_kernels.hip's (skw_resample_*_launch).
+// form.  Uses neither skw_model nor skw_ctx; the kernels are skw_kernels_resample.hip's (skw_resample_*_launch).
 #include "skw_engine_priv.h"
 
 // ------------------------------------------------------------------ resampler front end (R1-R3), model-free device context

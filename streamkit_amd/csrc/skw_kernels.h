@@ -224,7 +224,7 @@ struct SkwLogitParams {
 // skw_full_params, in device memory, written by the host per window like prompt_buf.  suppress_nst also selects the row's static mask of the pair.
 struct SkwRowRules { int32_t suppress_blank, suppress_nst, no_timestamps, single_segment, max_tokens, tid0_initial, pad[2]; };
 // SkwLogitParams = 15 model constants + any_sampled (per pass) + the 6 request fields above.  A field added to it must be put on one side: a request field that is not also in
-// SkwRowRules (and copied by smp_row_rules, skw_kernels.hip) would be baked into the step graphs of mixed calls as a constant.  These two sizes make such an addition stop here.
+// SkwRowRules (and copied by smp_row_rules, skw_kernels_sample.hip) would be baked into the step graphs of mixed calls as a constant.  These two sizes make such an addition stop here.
 static_assert(sizeof(SkwLogitParams) == (15 + 1 + 6) * sizeof(int) && sizeof(SkwRowRules) == (6 + 2) * sizeof(int32_t), "classify the new field: model constant or per-row request rule");
 // whisper_process_logits + whisper_sample_token(best) + the per-token state update of whisper_full_with_state.
 // logits: [B][n_vocab] (modified in place), static_mask: [n_vocab] bytes (1 = always suppressed: specials, langs, nst list when enabled)

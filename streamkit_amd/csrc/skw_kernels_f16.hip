@@ -1,6 +1,6 @@
 // skw_kernels_f16.hip — the "f16_mfma" precision of the encoder's contractions (K2, K4-K6) for gfx950.
 //
-// Same operands, layouts and epilogues as the exact kernels in skw_kernels.hip; only the contraction differs: the f16 values
+// Same operands, layouts and epilogues as the exact kernels in skw_kernels_gemm.hip, skw_kernels_attn_enc.hip and skw_kernels_dec.hip; only the contraction differs: the f16 values
 // go to the matrix cores as f16 (v_mfma_f32_16x16x32_f16, f32 accumulate, 16x the rate of the f32-input MFMA) instead of
 // being widened and chained in k order.  The hardware's internal summation order is not a simple chain (tools/probe/probe_mfma.hip),
 // so results are close to, not bit-identical with, the oracle's: the parity bar in this mode is identical token ids / timestamps /

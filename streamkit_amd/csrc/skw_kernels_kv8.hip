@@ -4,7 +4,7 @@
 //
 //   k_kv8_quantize           a layer's f16 fragment-order cross K / V^T images (skw_kfrag_off / skw_vtfrag_off) -> the q8 image (skw_kv8_*_off), all slots of the encode call in
 //                            one launch; a slot's key count comes from device memory (slot_k; null: n_ctx) and decides what is a pad — never the value
-//   k_dec_cross_attn_kv8     k_dec_cross_attn16's one streaming pass (skw_kernels.hip) over the q8 image: four waves per (row, head) taking every fourth 32-key block, RD records
+//   k_dec_cross_attn_kv8     k_dec_cross_attn16's one streaming pass (skw_kernels_dec.hip) over the q8 image: four waves per (row, head) taking every fourth 32-key block, RD records
 //                            in flight per wave, non-temporal buffer loads, the final combine of the four (m, l, O) in LDS.  Per record:
 //     scores   q quantised in the prologue (two q8_0 blocks; amax across the four lane groups by two shuffles).  S[key] = one v_mfma_i32_16x16x32_i8 per key tile and d half
 //              (A = 16 keys x 32 d, 8 bytes per lane; B = the q block broadcast to every column), then the chain of skw_kv8_score on the VALU: two exact integer dots, two scale
@@ -245,9 +245,7 @@ __global__ __launch_bounds__(256 * HPW, (HPW >= 3) ? 1 : 3 / HPW) void k_dec_cro
 template <bool VARK, bool RAW>
 static void kv8_launch(dim3 grid, dim3 blk, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, const half_t* q, long ldq, const uint8_t* img, int n_ctx, int Tpad, int H, half_t* out,
                        long ldo, const int* active, int as, int f32_out, const int* seq, int ofrag_k, SkwKClk* clk, const int* nkeys, float* raw) {
-    if (ev_start) hipExtLaunchKernelGGL((k_dec_cross_attn_kv8<3, SKW_KV8_RD, VARK, RAW>), grid, blk, 0, s, ev_start, ev_stop, 0, q, ldq, img, n_ctx, Tpad, H, out, ldo, active, as, f32_out, seq,
-                                        ofrag_k, clk, nkeys, raw);
-    else hipLaunchKernelGGL((k_dec_cross_attn_kv8<3, SKW_KV8_RD, VARK, RAW>), grid, blk, 0, s, q, ldq, img, n_ctx, Tpad, H, out, ldo, active, as, f32_out, seq, ofrag_k, clk, nkeys, raw);
+    skw_launch_ev(k_dec_cross_attn_kv8<3, SKW_KV8_RD, VARK, RAW>, grid, blk, 0, s, ev_start, ev_stop, q, ldq, img, n_ctx, Tpad, H, out, ldo, active, as, f32_out, seq, ofrag_k, clk, nkeys, raw);
 }
 void skw_dec_cross_attn_kv8(const half_t* q, const uint8_t* img, int B, int H, int d, int n_ctx, int Tpad, half_t* out, const int* active, hipStream_t s, int f32_out, const int* seq,
                             hipEvent_t ev_start, hipEvent_t ev_stop, int ofrag, SkwKClk* clk, const int* nkeys, float* raw) {

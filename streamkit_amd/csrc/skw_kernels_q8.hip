@@ -46,7 +46,6 @@ void skw_q8_quantize(const float* x, long ldx, int M, int K, int8_t* q, float* d
     hipLaunchKernelGGL(k_q8_quantize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, M, K, q, dT, sT);
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // skw_ggml_block_dot for a lane's four adjacent features at once, two per packed-f32 instruction (v_pk_mul_f32 / v_pk_add_f32 round each
 // element exactly as the scalar forms do; nothing is contracted): the kernels below are VALU-bound on this update
 template <int FORM>

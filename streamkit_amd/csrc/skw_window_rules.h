@@ -1,6 +1,6 @@
 // skw_window_rules.h — the decision rules of whisper_full_with_state that need no device: plain integer and double arithmetic on one window's tokens and bookkeeping.
 //
-// The token loop's update is the one function here that also runs on the device (the tail of both samplers, skw_kernels.hip); everything else is host code the engine's window
+// The token loop's update is the one function here that also runs on the device (the tail of both samplers, smp_commit in skw_kernels_sample.hip); everything else is host code the engine's window
 // loop calls between GPU phases (skw_engine.hip).  Nothing here knows the model, the context or HIP beyond SKW_HD, so g++ compiles the header alone:
 // tests/cpp/window_rules_main.cpp drives every function of it (tests/test_cpu_window_rules.py, plain and under the host sanitizers), against the fixture and the oracle's
 // statement of the same rules (oracle/skw_oracle.c: token_loop_update, window_output).

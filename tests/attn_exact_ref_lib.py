@@ -69,7 +69,7 @@ def skw_expf(x):
 
 
 def expf_unclamped(x):
-    """expf_nonpos_x2_softmax of skw_kernels.hip for finite x <= 0: the same polynomial, ldexp instead of the clamp — below -86 a subnormal, some e < 2^-124, or 0"""
+    """expf_nonpos_x2_softmax of skw_kernels_attn_enc.hip for finite x <= 0: the same polynomial, ldexp instead of the clamp — below -86 a subnormal, some e < 2^-124, or 0"""
     x = np.asarray(x, np.float32)
     y, n = _exp_poly(x)
     return np.ldexp(y, n.astype(np.int32)).astype(np.float32)

@@ -1,5 +1,5 @@
 // draw_main.cpp — include/skw_draw.h's serial walks as a program of its own (tests/test_cpu_sampler_draw.py), staged exactly as block_discrete_draw
-// (streamkit_amd/csrc/skw_kernels.hip) stages a row: SKW_DRAW_CHUNK doubles per chunk, one bmax per SKW_DRAW_BLOCK elements, q = p / sum for the whole row between the chains.
+// (streamkit_amd/csrc/skw_kernels_sample.hip) stages a row: SKW_DRAW_CHUNK doubles per chunk, one bmax per SKW_DRAW_BLOCK elements, q = p / sum for the whole row between the chains.
 // stdin: int32 words — the record count, then per record: n, the two words of u (a double's bit pattern, low word first), then n f32 bit patterns (the weights).
 // stdout, one line per record: index, the bits of sum (hex), blocks the first chain skipped, blocks of the row, blocks the second chain skipped, blocks the second
 // chain reached (up to and including the hit's) — then the plain sequential definition (oracle/skw_oracle.c discrete_draw, libstdc++'s): index, bits of sum.

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def direct_form(x, ch, in_rate, out_rate):
-    """y[o] = sum_t h[ph][t] * x[base - (T/2 - 1) + t], o*M = base*L + ph, zeros outside the signal (skw_kernels.hip k_resample_polyphase)"""
+    """y[o] = sum_t h[ph][t] * x[base - (T/2 - 1) + t], o*M = base*L + ph, zeros outside the signal (skw_kernels_resample.hip k_resample_polyphase)"""
     L, M, T, h = pr.design(in_rate, out_rate)
     x = np.asarray(x, np.float64).reshape(-1, ch)
     n_in = x.shape[0]
