@@ -151,7 +151,10 @@ void skw_full_default_params(skw_full_params*);
 int  skw_audio_ctx_for_samples(int n_samples, int n_audio_ctx);
 
 /* ---- the hot path ---- */
-/* pcm[i]: 16 kHz mono f32, n_samples[i] samples; host pointers (pcm_on_device = 0) or device pointers (= 1).
+/* One call, one request: skw_full_batch_request(ctx, &skw_full_request) — the struct stands further down, behind the types it names.  Every skw_full_batch* function and
+ * skw_align_batch below is skw_full_batch_request with these fields set: its arguments go to the fields of the same name, everything else stays zero.  Each keeps its place here
+ * because its comment is the contract of the field it introduced.
+ * pcm[i]: 16 kHz mono f32, n_samples[i] samples; host pointers (pcm_on_device = 0) or device pointers (= 1).
  * results[i] is filled and must be released with skw_result_free. n_clips <= max_batch. Returns 0 on success. */
 int  skw_full_batch(skw_ctx*, const skw_full_params*, const float* const* pcm, const int32_t* n_samples, int n_clips,
                     int pcm_on_device, skw_result* results);
@@ -259,6 +262,50 @@ int  skw_full_batch_traced(skw_ctx*, const skw_full_params*, const float* const*
 int  skw_full_batch_traced_context(skw_ctx*, const skw_full_params*, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                    const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, int32_t* const* context, skw_result* results);
 void skw_trace_free(skw_trace*);
+
+/* ---- the request: what every entry above fills in ----
+ * A field left zero asks for nothing, and a feature's array in which no clip asks is that call without the array, launch for launch (the paragraphs above, field by field).
+ * size is what lets the struct grow at its end: a caller compiled against an older header hands in its own sizeof, the fields it does not know stay zero.  A size below
+ * SKW_FULL_REQUEST_MIN (the struct as it was first published) or above this library's sizeof fails with -1 and a message.
+ * params_per_clip picks the launches, not just the reading of params: 0 is the uniform form (skw_full_batch, _rng, _traced*), 1 the per-row form (_mixed and every entry after it,
+ * skw_align_batch) even where all blocks are equal — same results, different kernels.
+ * Combinations no entry above offers are refused with -3 before anything runs: traces with params_per_clip, rng_state, rules, align or grammar; text_tokens with rng_state,
+ * context, rules, grammar or traces; forced_ids without n_forced or without traces.  A refused call writes back no generator state and no context; times[i] and traces[i] are
+ * zeroed before anything is checked, so they are defined after a failed call. */
+typedef struct {
+    uint32_t size;              /* sizeof(skw_full_request) as the caller compiled it */
+    int32_t  params_per_clip;   /* 0: params is ONE block (the uniform launches); 1: params[n_clips] (the per-row launches) */
+    const skw_full_params* params;
+    const float* const* pcm; const int32_t* n_samples; int32_t n_clips; int32_t pcm_on_device;
+    uint32_t* const* rng_state;                 /* NULL, or [n_clips], entries may be NULL */
+    int32_t* const* context;                    /* as skw_full_batch_context */
+    const skw_decode_rules* const* rules;       /* as skw_full_batch_rules */
+    const skw_align_params* const* align; skw_token_times* times;      /* as skw_full_batch_aligned */
+    const skw_grammar* const* grammar;          /* as skw_full_batch_grammar */
+    const int32_t* const* text_tokens; const int32_t* n_text;          /* forced alignment, as skw_align_batch: nothing is decoded; results may be NULL */
+    const int32_t* const* forced_ids; const int32_t* n_forced; skw_trace* traces;   /* traces != NULL: as skw_full_batch_traced_context */
+    skw_result* results;
+} skw_full_request;
+#define SKW_FULL_REQUEST_MIN 136
+int skw_full_batch_request(skw_ctx*, const skw_full_request*);
+
+/* Test hook: one sampler launch (constrain -> grammar -> sampler, as in the decode step) on caller-supplied logits; skw_engine.hip states it next to the code.  The five
+ * skw_debug_sample_rows* hooks are this request with their arguments filled in.  trace = 0, temperature, rng_state and the pointers behind them are not offered together with
+ * rules or grammar (-3 before the launch). */
+typedef struct {
+    int32_t  params_per_row;    /* 0: params is ONE block (the uniform launch); 1: params[n_rows] (the per-row launch) */
+    int32_t  n_rows;
+    const skw_full_params* params;
+    const int32_t* hist; int32_t hist_stride; int32_t form; const int32_t* n_hist; const float* logits;      /* hist [n_rows][hist_stride], logits [n_rows][n_vocab] on the host */
+    float* filtered_out; skw_token* tok_out; skw_trace_step* trace_out;
+    const skw_decode_rules* const* rules; const skw_grammar* const* grammar;      /* NULL, or [n_rows] with entries that may be NULL */
+    const int32_t* active;      /* NULL, or [n_rows]: 0 marks a row as finished before the launch */
+    const float* temperature; uint32_t* rng_state;      /* [n_rows] / [n_rows][SKW_RNG_STATE_WORDS], in and out */
+    int32_t trace;              /* 1: the launch with the trace buffers (what every hook but _ex runs); 0: without, trace_out is left alone */
+    int32_t kernel_id;          /* out: SKW_SMPK_* bits of the kernel the launcher picked */
+    float* probs_out; float* no_speech_prob; int32_t* n_tokens; int32_t* cur_token; int32_t* active_out;      /* the rows' state after the launch */
+} skw_sample_rows_request;
+int skw_debug_sample_rows_request(skw_ctx*, skw_sample_rows_request*);
 
 /* timing of the last skw_full_batch (milliseconds, GPU events on the engine's stream) */
 typedef struct { float mel_ms, encode_ms, decode_ms, total_ms; int32_t n_windows, n_decode_steps, n_tokens;

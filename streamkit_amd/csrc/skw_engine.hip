@@ -829,24 +829,20 @@ static int move_retry_slots(skw_ctx* c, const std::vector<int>& old_slots) {
 // The rules of whisper_full_with_state a window is decided by (ladder, prompt, verdict, prompt_past, segment cut, seek advance, contexts) are skw_window_rules.h; what is here
 // is the GPU orchestration around them.
 
-// What an entry point asks for.  pv: skw_full_batch_mixed — one skw_full_params per clip (p is then unused).  Everything a request decides is read through P(clip); the sampler
-// takes the rows' rules from device memory (skw_dec_sample_rows).  Without pv every P(clip) is *p and the launches are the uniform ones.
+// What an entry point asks for: the public skw_full_request (include/skw_engine.h) and what validate_request derives from it.  Everything a request decides is read through
+// P(clip); the sampler takes the rows' rules from device memory (skw_dec_sample_rows).  With params_per_clip = 0 every P(clip) is *params and the launches are the uniform ones.
+static_assert(sizeof(skw_full_request) == SKW_FULL_REQUEST_MIN, "SKW_FULL_REQUEST_MIN is the struct as first published: a new field goes to the END and leaves the constant alone");
 namespace {      // (internal linkage: none of this reaches the library's symbol table)
-struct FullRequest {
-    const skw_full_params* p = nullptr; const skw_full_params* pv = nullptr;
-    const float* const* pcm = nullptr; const int32_t* n_samples = nullptr; int n_clips = 0; int pcm_on_device = 0; skw_result* results = nullptr;
-    const int32_t* const* forced_ids = nullptr; const int32_t* n_forced = nullptr; std::vector<std::vector<SkwTraceStep>>* traces = nullptr;      // tracing / teacher forcing
-    uint32_t* const* rng_state = nullptr; int32_t* const* context = nullptr;
-    const skw_decode_rules* const* rules = nullptr; bool constrained = false;      // skw_full_batch_rules; constrained: some clip's record is not the default (set by validate_request)
-    // skw_full_batch_aligned: a clip's record (NULL / not enabled: the clip is not aligned) and where its token times go; aligned: some clip asked (set by validate_request)
-    const skw_align_params* const* align = nullptr; skw_token_times* times = nullptr; bool aligned = false;
-    // skw_align_batch: no decoding — text[i][0 .. n_text[i]) is aligned to clip i's first window
-    const int32_t* const* text = nullptr; const int32_t* n_text = nullptr;
-    const skw_grammar* const* grammar = nullptr; bool grammared = false;      // skw_full_batch_grammar; grammared: some clip has one (set by validate_request)
+struct FullRequest : skw_full_request {
+    bool constrained = false;      // rules: some clip's record is not the default
+    bool aligned = false;          // align: some clip asked (a NULL / not enabled record: the clip is not aligned)
+    bool grammared = false;        // grammar: some clip has one
+    std::vector<std::vector<SkwTraceStep>> trace_steps;      // tracing / teacher forcing: per clip the records collect_window gathers, finish_call hands out
+    explicit FullRequest(const skw_full_request& q) : skw_full_request(q) {}
     bool wants_align(int ci) const { return align && align[ci] && align[ci]->enabled; }
-    bool mixed() const { return pv != nullptr; }
+    bool mixed() const { return params_per_clip != 0; }
     bool tracing() const { return traces != nullptr; }
-    const skw_full_params& P(int ci) const { return pv ? pv[ci] : *p; }
+    const skw_full_params& P(int ci) const { return params_per_clip ? params[ci] : *params; }
     int K_of(int ci, const skw_hparams& hp) const { return P(ci).audio_ctx > 0 ? P(ci).audio_ctx : hp.n_audio_ctx; }      // the clip's audio context, every window of it
 };
 // The call's host state, per clip unless said otherwise
@@ -896,6 +892,14 @@ static int ensure_trace_buffers(skw_ctx* c) {
 static int validate_request(skw_ctx* c, FullRequest& rq) {
     char* errbuf = c->errbuf; const skw_hparams& hp = c->m->hp;
     if (rq.n_clips < 1 || rq.n_clips > c->max_batch) { snprintf(errbuf, 512, "n_clips %d outside [1, %d]", rq.n_clips, c->max_batch); return -1; }
+    // combinations no entry point offers (only skw_full_batch_request can ask for them)
+    if (rq.traces && (rq.params_per_clip || rq.rng_state || rq.rules || rq.align || rq.grammar)) {
+        snprintf(errbuf, 512, "traces cannot be combined with params_per_clip, rng_state, rules, align or grammar (they are not part of the traced entries)"); return -3; }
+    if (rq.text_tokens && (rq.rng_state || rq.context || rq.rules || rq.grammar || rq.traces)) {
+        snprintf(errbuf, 512, "text_tokens (forced alignment: nothing is decoded) cannot be combined with rng_state, context, rules, grammar or traces"); return -3; }
+    if (rq.forced_ids && (!rq.n_forced || !rq.traces)) { snprintf(errbuf, 512, "forced_ids needs n_forced and traces"); return -3; }
+    if (rq.text_tokens && !rq.n_text) { snprintf(errbuf, 512, "text_tokens needs n_text"); return -3; }
+    if (rq.text_tokens) for (int i = 0; i < rq.n_clips; ++i) if (!rq.text_tokens[i]) { snprintf(errbuf, 512, "clip %d: no text tokens", i); return -3; }
     for (int i = 0; i < rq.n_clips; ++i) if (rq.P(i).audio_ctx < 0 || rq.P(i).audio_ctx > hp.n_audio_ctx) {
         snprintf(errbuf, 512, "clip %d: audio_ctx %d outside [0, %d] (0 = the model's n_audio_ctx)", i, rq.P(i).audio_ctx, hp.n_audio_ctx); return -3; }
     // contexts handed in (skw_full_batch_context) are checked before anything is launched: a refused call leaves every context, like every generator state, as it was
@@ -913,18 +917,17 @@ static int validate_request(skw_ctx* c, FullRequest& rq) {
         if (!checked && !skw_grammar_check(rq.grammar[i], who, errbuf, 512)) return -3;
         if (rq.grammar[i]) rq.grammared = true;
     }
-    if (rq.grammared && rq.tracing()) { snprintf(errbuf, 512, "grammars are not part of the traced entries"); return -3; }
     rq.aligned = false;
     if (rq.align) for (int i = 0; i < rq.n_clips; ++i) {
         if (!skw_align_check_params(rq.align[i], hp.n_text_layer, hp.n_text_head, i, errbuf, 512)) return -3;
         if (rq.wants_align(i)) rq.aligned = true;
     }
     if (rq.aligned && !rq.times) { snprintf(errbuf, 512, "alignment asked for without a place for the token times"); return -3; }
-    if (rq.text) for (int i = 0; i < rq.n_clips; ++i) {
+    if (rq.text_tokens) for (int i = 0; i < rq.n_clips; ++i) {
         if (!rq.wants_align(i)) { snprintf(errbuf, 512, "clip %d: skw_align_batch needs an enabled alignment record", i); return -3; }
         if (rq.n_text[i] < 1 || rq.n_text[i] > hp.n_text_ctx / 2) { snprintf(errbuf, 512, "clip %d: %d text tokens outside [1, %d]", i, rq.n_text[i], hp.n_text_ctx / 2); return -3; }
-        for (int k = 0; k < rq.n_text[i]; ++k) if (rq.text[i][k] < 0 || rq.text[i][k] >= c->m->tok_eot) {
-            snprintf(errbuf, 512, "clip %d: text token %d (id %d) is not a text token", i, k, rq.text[i][k]); return -3; }
+        for (int k = 0; k < rq.n_text[i]; ++k) if (rq.text_tokens[i][k] < 0 || rq.text_tokens[i][k] >= c->m->tok_eot) {
+            snprintf(errbuf, 512, "clip %d: text token %d (id %d) is not a text token", i, k, rq.text_tokens[i][k]); return -3; }
         if (rq.n_samples[i] > WHISPER_SAMPLE_RATE * 30) { snprintf(errbuf, 512, "clip %d: skw_align_batch aligns one window (at most 30 s of audio)", i); return -3; }
     }
     return 0;
@@ -937,7 +940,7 @@ static int load_call(skw_ctx* c, const FullRequest& rq, CallState& cs) {
     if (c->kclk_on && kclk_reset(c)) return -1;
     HIPCHK(hipEventRecord(c->ev[0], c->stream));
     if (load_clips(c, rq.pcm, rq.n_samples, n_clips, rq.pcm_on_device, cs.n_len, cs.n_len_org)) return -1;
-    if (rq.mixed()) build_static_mask_pair(c); else build_static_mask(c, rq.p);
+    if (rq.mixed()) build_static_mask_pair(c); else build_static_mask(c, rq.params);
     run_mel(c, n_clips);
     HIPCHK(hipEventRecord(c->ev[1], c->stream));
     for (int ci = 0; ci < n_clips; ++ci) cs.temps[ci] = skw_temperature_ladder(rq.P(ci).temperature, rq.P(ci).temperature_inc);      // (a clip's own ladder)
@@ -1178,7 +1181,7 @@ static int step_loop(skw_ctx* c, const FullRequest& rq, CallState& cs, const Win
 
 // The rows' state and tokens come back and the stream drains (the batch's host vectors may go after this); then per row the pass's verdict — this window again at the next
 // temperature, or its output and the advance of seek (whisper_full_with_state's tail, skw_window_rules.h)
-static int collect_window(skw_ctx* c, const FullRequest& rq, CallState& cs, const WindowBatch& w) {
+static int collect_window(skw_ctx* c, FullRequest& rq, CallState& cs, const WindowBatch& w) {
     char* errbuf = c->errbuf; const skw_model* m = c->m; const int Bw = w.Bw; const std::vector<int>& act = w.act;
     HIPCHK(hipMemcpyAsync(c->h_st, c->st, sizeof(SkwSeqState) * Bw, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(c->h_toks, c->toks, sizeof(SkwTokenOut) * Bw * c->max_tok, hipMemcpyDeviceToHost, c->stream));
@@ -1192,7 +1195,7 @@ static int collect_window(skw_ctx* c, const FullRequest& rq, CallState& cs, cons
             if (rq.forced_ids && rq.forced_ids[ci] && cs.f_cursor[ci] + n > rq.n_forced[ci]) { snprintf(errbuf, 512,
                 "clip %d: forced token sequence exhausted (%d given, decision %d reached): the runs' control flow diverged", ci, rq.n_forced[ci], cs.f_cursor[ci] + n);
             return -4; }
-            (*rq.traces)[ci].insert((*rq.traces)[ci].end(), tb.begin() + (size_t)j * c->max_tok, tb.begin() + (size_t)j * c->max_tok + n);
+            rq.trace_steps[ci].insert(rq.trace_steps[ci].end(), tb.begin() + (size_t)j * c->max_tok, tb.begin() + (size_t)j * c->max_tok + n);
             cs.f_cursor[ci] += n;
         }
     }
@@ -1341,11 +1344,16 @@ static int finish_call(skw_ctx* c, const FullRequest& rq, CallState& cs) {
         tot_tokens += res.n_tokens;
     }
     if (rq.times) for (int i = 0; i < n_clips; ++i) {      // per result token (skw_align_batch: per given text token); -1 where no time was computed
-        const size_t nt = rq.text ? (size_t)rq.n_text[i] : cs.acc[i].tok.size();
+        const size_t nt = rq.text_tokens ? (size_t)rq.n_text[i] : cs.acc[i].tok.size();
         cs.tt0[i].resize(nt, -1); cs.tt1[i].resize(nt, -1);
         skw_token_times& tt = rq.times[i]; tt.n = (int32_t)nt;
         tt.t0 = (int64_t*)malloc(sizeof(int64_t) * std::max<size_t>(1, nt)); tt.t1 = (int64_t*)malloc(sizeof(int64_t) * std::max<size_t>(1, nt));
         memcpy(tt.t0, cs.tt0[i].data(), sizeof(int64_t) * nt); memcpy(tt.t1, cs.tt1[i].data(), sizeof(int64_t) * nt);
+    }
+    if (rq.traces) for (int i = 0; i < n_clips; ++i) {      // every sampling decision of the clip, in execution order
+        const std::vector<SkwTraceStep>& tr = rq.trace_steps[i];
+        rq.traces[i].n = (int32_t)tr.size(); rq.traces[i].steps = (skw_trace_step*)malloc(sizeof(skw_trace_step) * std::max<size_t>(1, tr.size()));
+        memcpy(rq.traces[i].steps, tr.data(), sizeof(skw_trace_step) * tr.size());
     }
     prof_collect(c);
     { float a = 0, t = 0; hipEventElapsedTime(&a, c->ev[0], c->ev[1]); hipEventElapsedTime(&t, c->ev[0], c->ev[5]);
@@ -1409,7 +1417,7 @@ static int grammar_upload(skw_ctx* c, const skw_grammar* const* gv, int n) {
     return 0;
 }
 
-static int full_batch_impl(skw_ctx* c, FullRequest rq) {
+static int full_batch_impl(skw_ctx* c, FullRequest& rq) {
     char* errbuf = c->errbuf; errbuf[0] = 0;
     WS_READY(c);
     if (int rc = validate_request(c, rq)) return rc;
@@ -1419,15 +1427,15 @@ static int full_batch_impl(skw_ctx* c, FullRequest rq) {
     CallState cs(rq.n_clips); c->al_tap_next = 0;
     if (int rc = load_call(c, rq, cs)) return rc;
     if (int rc = detect_languages(c, rq, cs)) return rc;
-    cs.lp = rq.mixed() ? mixed_logit_params(c->m) : make_logit_params(c->m, rq.p);
+    cs.lp = rq.mixed() ? mixed_logit_params(c->m) : make_logit_params(c->m, rq.params);
     while (true) {
         WindowBatch w;      // (alive until collect_window has synchronised the stream)
         if (!plan_window(rq, cs, w)) break;
         if (int rc = stage_window(c, rq, cs, w)) return rc;
-        if (rq.text) {      // skw_align_batch: the encoder has run on the clips' one window; the given text stands where a decoded window's would
+        if (rq.text_tokens) {      // skw_align_batch: the encoder has run on the clips' one window; the given text stands where a decoded window's would
             HIPCHK(hipStreamSynchronize(c->stream));
             for (int j = 0; j < w.Bw; ++j) { const int ci = w.act[j]; CallState::AlignJob job{ci, j, 0, w.ks[j], {}, {}};
-                for (int k = 0; k < rq.n_text[ci]; ++k) { job.text.push_back(rq.text[ci][k]); job.idx.push_back(k); }
+                for (int k = 0; k < rq.n_text[ci]; ++k) { job.text.push_back(rq.text_tokens[ci][k]); job.idx.push_back(k); }
                 cs.align_jobs.push_back(job); }
             if (int rc = align_window(c, rq, cs)) return rc;
             break;
@@ -1445,12 +1453,42 @@ template <typename F> static int guarded(skw_ctx* c, const char* entry, F&& body
     try { return body(); }
     catch (const std::exception& e) { snprintf(c->errbuf, 512, "%s: %s", entry, e.what()); return -5; }
 }
-static FullRequest make_request(const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device, skw_result* results) {
-    FullRequest rq; rq.p = p; rq.pcm = pcm; rq.n_samples = n_samples; rq.n_clips = n_clips; rq.pcm_on_device = pcm_on_device; rq.results = results;
-    return rq;
+// The one function behind every entry point; entry: the caller's name, for the guard's message.  times[i] and traces[i] are zeroed first: they are defined after a failed call.
+// Forced alignment decodes nothing: a caller without results gets the phases' bookkeeping on scratch ones, freed with the call.
+static int full_batch_call(skw_ctx* c, const char* entry, const skw_full_request& q) {
+    static_assert(sizeof(skw_trace_step) == sizeof(SkwTraceStep), "skw_trace_step is SkwTraceStep");
+    return guarded(c, entry, [&] {
+        FullRequest rq(q);
+        if (rq.times) for (int i = 0; i < rq.n_clips; ++i) { rq.times[i].n = 0; rq.times[i].t0 = rq.times[i].t1 = nullptr; }
+        if (rq.traces) { for (int i = 0; i < rq.n_clips; ++i) { rq.traces[i].n = 0; rq.traces[i].steps = nullptr; } rq.trace_steps.resize(std::max(0, rq.n_clips)); }
+        std::vector<skw_result> scratch;
+        if (rq.text_tokens && !rq.results) { scratch.resize(std::max(1, rq.n_clips)); memset((void*)scratch.data(), 0, sizeof(skw_result) * scratch.size()); rq.results = scratch.data(); }
+        const int rc = full_batch_impl(c, rq);
+        for (skw_result& r : scratch) skw_result_free(&r);
+        return rc; });
+}
+
+extern "C" int skw_full_batch_request(skw_ctx* c, const skw_full_request* in) {
+    skw_full_request q; memset(&q, 0, sizeof q);
+    if (!in || in->size < SKW_FULL_REQUEST_MIN || in->size > sizeof q) {
+        snprintf(c->errbuf, 512, "skw_full_batch_request: size %u outside [%d, %zu] (sizeof(skw_full_request) as the caller compiled it)", in ? in->size : 0u, SKW_FULL_REQUEST_MIN, sizeof q);
+        return -1; }
+    memcpy(&q, in, std::min<size_t>(in->size, sizeof q));
+    if (!q.params || (!q.results && !q.text_tokens)) { snprintf(c->errbuf, 512, "skw_full_batch_request: params and results must be given (results may be NULL with text_tokens)"); return -1; }
+    return full_batch_call(c, "skw_full_batch_request", q);
+}
+// ---- the entry points of before the request: each is its own argument check and the fields it sets
+static skw_full_request request_of(int per_clip, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device, skw_result* results) {
+    skw_full_request q; memset(&q, 0, sizeof q);
+    q.size = sizeof q; q.params_per_clip = per_clip; q.params = params; q.pcm = pcm; q.n_samples = n_samples; q.n_clips = n_clips; q.pcm_on_device = pcm_on_device; q.results = results;
+    return q;
+}
+static bool params_given(skw_ctx* c, const char* entry, const skw_full_params* params) {
+    if (!params) snprintf(c->errbuf, 512, "%s: params is NULL (one skw_full_params per clip)", entry);
+    return params != nullptr;
 }
 extern "C" int skw_full_batch(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device, skw_result* results) {
-    return guarded(c, "skw_full_batch", [&] { return full_batch_impl(c, make_request(p, pcm, n_samples, n_clips, pcm_on_device, results)); });
+    return full_batch_call(c, "skw_full_batch", request_of(0, p, pcm, n_samples, n_clips, pcm_on_device, results));
 }
 extern "C" void skw_rng_state_init(uint32_t* state) {      // std::mt19937(0), as whisper_init_state leaves decoder 0's generator
     state[0] = 0u; for (int i = 1; i < 624; ++i) state[i] = 1812433253u * (state[i - 1] ^ (state[i - 1] >> 30)) + (uint32_t)i;
@@ -1458,51 +1496,43 @@ extern "C" void skw_rng_state_init(uint32_t* state) {      // std::mt19937(0), a
 }
 extern "C" int skw_full_batch_rng(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                   uint32_t* const* rng_state, skw_result* results) {
-    return guarded(c, "skw_full_batch_rng", [&] {
-        FullRequest rq = make_request(p, pcm, n_samples, n_clips, pcm_on_device, results); rq.rng_state = rng_state;
-        return full_batch_impl(c, rq); });
+    skw_full_request q = request_of(0, p, pcm, n_samples, n_clips, pcm_on_device, results); q.rng_state = rng_state;
+    return full_batch_call(c, "skw_full_batch_rng", q);
 }
 extern "C" int skw_full_batch_mixed(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                     uint32_t* const* rng_state, skw_result* results) {
-    return guarded(c, "skw_full_batch_mixed", [&] {
-        if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_mixed: params is NULL (one skw_full_params per clip)"); return -1; }
-        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state;
-        return full_batch_impl(c, rq); });
+    if (!params_given(c, "skw_full_batch_mixed", params)) return -1;
+    skw_full_request q = request_of(1, params, pcm, n_samples, n_clips, pcm_on_device, results); q.rng_state = rng_state;
+    return full_batch_call(c, "skw_full_batch_mixed", q);
 }
 extern "C" int skw_full_batch_context(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                       uint32_t* const* rng_state, int32_t* const* context, skw_result* results) {
-    return guarded(c, "skw_full_batch_context", [&] {
-        if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_context: params is NULL (one skw_full_params per clip)"); return -1; }
-        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state; rq.context = context;
-        return full_batch_impl(c, rq); });
+    if (!params_given(c, "skw_full_batch_context", params)) return -1;
+    skw_full_request q = request_of(1, params, pcm, n_samples, n_clips, pcm_on_device, results); q.rng_state = rng_state; q.context = context;
+    return full_batch_call(c, "skw_full_batch_context", q);
 }
 extern "C" void skw_decode_rules_default(skw_decode_rules* r) { skw_decode_rules_set_default(r); }
 extern "C" int skw_full_batch_rules(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                     uint32_t* const* rng_state, int32_t* const* context, const skw_decode_rules* const* rules, skw_result* results) {
-    return guarded(c, "skw_full_batch_rules", [&] {
-        if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_rules: params is NULL (one skw_full_params per clip)"); return -1; }
-        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state; rq.context = context; rq.rules = rules;
-        return full_batch_impl(c, rq); });
+    if (!params_given(c, "skw_full_batch_rules", params)) return -1;
+    skw_full_request q = request_of(1, params, pcm, n_samples, n_clips, pcm_on_device, results); q.rng_state = rng_state; q.context = context; q.rules = rules;
+    return full_batch_call(c, "skw_full_batch_rules", q);
 }
 extern "C" int skw_full_batch_aligned(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                       uint32_t* const* rng_state, int32_t* const* context, const skw_decode_rules* const* rules, const skw_align_params* const* align,
                                       skw_token_times* times, skw_result* results) {
-    return guarded(c, "skw_full_batch_aligned", [&] {
-        if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_aligned: params is NULL (one skw_full_params per clip)"); return -1; }
-        if (times) for (int i = 0; i < n_clips; ++i) { times[i].n = 0; times[i].t0 = times[i].t1 = nullptr; }
-        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state; rq.context = context; rq.rules = rules;
-        rq.align = align; rq.times = times;
-        return full_batch_impl(c, rq); });
+    if (!params_given(c, "skw_full_batch_aligned", params)) return -1;
+    skw_full_request q = request_of(1, params, pcm, n_samples, n_clips, pcm_on_device, results); q.rng_state = rng_state; q.context = context; q.rules = rules;
+    q.align = align; q.times = times;
+    return full_batch_call(c, "skw_full_batch_aligned", q);
 }
 extern "C" int skw_full_batch_grammar(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                       uint32_t* const* rng_state, int32_t* const* context, const skw_decode_rules* const* rules, const skw_align_params* const* align,
                                       skw_token_times* times, const skw_grammar* const* grammar, skw_result* results) {
-    return guarded(c, "skw_full_batch_grammar", [&] {
-        if (!params) { snprintf(c->errbuf, 512, "skw_full_batch_grammar: params is NULL (one skw_full_params per clip)"); return -1; }
-        if (times) for (int i = 0; i < n_clips; ++i) { times[i].n = 0; times[i].t0 = times[i].t1 = nullptr; }
-        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, results); rq.pv = params; rq.rng_state = rng_state; rq.context = context; rq.rules = rules;
-        rq.align = align; rq.times = times; rq.grammar = grammar;
-        return full_batch_impl(c, rq); });
+    if (!params_given(c, "skw_full_batch_grammar", params)) return -1;
+    skw_full_request q = request_of(1, params, pcm, n_samples, n_clips, pcm_on_device, results); q.rng_state = rng_state; q.context = context; q.rules = rules;
+    q.align = align; q.times = times; q.grammar = grammar;
+    return full_batch_call(c, "skw_full_batch_grammar", q);
 }
 extern "C" int skw_grammar_compile(const char* pattern, size_t len, int flags, float penalty, skw_grammar** out, char* err, size_t errlen) {
     return skw_grammar_compile_impl(pattern, len, flags, penalty, out, err, errlen);
@@ -1511,33 +1541,16 @@ extern "C" void skw_grammar_free(skw_grammar* g) { skw_grammar_free_impl(g); }
 extern "C" long skw_debug_grammar_uploads(const skw_ctx* c) { return c->gr_uploads; }      // tests: device allocations made for grammars so far (the vocabulary image, then one per cache miss)
 extern "C" int skw_align_batch(skw_ctx* c, const skw_full_params* params, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                const int32_t* const* text_tokens, const int32_t* n_text, const skw_align_params* const* align, skw_token_times* times) {
-    return guarded(c, "skw_align_batch", [&] {
-        if (!params || !text_tokens || !n_text || !align || !times) { snprintf(c->errbuf, 512, "skw_align_batch: params, text_tokens, n_text, align and times must all be given"); return -1; }
-        for (int i = 0; i < n_clips; ++i) { times[i].n = 0; times[i].t0 = times[i].t1 = nullptr; }
-        for (int i = 0; i < n_clips; ++i) if (!text_tokens[i]) { snprintf(c->errbuf, 512, "clip %d: no text tokens", i); return -3; }
-        std::vector<skw_result> res(std::max(1, n_clips)); memset((void*)res.data(), 0, sizeof(skw_result) * res.size());
-        FullRequest rq = make_request(params, pcm, n_samples, n_clips, pcm_on_device, res.data()); rq.pv = params; rq.align = align; rq.times = times;
-        rq.text = text_tokens; rq.n_text = n_text;
-        const int rc = full_batch_impl(c, rq);
-        for (int i = 0; i < n_clips; ++i) skw_result_free(&res[i]);
-        return rc; });
+    if (!params || !text_tokens || !n_text || !align || !times) { snprintf(c->errbuf, 512, "skw_align_batch: params, text_tokens, n_text, align and times must all be given"); return -1; }
+    skw_full_request q = request_of(1, params, pcm, n_samples, n_clips, pcm_on_device, nullptr); q.align = align; q.times = times; q.text_tokens = text_tokens; q.n_text = n_text;
+    return full_batch_call(c, "skw_align_batch", q);
 }
 extern "C" void skw_token_times_free(skw_token_times* t) { if (!t) return; free(t->t0); free(t->t1); t->t0 = t->t1 = nullptr; t->n = 0; }
 extern "C" int skw_full_batch_traced_context(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                              const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, int32_t* const* context, skw_result* results) {
-    static_assert(sizeof(skw_trace_step) == sizeof(SkwTraceStep), "skw_trace_step is SkwTraceStep");
-    return guarded(c, "skw_full_batch_traced", [&] {      // (both traced entry points report under this name)
-        if (!traces || (forced_ids && !n_forced)) { snprintf(c->errbuf, 512, "skw_full_batch_traced: bad arguments"); return -1; }
-        for (int i = 0; i < n_clips; ++i) { traces[i].n = 0; traces[i].steps = nullptr; }
-        std::vector<std::vector<SkwTraceStep>> tr(std::max(0, n_clips));
-        FullRequest rq = make_request(p, pcm, n_samples, n_clips, pcm_on_device, results); rq.forced_ids = forced_ids; rq.n_forced = n_forced; rq.traces = &tr; rq.context = context;
-        const int rc = full_batch_impl(c, rq);
-        if (rc) return rc;
-        for (int i = 0; i < n_clips; ++i) {
-            traces[i].n = (int32_t)tr[i].size(); traces[i].steps = (skw_trace_step*)malloc(sizeof(skw_trace_step) * std::max<size_t>(1, tr[i].size()));
-            memcpy(traces[i].steps, tr[i].data(), sizeof(skw_trace_step) * tr[i].size());
-        }
-        return 0; });
+    if (!traces || (forced_ids && !n_forced)) { snprintf(c->errbuf, 512, "skw_full_batch_traced: bad arguments"); return -1; }
+    skw_full_request q = request_of(0, p, pcm, n_samples, n_clips, pcm_on_device, results); q.forced_ids = forced_ids; q.n_forced = n_forced; q.traces = traces; q.context = context;
+    return full_batch_call(c, "skw_full_batch_traced", q);      // (both traced entry points report under this name)
 }
 extern "C" int skw_full_batch_traced(skw_ctx* c, const skw_full_params* p, const float* const* pcm, const int32_t* n_samples, int n_clips, int pcm_on_device,
                                      const int32_t* const* forced_ids, const int32_t* n_forced, skw_trace* traces, skw_result* results) {
@@ -1586,27 +1599,33 @@ static void tap(skw_ctx* c, const char* name, const void* dev, int rows, int col
 // caller-supplied logits; ONE launch of the sampler (form 0: the one the decode step uses; form 1: the streaming kernel, which leaves the filtered row in
 // memory) makes each row's next decision.  has_ts / seek_delta / result_len are replayed from the history by the token loop's update rule, as
 // oracle/skwo_debug_process_logits does.  Outputs per row: the decision (skw_token), its trace record, and (form 1, optional) the filtered logits.
-// pv (skw_debug_sample_rows_mixed): one skw_full_params per row — the launch is the per-row form of the sampler, each row under its own rules and its own static mask.
-// rv (skw_debug_sample_rows_rules): one skw_decode_rules (or NULL) per row — k_dec_constrain runs on the rows' logits ahead of the sampler, as in the decode step.
-// ex (skw_debug_sample_rows_ex): per-row temperatures and generator states, the launch with or without the trace buffers, and what else the sampler leaves behind:
+// params_per_row (skw_debug_sample_rows_mixed): one skw_full_params per row — the launch is the per-row form of the sampler, each row under its own rules and its own static mask.
+// rules (skw_debug_sample_rows_rules): one skw_decode_rules (or NULL) per row — k_dec_constrain runs on the rows' logits ahead of the sampler, as in the decode step.
+// the fields skw_debug_sample_rows_ex fills (from its skw_sample_rows_ex): per-row temperatures and generator states, the launch with or without the trace buffers, and what
+// else the sampler leaves behind:
 //  temperature [n_rows] (null: 0 everywhere) — lp.any_sampled is 1 iff some row's is > 0; rng_state [n_rows][625], in and out (null: every row on generator 0, untouched
 //  memory of the context): row r draws from generator r (clip_idx[r] = r), an index above 624 is refused like skw_full_batch_rng's; trace = 0: forced = trace = nullptr
 //  reach the launcher (k_dec_sample<false, any_sampled, ROWS>), trace_out is left alone; probs_out [n_rows][n_vocab]: the f32 probabilities of rows at a temperature > 0
-//  (other rows' entries are left alone); no_speech_prob / n_tokens / cur_token / active [n_rows]: the row's state after the launch; kernel_id: SKW_SMPK_* bits of the
+//  (other rows' entries are left alone); no_speech_prob / n_tokens / cur_token / active_out [n_rows]: the row's state after the launch; kernel_id: SKW_SMPK_* bits of the
 //  kernel the launcher picked (skw_dec_sample_kernel, the function it branches on).
 struct skw_sample_rows_ex { const float* temperature; uint32_t* rng_state; int32_t trace; int32_t kernel_id; float* probs_out; float* no_speech_prob;
                             int32_t* n_tokens; int32_t* cur_token; int32_t* active; };
-static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const skw_full_params* pv, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
-                                  const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out,
-                                  const skw_decode_rules* const* rv = nullptr, skw_sample_rows_ex* ex = nullptr, const skw_grammar* const* gv = nullptr) {
+// The hook behind all of them (skw_sample_rows_request, include/skw_engine.h); entry: the caller's name, for the guard's message
+static int sample_rows_impl(skw_ctx* c, const char* entry, skw_sample_rows_request& q) {
+  return guarded(c, entry, [&] {
     char* errbuf = c->errbuf; errbuf[0] = 0;
+    const skw_full_params* p = q.params; const skw_full_params* pv = q.params_per_row ? q.params : nullptr; const int n_rows = q.n_rows, hist_stride = q.hist_stride, form = q.form;
+    const int32_t* hist = q.hist; const int32_t* n_hist = q.n_hist; const skw_decode_rules* const* rv = q.rules; const skw_grammar* const* gv = q.grammar;
+    const bool want_state = q.no_speech_prob || q.n_tokens || q.cur_token || q.active_out;
     WS_READY(c);
     if (n_rows < 1 || n_rows > c->max_batch) { snprintf(errbuf, 512, "n_rows %d outside [1, %d]", n_rows, c->max_batch); return -1; }
-    if (ex && ex->rng_state) for (int r = 0; r < n_rows; ++r) if (ex->rng_state[(size_t)r * SKW_RNG_WORDS + 624] > 624u) {
-        snprintf(errbuf, 512, "row %d: the generator state handed in is not a std::mt19937 state (index %u)", r, ex->rng_state[(size_t)r * SKW_RNG_WORDS + 624]); return -1; }
-    if (ex && ex->temperature && !ex->rng_state) for (int r = 0; r < n_rows; ++r) if (ex->temperature[r] > 0.0f) {
+    if ((rv || gv) && (q.temperature || q.rng_state || !q.trace || q.probs_out || want_state)) {      // (what no hook offers)
+        snprintf(errbuf, 512, "rules and grammar go with the plain launch only: no temperature, rng_state, trace = 0, probs_out or row state"); return -3; }
+    if (q.rng_state) for (int r = 0; r < n_rows; ++r) if (q.rng_state[(size_t)r * SKW_RNG_WORDS + 624] > 624u) {
+        snprintf(errbuf, 512, "row %d: the generator state handed in is not a std::mt19937 state (index %u)", r, q.rng_state[(size_t)r * SKW_RNG_WORDS + 624]); return -1; }
+    if (q.temperature && !q.rng_state) for (int r = 0; r < n_rows; ++r) if (q.temperature[r] > 0.0f) {
         snprintf(errbuf, 512, "row %d: a temperature > 0 needs rng_state (one generator per row)", r); return -1; }
-    const bool with_trace = !ex || ex->trace;
+    const bool with_trace = q.trace != 0;
     HIPCHK(hipSetDevice(c->m->device));
     const skw_model* m = c->m; const int NV = m->hp.n_vocab, MT = c->max_tok;
     for (int r = 0; r < n_rows; ++r) if (n_hist[r] < 0 || n_hist[r] >= MT || n_hist[r] > hist_stride) { snprintf(errbuf, 512, "row %d: history of %d tokens (at most %d)", r, n_hist[r], MT - 1);
@@ -1629,15 +1648,15 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
         HIPCHK(hipMemcpyAsync(c->row_rules, rules.data(), sizeof(SkwRowRules) * n_rows, hipMemcpyHostToDevice, c->stream));
     } else { build_static_mask(c, p); lp = make_logit_params(m, p); }
     lp.any_sampled = 0;
-    if (ex && ex->temperature) for (int r = 0; r < n_rows; ++r) if (ex->temperature[r] > 0.0f) lp.any_sampled = 1;
+    if (q.temperature) for (int r = 0; r < n_rows; ++r) if (q.temperature[r] > 0.0f) lp.any_sampled = 1;
     std::vector<SkwTokenOut> toks((size_t)n_rows * MT); memset(toks.data(), 0, toks.size() * sizeof(SkwTokenOut));
     std::vector<int> forced((size_t)n_rows * MT, -1), zero(n_rows, 0);
-    if (ex && ex->rng_state) for (int r = 0; r < n_rows; ++r) zero[r] = r;      // (row r on generator r)
+    if (q.rng_state) for (int r = 0; r < n_rows; ++r) zero[r] = r;      // (row r on generator r)
     for (int r = 0; r < n_rows; ++r) {
         SkwSeqState& s = c->h_st[r]; memset(&s, 0, sizeof s);
         s.active = 1; s.seek_delta = SKW_WINDOW_FRAMES; s.seek = 0; s.n_prompt = 1; s.min_margin = INFINITY;
         s.cur_pos = n_hist[r]; s.n_tokens = n_hist[r];
-        if (ex && ex->temperature) s.temperature = ex->temperature[r];
+        if (q.temperature) s.temperature = q.temperature[r];
         // the history's timestamps through the token loop's update (as the parent of this hook, oracle/skwo_debug_process_logits, replays them): how has_ts / seek_delta /
         // result_len follow them, and the one failure a history can show.  No stop rule can fire: no budget, no loop bound, the audio without end, and <|endoftext|> is no timestamp
         s.seek_end = INT32_MAX;
@@ -1647,20 +1666,20 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
                 snprintf(errbuf, 512, "row %d: the token loop cannot produce this history (timestamp goes backwards at %d)", r, i); return -1; }
         }
         s.seek_end = SKW_WINDOW_FRAMES;
-        if (c->dbg_active && !c->dbg_active[r]) s.active = 0;
+        if (q.active && !q.active[r]) s.active = 0;
         c->h_row_live[r] = 1;
     }
     HIPCHK(hipMemcpyAsync(c->st, c->h_st, sizeof(SkwSeqState) * n_rows, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->toks, toks.data(), sizeof(SkwTokenOut) * toks.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->forced_dev, forced.data(), sizeof(int) * forced.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->clip_idx, zero.data(), sizeof(int) * n_rows, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->logits, logits_host, sizeof(float) * (size_t)n_rows * NV, hipMemcpyHostToDevice, c->stream));
-    if (ex && ex->rng_state) HIPCHK(hipMemcpyAsync(c->rng, ex->rng_state, sizeof(uint32_t) * SKW_RNG_WORDS * n_rows, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->logits, q.logits, sizeof(float) * (size_t)n_rows * NV, hipMemcpyHostToDevice, c->stream));
+    if (q.rng_state) HIPCHK(hipMemcpyAsync(c->rng, q.rng_state, sizeof(uint32_t) * SKW_RNG_WORDS * n_rows, hipMemcpyHostToDevice, c->stream));
     const int* forced_dev = with_trace ? c->forced_dev : nullptr; SkwTraceStep* trace_dev = with_trace ? c->trace_dev : nullptr;
     if (rv) skw_dec_constrain(c->logits, NV, lp.tok_eot, c->row_cons, c->st, c->toks, MT, n_rows, c->stream);
     if (gv) skw_dec_grammar(c->logits, NV, lp.tok_eot, c->row_gram, c->st, c->toks, MT, n_rows, c->gr_voc_off, c->gr_voc_bytes, c->stream);
     skw_debug_force_stream_sampler(form == 1);
-    if (ex) ex->kernel_id = skw_dec_sample_kernel(lp, trace_dev != nullptr, pv != nullptr);
+    q.kernel_id = skw_dec_sample_kernel(lp, trace_dev != nullptr, pv != nullptr);
     if (pv) skw_dec_sample_rows(c->logits, c->static_mask_pair, lp, c->row_rules, c->st, c->toks, MT, n_rows, c->d_row_live, c->probs, c->rng, c->clip_idx, c->prompt_buf, c->stream,
                                 forced_dev, trace_dev);
     else skw_dec_sample(c->logits, c->static_mask, lp, c->st, c->toks, MT, n_rows, c->d_row_live, c->probs, c->rng, c->clip_idx, c->prompt_buf, c->stream, forced_dev, trace_dev);
@@ -1669,42 +1688,52 @@ static int debug_sample_rows_impl(skw_ctx* c, const skw_full_params* p, const sk
     std::vector<SkwTraceStep> tr((size_t)n_rows * MT);
     HIPCHK(hipMemcpyAsync(toks.data(), c->toks, sizeof(SkwTokenOut) * toks.size(), hipMemcpyDeviceToHost, c->stream));
     if (with_trace) HIPCHK(hipMemcpyAsync(tr.data(), c->trace_dev, sizeof(SkwTraceStep) * tr.size(), hipMemcpyDeviceToHost, c->stream));
-    if (filtered_out) HIPCHK(hipMemcpyAsync(filtered_out, c->logits, sizeof(float) * (size_t)n_rows * NV, hipMemcpyDeviceToHost, c->stream));
-    std::vector<SkwSeqState> st_after(ex ? n_rows : 0);
-    if (ex) {
-        HIPCHK(hipMemcpyAsync(st_after.data(), c->st, sizeof(SkwSeqState) * n_rows, hipMemcpyDeviceToHost, c->stream));
-        if (ex->rng_state) HIPCHK(hipMemcpyAsync(ex->rng_state, c->rng, sizeof(uint32_t) * SKW_RNG_WORDS * n_rows, hipMemcpyDeviceToHost, c->stream));
-        if (ex->probs_out && ex->temperature) for (int r = 0; r < n_rows; ++r) if (ex->temperature[r] > 0.0f)
-            HIPCHK(hipMemcpyAsync(ex->probs_out + (size_t)r * NV, c->probs + (size_t)r * skw_probs_row_floats(NV), sizeof(float) * NV, hipMemcpyDeviceToHost, c->stream));
-    }
+    if (q.filtered_out) HIPCHK(hipMemcpyAsync(q.filtered_out, c->logits, sizeof(float) * (size_t)n_rows * NV, hipMemcpyDeviceToHost, c->stream));
+    std::vector<SkwSeqState> st_after(want_state ? n_rows : 0);
+    if (want_state) HIPCHK(hipMemcpyAsync(st_after.data(), c->st, sizeof(SkwSeqState) * n_rows, hipMemcpyDeviceToHost, c->stream));
+    if (q.rng_state) HIPCHK(hipMemcpyAsync(q.rng_state, c->rng, sizeof(uint32_t) * SKW_RNG_WORDS * n_rows, hipMemcpyDeviceToHost, c->stream));
+    if (q.probs_out && q.temperature) for (int r = 0; r < n_rows; ++r) if (q.temperature[r] > 0.0f)
+        HIPCHK(hipMemcpyAsync(q.probs_out + (size_t)r * NV, c->probs + (size_t)r * skw_probs_row_floats(NV), sizeof(float) * NV, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int r = 0; r < n_rows; ++r) {
         const SkwTokenOut& t = toks[(size_t)r * MT + n_hist[r]];
-        if (tok_out) { skw_token o; o.id = t.id; o.tid = t.tid; o.p = t.p; o.plog = t.plog; o.pt = t.pt; o.ptsum = t.ptsum; o.margin = t.margin; tok_out[r] = o; }
-        if (trace_out && with_trace) memcpy(&trace_out[r], &tr[(size_t)r * MT + n_hist[r]], sizeof(skw_trace_step));
-        if (ex) {
-            if (ex->no_speech_prob) ex->no_speech_prob[r] = st_after[r].no_speech_prob;
-            if (ex->n_tokens) ex->n_tokens[r] = st_after[r].n_tokens;
-            if (ex->cur_token) ex->cur_token[r] = st_after[r].cur_token;
-            if (ex->active) ex->active[r] = st_after[r].active;
-        }
+        if (q.tok_out) { skw_token o; o.id = t.id; o.tid = t.tid; o.p = t.p; o.plog = t.plog; o.pt = t.pt; o.ptsum = t.ptsum; o.margin = t.margin; q.tok_out[r] = o; }
+        if (q.trace_out && with_trace) memcpy(&q.trace_out[r], &tr[(size_t)r * MT + n_hist[r]], sizeof(skw_trace_step));
+        if (q.no_speech_prob) q.no_speech_prob[r] = st_after[r].no_speech_prob;
+        if (q.n_tokens) q.n_tokens[r] = st_after[r].n_tokens;
+        if (q.cur_token) q.cur_token[r] = st_after[r].cur_token;
+        if (q.active_out) q.active_out[r] = st_after[r].active;
     }
-    return 0;
+    return 0; });
+}
+extern "C" int skw_debug_sample_rows_request(skw_ctx* c, skw_sample_rows_request* q) {
+    if (!q || !q->params) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_request: the request and its params are required"); return -1; }
+    return sample_rows_impl(c, "skw_debug_sample_rows_request", *q);
+}
+static skw_sample_rows_request sample_rows_of(int per_row, const skw_full_params* p, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist, const float* logits_host, int form,
+                                              float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out) {
+    skw_sample_rows_request q; memset(&q, 0, sizeof q);
+    q.params_per_row = per_row; q.params = p; q.n_rows = n_rows; q.hist = hist; q.hist_stride = hist_stride; q.n_hist = n_hist; q.logits = logits_host; q.form = form;
+    q.filtered_out = filtered_out; q.tok_out = tok_out; q.trace_out = trace_out; q.trace = 1;
+    return q;
 }
 extern "C" int skw_debug_sample_rows(skw_ctx* c, const skw_full_params* p, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist, const float* logits_host, int form,
                                      float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out) {
-    return debug_sample_rows_impl(c, p, nullptr, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out);
+    skw_sample_rows_request q = sample_rows_of(0, p, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out);
+    return sample_rows_impl(c, "skw_debug_sample_rows", q);
 }
 extern "C" int skw_debug_sample_rows_mixed(skw_ctx* c, const skw_full_params* params /* [n_rows] */, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
                                            const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out) {
     if (!params) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_mixed: params is NULL (one skw_full_params per row)"); return -1; }
-    return debug_sample_rows_impl(c, params, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out);
+    skw_sample_rows_request q = sample_rows_of(1, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out);
+    return sample_rows_impl(c, "skw_debug_sample_rows_mixed", q);
 }
 extern "C" int skw_debug_sample_rows_rules(skw_ctx* c, const skw_full_params* params /* [n_rows] */, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
                                            const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out,
                                            const skw_decode_rules* const* rules /* [n_rows], entries may be NULL */) {
     if (!params || !rules) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_rules: params and rules are one per row (rules entries may be NULL)"); return -1; }
-    return debug_sample_rows_impl(c, params, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out, rules);
+    skw_sample_rows_request q = sample_rows_of(1, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out); q.rules = rules;
+    return sample_rows_impl(c, "skw_debug_sample_rows_rules", q);
 }
 // constrain -> grammar -> sampler, as in the decode step: rules as above (NULL: no row has a record), grammar one skw_grammar (or NULL) per row.  active [n_rows] (or NULL):
 // 0 marks a row as finished before the launch — every kernel leaves it alone
@@ -1712,16 +1741,20 @@ extern "C" int skw_debug_sample_rows_grammar(skw_ctx* c, const skw_full_params* 
                                              const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out,
                                              const skw_decode_rules* const* rules, const skw_grammar* const* grammar, const int32_t* active) {
     if (!params || !grammar) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_grammar: params and grammar are one per row (grammar entries may be NULL)"); return -1; }
-    return guarded(c, "skw_debug_sample_rows_grammar", [&] {
-        c->dbg_active = active;
-        const int rc = debug_sample_rows_impl(c, params, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out, rules, nullptr, grammar);
-        c->dbg_active = nullptr; return rc; });
+    skw_sample_rows_request q = sample_rows_of(1, params, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out);
+    q.rules = rules; q.grammar = grammar; q.active = active;
+    return sample_rows_impl(c, "skw_debug_sample_rows_grammar", q);
 }
 // per_row: p is one skw_full_params per row (the per-row form of the sampler, as skw_debug_sample_rows_mixed), else one block for the launch
 extern "C" int skw_debug_sample_rows_ex(skw_ctx* c, const skw_full_params* p, int per_row, int n_rows, const int32_t* hist, int hist_stride, const int32_t* n_hist,
                                         const float* logits_host, int form, float* filtered_out, skw_token* tok_out, skw_trace_step* trace_out, skw_sample_rows_ex* ex) {
     if (!p || !ex) { snprintf(c->errbuf, 512, "skw_debug_sample_rows_ex: params and ex are required"); return -1; }
-    return debug_sample_rows_impl(c, p, per_row ? p : nullptr, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out, nullptr, ex);
+    skw_sample_rows_request q = sample_rows_of(per_row != 0, p, n_rows, hist, hist_stride, n_hist, logits_host, form, filtered_out, tok_out, trace_out);
+    q.temperature = ex->temperature; q.rng_state = ex->rng_state; q.trace = ex->trace; q.probs_out = ex->probs_out; q.no_speech_prob = ex->no_speech_prob; q.n_tokens = ex->n_tokens;
+    q.cur_token = ex->cur_token; q.active_out = ex->active;
+    const int rc = sample_rows_impl(c, "skw_debug_sample_rows_ex", q);
+    if (rc == 0) ex->kernel_id = q.kernel_id;
+    return rc;
 }
 
 // ------------------------------------------------------------------ stage taps

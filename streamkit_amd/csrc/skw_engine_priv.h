@@ -115,7 +115,6 @@ struct skw_ctx {
     // record per clip (next == nullptr: the clip has none)
     SkwRowGrammar* row_gram = nullptr; int32_t* gr_voc_off = nullptr; uint8_t* gr_voc_bytes = nullptr;
     struct GrammarImage { uint64_t hash; int n_states; std::vector<uint16_t> next; std::vector<uint8_t> accept; uint16_t* d_next; uint8_t* d_accept; long stamp; };
-    const int32_t* dbg_active = nullptr;      // skw_debug_sample_rows_grammar: rows the hook marks as finished (only inside that call)
     std::vector<GrammarImage> gr_cache; long gr_stamp = 0, gr_uploads = 0; std::vector<SkwRowGrammar> gr_clip;
     SkwSeqState* h_st = nullptr; SkwTokenOut* h_toks = nullptr; // pinned
     int* h_row_live = nullptr; int* d_row_live = nullptr;      // per-row live flags in pinned host memory and their device-side address: k_dec_sample clears a row's flag itself,

@@ -423,27 +423,29 @@ struct SharedEngine {
                     for (int i = 0; i < n; ++i) { pv[i] = batch[i]->params; differ = differ || memcmp(&pv[0], &pv[i], sizeof(skw_full_params)) != 0; }
                     // a batch in which no job has a prompt or carries context makes exactly the calls it made before contexts existed; otherwise ONE context call serves it (jobs without
                     // text hand in NULL: their rows are skw_full_batch_mixed's)
-                    std::vector<int32_t*> cxs(n); bool any_ctx = false;
-                    for (int i = 0; i < n; ++i) { cxs[i] = batch[i]->context(); any_ctx = any_ctx || cxs[i] != nullptr; }
+                    std::vector<int32_t*> cxs(n); for (int i = 0; i < n; ++i) cxs[i] = batch[i]->context();
                     // (jobs that all share one parameter block run the uniform call: the same launches as before mixed batches existed)
-                    // decoding constraints: a batch in which some job has them is ONE rules call (jobs without hand in NULL: their rows are the context call's); otherwise as before
-                    std::vector<const skw_decode_rules*> rls(n); bool any_rules = false, rules_differ = false;
-                    for (int i = 0; i < n; ++i) { rls[i] = batch[i]->decode_rules(); any_rules = any_rules || rls[i] != nullptr;
-                                                  rules_differ = rules_differ || memcmp(&batch[0]->rules, &batch[i]->rules, sizeof(skw_decode_rules)) != 0; }
-                    // word timestamps: a batch in which some job asks is ONE aligned call (jobs that do not ask hand in NULL: their rows are the rules call's); otherwise as before
-                    std::vector<const skw_align_params*> als(n); std::vector<skw_token_times> tms(n, skw_token_times{0, nullptr, nullptr}); bool any_align = false;
-                    for (int i = 0; i < n; ++i) { als[i] = batch[i]->align_params(); any_align = any_align || als[i] != nullptr; }
-                    // grammars: a batch in which some job has one is ONE grammar call (jobs without hand in NULL: their rows are the aligned call's); otherwise as before
-                    std::vector<const skw_grammar*> grs(n); bool any_gram = false;
-                    for (int i = 0; i < n; ++i) { grs[i] = batch[i]->grammar.get(); any_gram = any_gram || grs[i] != nullptr; }
-                    rc = any_gram ? skw_full_batch_grammar(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), any_ctx ? cxs.data() : nullptr, any_rules ? rls.data() : nullptr,
-                                                           any_align ? als.data() : nullptr, any_align ? tms.data() : nullptr, grs.data(), res.data())
-                       : any_align ? skw_full_batch_aligned(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), any_ctx ? cxs.data() : nullptr, any_rules ? rls.data() : nullptr,
-                                                            als.data(), tms.data(), res.data())
-                       : any_rules ? skw_full_batch_rules(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), any_ctx ? cxs.data() : nullptr, rls.data(), res.data())
-                       : any_ctx ? skw_full_batch_context(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), cxs.data(), res.data())
-                       : differ ? skw_full_batch_mixed(ctx, pv.data(), ptrs.data(), ns.data(), n, 0, rngs.data(), res.data())
-                                : skw_full_batch_rng(ctx, &pv[0], ptrs.data(), ns.data(), n, 0, rngs.data(), res.data());
+                    // decoding constraints: a batch in which some job has them hands its rules in (jobs without hand in NULL: their rows are the context call's); otherwise as before
+                    std::vector<const skw_decode_rules*> rls(n); bool rules_differ = false;
+                    for (int i = 0; i < n; ++i) { rls[i] = batch[i]->decode_rules(); rules_differ = rules_differ || memcmp(&batch[0]->rules, &batch[i]->rules, sizeof(skw_decode_rules)) != 0; }
+                    // word timestamps: a batch in which some job asks hands its records in (jobs that do not ask hand in NULL: their rows are the rules call's); otherwise as before
+                    std::vector<const skw_align_params*> als(n); std::vector<skw_token_times> tms(n, skw_token_times{0, nullptr, nullptr});
+                    for (int i = 0; i < n; ++i) als[i] = batch[i]->align_params();
+                    // grammars: a batch in which some job has one hands them in (jobs without hand in NULL: their rows are the aligned call's); otherwise as before
+                    std::vector<const skw_grammar*> grs(n); for (int i = 0; i < n; ++i) grs[i] = batch[i]->grammar.get();
+                    // ONE engine call for jobs [i0, i0 + m) — the whole batch, or one job alone: a feature's array goes in where some job of the span uses it (NULL otherwise; the
+                    // generators always), and the launches are the uniform ones exactly where no job of the span uses any and the span shares one parameter block
+                    auto used = [](const auto& v, int i0, int m) { for (int i = i0; i < i0 + m; ++i) if (v[i]) return true; return false; };
+                    auto call = [&](int i0, int m, bool one_block, skw_result* out, skw_token_times* times) {
+                        const bool cx = used(cxs, i0, m), rl = used(rls, i0, m), al = used(als, i0, m), gr = used(grs, i0, m);
+                        skw_full_request q{}; q.size = sizeof q; q.params_per_clip = (cx || rl || al || gr || !one_block) ? 1 : 0;
+                        q.params = &pv[i0]; q.pcm = &ptrs[i0]; q.n_samples = &ns[i0]; q.n_clips = m; q.rng_state = &rngs[i0]; q.results = out;
+                        q.context = cx ? &cxs[i0] : nullptr; q.rules = rl ? &rls[i0] : nullptr; q.align = al ? &als[i0] : nullptr; q.times = al ? times : nullptr;
+                        q.grammar = gr ? &grs[i0] : nullptr;
+                        return skw_full_batch_request(ctx, &q);
+                    };
+                    const bool any_ctx = used(cxs, 0, n), any_rules = used(rls, 0, n), any_align = used(als, 0, n), any_gram = used(grs, 0, n);
+                    rc = call(0, n, !differ, res.data(), tms.data());
                     g_engine_calls.fetch_add(1); g_batch_jobs.fetch_add(n); if (differ) g_mixed_calls.fetch_add(1); if (any_ctx) g_context_calls.fetch_add(1);
                     if (any_rules) g_rules_calls.fetch_add(1);
                     if (any_align) g_align_calls.fetch_add(1);
@@ -454,15 +456,9 @@ struct SharedEngine {
                         // (the engine fails the whole call and hands no generator state back) is no reason for the others to fail.  Each job again, alone, under its own
                         // parameters; every job gets its own outcome.  (Jobs with equal blocks share their configuration, and shared the call before mixed batches too.)
                         for (int i = 0; i < n; ++i) {
-                            skw_result one{}; const float* pp = ptrs[i]; uint32_t* rg = rngs[i];
-                            int32_t* cx = cxs[i];      // (the refused call wrote no context back: each job's own, as it was queued)
-                            const skw_decode_rules* rl = rls[i];
-                            const skw_align_params* al = als[i]; skw_token_times tm{0, nullptr, nullptr};
-                            const skw_grammar* gr = grs[i];      // (a job's grammar goes with it into its own call)
-                            int r1 = gr ? skw_full_batch_grammar(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, cx ? &cx : nullptr, rl ? &rl : nullptr, al ? &al : nullptr, al ? &tm : nullptr, &gr, &one)
-                                   : al ? skw_full_batch_aligned(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, cx ? &cx : nullptr, rl ? &rl : nullptr, &al, &tm, &one)
-                                   : rl ? skw_full_batch_rules(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, cx ? &cx : nullptr, &rl, &one)
-                                   : cx ? skw_full_batch_context(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &cx, &one) : skw_full_batch_rng(ctx, &pv[i], &pp, &ns[i], 1, 0, &rg, &one);
+                            // (the refused call wrote no context back: each job's own, as it was queued; its rules, alignment record and grammar go with it into its own call)
+                            skw_result one{}; skw_token_times tm{0, nullptr, nullptr};
+                            int r1 = call(i, 1, true, &one, &tm);
                             g_engine_calls.fetch_add(1);
                             if (r1 == 0) { batch[i]->result = one; batch[i]->times = tm; }
                             else { try { batch[i]->error = skw_ctx_last_error(ctx); } catch (const std::exception&) { r1 = -1; } }      // (a promise is satisfied once)

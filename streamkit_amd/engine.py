@@ -89,7 +89,7 @@ def rules_array(rules, n, n_vocab, who):
             if not isinstance(r, DecodeRules):
                 raise ValueError("%s %d: rules must be DecodeRules or None" % (who, i))
             r.check(n_vocab, "%s %d" % (who, i))
-    return list(rules), (C.c_void_p * n)(*[None if r is None else C.addressof(r) for r in rules])
+    return list(rules), _ptr_array(rules, C.addressof)
 
 
 GRAMMAR_MAX_STATES = 4096      # SKW_GRAMMAR_MAX_STATES
@@ -158,7 +158,7 @@ def grammars_array(grammars, n, who):
     for i, g in enumerate(grammars):
         if g is not None and not isinstance(g, Grammar):
             raise ValueError("%s %d: grammars must be Grammar or None" % (who, i))
-    return (C.c_void_p * n)(*[None if g is None else C.addressof(g.rec) for g in grammars])
+    return _ptr_array(grammars, lambda g: C.addressof(g.rec))
 
 
 class Segment(C.Structure):
@@ -313,6 +313,8 @@ def lib():
         L.skw_grammar_compile.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_float, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
         L.skw_grammar_free.argtypes = [C.c_void_p]
         L.skw_debug_grammar_uploads.restype = C.c_long; L.skw_debug_grammar_uploads.argtypes = [C.c_void_p]
+        L.skw_full_batch_request.argtypes = [C.c_void_p, C.POINTER(FullRequest)]
+        L.skw_debug_sample_rows_request.argtypes = [C.c_void_p, C.POINTER(SampleRowsRequest)]
         L.skw_debug_sample_rows_grammar.argtypes = [C.c_void_p, C.POINTER(FullParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
         _LIB = L
@@ -364,6 +366,39 @@ class Gemm16EpiArgs(C.Structure):      # struct skw_gemm16_epi_args (skw_hooks.h
 class SampleRowsEx(C.Structure):      # skw_sample_rows_ex (skw_engine.hip)
     _fields_ = [("temperature", C.c_void_p), ("rng_state", C.c_void_p), ("trace", C.c_int32), ("kernel_id", C.c_int32), ("probs_out", C.c_void_p), ("no_speech_prob", C.c_void_p),
                 ("n_tokens", C.c_void_p), ("cur_token", C.c_void_p), ("active", C.c_void_p)]
+
+
+class FullRequest(C.Structure):      # skw_full_request (include/skw_engine.h): what every full_batch / align_batch call is
+    _fields_ = [("size", C.c_uint32), ("params_per_clip", C.c_int32), ("params", C.POINTER(FullParams)),
+                ("pcm", C.POINTER(C.c_void_p)), ("n_samples", C.POINTER(C.c_int32)), ("n_clips", C.c_int32), ("pcm_on_device", C.c_int32),
+                ("rng_state", C.POINTER(C.c_void_p)), ("context", C.POINTER(C.c_void_p)), ("rules", C.POINTER(C.c_void_p)),
+                ("align", C.POINTER(C.c_void_p)), ("times", C.POINTER(TokenTimes)), ("grammar", C.POINTER(C.c_void_p)),
+                ("text_tokens", C.POINTER(C.c_void_p)), ("n_text", C.POINTER(C.c_int32)),
+                ("forced_ids", C.POINTER(C.c_void_p)), ("n_forced", C.POINTER(C.c_int32)), ("traces", C.POINTER(Trace)), ("results", C.POINTER(Result))]
+
+
+FULL_REQUEST_MIN = 136      # SKW_FULL_REQUEST_MIN
+
+
+class SampleRowsRequest(C.Structure):      # skw_sample_rows_request (include/skw_engine.h): what every sample_rows call is
+    _fields_ = [("params_per_row", C.c_int32), ("n_rows", C.c_int32), ("params", C.POINTER(FullParams)),
+                ("hist", C.c_void_p), ("hist_stride", C.c_int32), ("form", C.c_int32), ("n_hist", C.c_void_p), ("logits", C.c_void_p),
+                ("filtered_out", C.c_void_p), ("tok_out", C.c_void_p), ("trace_out", C.c_void_p),
+                ("rules", C.POINTER(C.c_void_p)), ("grammar", C.POINTER(C.c_void_p)), ("active", C.c_void_p),
+                ("temperature", C.c_void_p), ("rng_state", C.c_void_p), ("trace", C.c_int32), ("kernel_id", C.c_int32),
+                ("probs_out", C.c_void_p), ("no_speech_prob", C.c_void_p), ("n_tokens", C.c_void_p), ("cur_token", C.c_void_p), ("active_out", C.c_void_p)]
+
+
+def _ptr_array(items, address):
+    """[object | None] * n -> (c_void_p * n) of address(object), NULL where None (the caller keeps the objects alive)"""
+    return (C.c_void_p * len(items))(*[None if x is None else address(x) for x in items])
+
+
+def _params_for(p, per, n):
+    """the request's params: a list as an array, one block repeated n times where the launch is the per-clip / per-row one (per), else the block itself"""
+    if isinstance(p, (list, tuple)):
+        return (FullParams * len(p))(*p)
+    return (FullParams * n)(*([p] * n)) if per else C.pointer(p)
 
 
 # what a sampler launch ran (SKW_SMPK_* of skw_kernels.h): k_dec_sample<TRACE, DRAW, ROWS> or k_dec_sample_stream<ROWS>
@@ -518,112 +553,77 @@ class Context:
         grammars=[Grammar or None per clip]: skw_full_batch_grammar — the clips that bring one are decoded under it (tokens whose text cannot continue a match lose the
         grammar's penalty, <|endoftext|> loses it while the match is incomplete); None leaves the clip as it is without.  May be combined with everything align may."""
         per_clip = isinstance(params, (list, tuple))
-        if grammars is not None and (trace or forced is not None):
+        tracing = trace or forced is not None
+        if grammars is not None and tracing:
             raise ValueError("full_batch: grammars cannot be combined with trace / forced (grammars are not part of the traced entries)")
-        if align is not None and (trace or forced is not None):
+        if align is not None and tracing:
             raise ValueError("full_batch: align cannot be combined with trace / forced")
+        rq = FullRequest(size=C.sizeof(FullRequest))
         if rules is not None:
-            if trace or forced is not None:
+            if tracing:
                 raise ValueError("full_batch: rules cannot be combined with trace / forced (there is no traced entry point with decoding constraints)")
             n_in = len(device_ptrs) if device_ptrs is not None else len(clips)
-            rules_keep, rules_ptr = rules_array(rules, n_in, self.model.hp.n_vocab, "clip")
-        if trace or forced is not None:      # (checked before anything touches the library or the device)
+            rules_keep, rq.rules = rules_array(rules, n_in, self.model.hp.n_vocab, "clip")
+        if tracing:      # (checked before anything touches the library or the device)
             if per_clip:
                 raise ValueError("full_batch: trace / forced take one FullParams, not a list (tracing with per-clip parameters is not supported)")
             if rng_states is not None:
                 raise ValueError("full_batch: rng_states cannot be combined with trace / forced (the traced call starts every generator at seed 0)")
-        p = (FullParams * len(params))(*params) if per_clip else (params or self.default_params())
         if device_ptrs is not None:
             n = len(device_ptrs)
-            ptrs = (C.c_void_p * n)(*device_ptrs)
-            ns = (C.c_int32 * n)(*n_samples)
-            on_dev = 1
+            rq.pcm = (C.c_void_p * n)(*device_ptrs)
+            rq.n_samples = (C.c_int32 * n)(*n_samples)
+            rq.pcm_on_device = 1
         else:
             clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
             n = len(clips)
-            ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
-            ns = (C.c_int32 * n)(*[c.size for c in clips])
-            on_dev = 0
+            rq.pcm = _ptr_array(clips, lambda c: c.ctypes.data)
+            rq.n_samples = (C.c_int32 * n)(*[c.size for c in clips])
         if per_clip and len(params) != n:
             raise ValueError("full_batch: %d parameter blocks for %d clips" % (len(params), n))
+        # the per-clip launches as soon as a per-clip feature is asked for (the traced call takes contexts and stays uniform), the uniform ones otherwise
+        rq.params_per_clip = 1 if per_clip or grammars is not None or align is not None or rules is not None or (contexts is not None and not tracing) else 0
+        rq.params = _params_for(params or self.default_params(), rq.params_per_clip, n)
+        rq.n_clips = n
         res = (Result * n)()
-        cp = None
+        rq.results = res
         if contexts is not None:
             if len(contexts) != n:
                 raise ValueError("full_batch: %d contexts for %d clips" % (len(contexts), n))
             assert all(x is None or (x.dtype == np.int32 and x.size == CONTEXT_WORDS and x.flags["C_CONTIGUOUS"]) for x in contexts)
-            cp = (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in contexts])
-        times = None
+            rq.context = _ptr_array(contexts, lambda x: x.ctypes.data)
         if grammars is not None:
-            gp = grammars_array(grammars, n, "clip")
-            if align is not None and len(align) != n:
-                raise ValueError("full_batch: %d alignment records for %d clips" % (len(align), n))
-            sp = None
-            if rng_states is not None:
-                assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
-                sp = (C.c_void_p * n)(*[None if s is None else s.ctypes.data for s in rng_states])
-            pp = p if per_clip else (FullParams * n)(*([p] * n))
-            ap = None
-            if align is not None:
-                ap = (C.c_void_p * n)(*[None if a is None else C.addressof(a) for a in align])
-                times = (TokenTimes * n)()
-            self._check(lib().skw_full_batch_grammar(self.h, pp, ptrs, ns, n, on_dev, sp, cp, rules_ptr if rules is not None else None, ap, times, gp, res))
-        elif align is not None:
+            rq.grammar = grammars_array(grammars, n, "clip")
+        times = None
+        if align is not None:
             if len(align) != n:
                 raise ValueError("full_batch: %d alignment records for %d clips" % (len(align), n))
-            sp = None
-            if rng_states is not None:
-                assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
-                sp = (C.c_void_p * n)(*[None if s is None else s.ctypes.data for s in rng_states])
-            pp = p if per_clip else (FullParams * n)(*([p] * n))
-            ap = (C.c_void_p * n)(*[None if a is None else C.addressof(a) for a in align])
+            rq.align = _ptr_array(align, C.addressof)
             times = (TokenTimes * n)()
-            self._check(lib().skw_full_batch_aligned(self.h, pp, ptrs, ns, n, on_dev, sp, cp, rules_ptr if rules is not None else None, ap, times, res))
-        elif rules is not None:
-            sp = None
-            if rng_states is not None:
-                assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
-                sp = (C.c_void_p * n)(*[None if s is None else s.ctypes.data for s in rng_states])
-            pp = p if per_clip else (FullParams * n)(*([p] * n))
-            self._check(lib().skw_full_batch_rules(self.h, pp, ptrs, ns, n, on_dev, sp, cp, rules_ptr, res))
-        elif contexts is not None and not (trace or forced is not None):
-            sp = None
-            if rng_states is not None:
-                assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
-                sp = (C.c_void_p * n)(*[None if s is None else s.ctypes.data for s in rng_states])
-            pp = p if per_clip else (FullParams * n)(*([p] * n))
-            self._check(lib().skw_full_batch_context(self.h, pp, ptrs, ns, n, on_dev, sp, cp, res))
-        elif trace or forced is not None:
+            rq.times = times
+        if rng_states is not None:
+            assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
+            rq.rng_state = _ptr_array(rng_states, lambda s: s.ctypes.data)
+        if tracing:
             tr = (Trace * n)()
-            fptr = fn = None
+            rq.traces = tr
             if forced is not None:
                 keep = [np.ascontiguousarray(f, dtype=np.int32) for f in forced]
-                fptr = (C.c_void_p * n)(*[k.ctypes.data for k in keep])
-                fn = (C.c_int32 * n)(*[k.size for k in keep])
-            self._check(lib().skw_full_batch_traced_context(self.h, C.byref(p), ptrs, ns, n, on_dev, fptr, fn, tr, cp, res))
-            traces = []
-            for i in range(n):
-                a = np.frombuffer((C.c_char * (tr[i].n * TRACE_DT.itemsize)).from_address(tr[i].steps), dtype=TRACE_DT).copy() if tr[i].n else np.zeros(0, TRACE_DT)
-                traces.append(a)
-                lib().skw_trace_free(C.byref(tr[i]))
-        elif rng_states is not None or per_clip:
-            sp = None
-            if rng_states is not None:
-                assert len(rng_states) == n and all(s is None or (s.dtype == np.uint32 and s.size == 625 and s.flags["C_CONTIGUOUS"]) for s in rng_states)
-                sp = (C.c_void_p * n)(*[None if s is None else s.ctypes.data for s in rng_states])
-            if per_clip:
-                self._check(lib().skw_full_batch_mixed(self.h, p, ptrs, ns, n, on_dev, sp, res))
-            else:
-                self._check(lib().skw_full_batch_rng(self.h, C.byref(p), ptrs, ns, n, on_dev, sp, res))
-        else:
-            self._check(lib().skw_full_batch(self.h, C.byref(p), ptrs, ns, n, on_dev, res))
+                rq.forced_ids = _ptr_array(keep, lambda k: k.ctypes.data)
+                rq.n_forced = (C.c_int32 * n)(*[k.size for k in keep])
+        self._check(lib().skw_full_batch_request(self.h, C.byref(rq)))
         out = [_result_to_dict(res[i]) for i in range(n)]
         for i in range(n):
             lib().skw_result_free(C.byref(res[i]))
         if times is not None:
             for i in range(n):
                 out[i]["token_times"] = _times_out(times[i])
-        if trace or forced is not None:
+        if tracing:
+            traces = []
+            for i in range(n):
+                a = np.frombuffer((C.c_char * (tr[i].n * TRACE_DT.itemsize)).from_address(tr[i].steps), dtype=TRACE_DT).copy() if tr[i].n else np.zeros(0, TRACE_DT)
+                traces.append(a)
+                lib().skw_trace_free(C.byref(tr[i]))
             return out, traces
         return out
 
@@ -632,14 +632,13 @@ class Context:
         -> per clip a list of (t0, t1) in centiseconds, one per given token."""
         clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
         n = len(clips)
-        per_clip = isinstance(params, (list, tuple))
-        p = (FullParams * n)(*params) if per_clip else (FullParams * n)(*([params or self.default_params()] * n))
-        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips]); ns = (C.c_int32 * n)(*[c.size for c in clips])
         keep = [np.ascontiguousarray(t, dtype=np.int32) for t in texts]
-        tp = (C.c_void_p * n)(*[k.ctypes.data for k in keep]); tn = (C.c_int32 * n)(*[k.size for k in keep])
-        ap = (C.c_void_p * n)(*[None if a is None else C.addressof(a) for a in align])
         times = (TokenTimes * n)()
-        self._check(lib().skw_align_batch(self.h, p, ptrs, ns, n, 0, tp, tn, ap, times))
+        rq = FullRequest(size=C.sizeof(FullRequest), params_per_clip=1, params=_params_for(params or self.default_params(), 1, n), n_clips=n,
+                         pcm=_ptr_array(clips, lambda c: c.ctypes.data), n_samples=(C.c_int32 * n)(*[c.size for c in clips]),
+                         text_tokens=_ptr_array(keep, lambda k: k.ctypes.data), n_text=(C.c_int32 * n)(*[k.size for k in keep]),
+                         align=_ptr_array(align, C.addressof), times=times)
+        self._check(lib().skw_full_batch_request(self.h, C.byref(rq)))
         return [_times_out(times[i]) for i in range(n)]
 
     def set_prompt_pass(self, on):
@@ -752,11 +751,11 @@ class Context:
         NaN elsewhere), no_speech_prob, n_tokens, cur_token, active [rows] (the rows' state after the launch)."""
         per_row = isinstance(params, (list, tuple))
         R = len(hists)
+        rq = SampleRowsRequest(n_rows=R, form=int(form), trace=1 if trace else 0, kernel_id=-1)
         if rules is not None:
-            rules_keep, rules_ptr = rules_array(rules, R, self.model.hp.n_vocab, "row")
+            rules_keep, rq.rules = rules_array(rules, R, self.model.hp.n_vocab, "row")
         if per_row and len(params) != R:
             raise ValueError("sample_rows: %d parameter blocks for %d rows" % (len(params), R))
-        p = (FullParams * R)(*params) if per_row else (params or self.default_params())
         stride = max(1, max(len(h) for h in hists))
         hb = np.zeros((R, stride), dtype=np.int32)
         for r, h in enumerate(hists):
@@ -766,37 +765,33 @@ class Context:
         filt = np.empty_like(lg) if want_filtered else None
         toks = np.zeros(R, dtype=_TOKEN_DT)
         tr = np.zeros(R, dtype=TRACE_DT)
+        rq.hist, rq.hist_stride, rq.n_hist, rq.logits = hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data
+        rq.filtered_out, rq.tok_out, rq.trace_out = filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data
+        ex = temperature is not None or rng_state is not None or not trace or extras      # (what skw_debug_sample_rows_ex added: a fourth element comes back)
         if grammars is not None:
-            if temperature is not None or rng_state is not None or not trace or extras:
+            if ex:
                 raise ValueError("sample_rows: grammars= goes with the plain call only")
-            gp = grammars_array(grammars, R, "row")
+            rq.grammar = grammars_array(grammars, R, "row")
             act = None if active is None else np.ascontiguousarray(active, dtype=np.int32).reshape(R)
-            self._check(lib().skw_debug_sample_rows_grammar(self.h, p if per_row else (FullParams * R)(*([p] * R)), R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
-                                                            filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data,
-                                                            rules_ptr if rules is not None else None, gp, None if act is None else act.ctypes.data))
-            return toks, tr, filt
-        if temperature is not None or rng_state is not None or not trace or extras:
+            rq.active = None if act is None else act.ctypes.data
+        elif ex:
             if rules is not None:
                 raise ValueError("sample_rows: rules= goes with the plain call only")
-            NV = self.model.hp.n_vocab
             t = np.zeros(R, np.float32) if temperature is None else np.ascontiguousarray(temperature, dtype=np.float32).reshape(R)
             if rng_state is not None:
                 assert rng_state.dtype == np.uint32 and rng_state.shape == (R, 625) and rng_state.flags["C_CONTIGUOUS"]
-            out = dict(probs=np.full((R, NV), np.nan, np.float32), no_speech_prob=np.zeros(R, np.float32), n_tokens=np.zeros(R, np.int32), cur_token=np.zeros(R, np.int32),
-                       active=np.zeros(R, np.int32))
-            ex = SampleRowsEx(t.ctypes.data, None if rng_state is None else rng_state.ctypes.data, 1 if trace else 0, -1, out["probs"].ctypes.data, out["no_speech_prob"].ctypes.data,
-                              out["n_tokens"].ctypes.data, out["cur_token"].ctypes.data, out["active"].ctypes.data)
-            self._check(lib().skw_debug_sample_rows_ex(self.h, p if per_row else C.byref(p), 1 if per_row else 0, R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
-                                                       filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data, C.byref(ex)))
-            out["kernel"] = sampler_kernel_name(ex.kernel_id)
+                rq.rng_state = rng_state.ctypes.data
+            out = dict(probs=np.full((R, self.model.hp.n_vocab), np.nan, np.float32), no_speech_prob=np.zeros(R, np.float32), n_tokens=np.zeros(R, np.int32),
+                       cur_token=np.zeros(R, np.int32), active=np.zeros(R, np.int32))
+            rq.temperature, rq.probs_out, rq.no_speech_prob = t.ctypes.data, out["probs"].ctypes.data, out["no_speech_prob"].ctypes.data
+            rq.n_tokens, rq.cur_token, rq.active_out = out["n_tokens"].ctypes.data, out["cur_token"].ctypes.data, out["active"].ctypes.data
+        # rules and grammars run the per-row form of the sampler whatever the parameters; otherwise a list of parameters does
+        rq.params_per_row = 1 if per_row or grammars is not None or rules is not None else 0
+        rq.params = _params_for(params or self.default_params(), rq.params_per_row, R)
+        self._check(lib().skw_debug_sample_rows_request(self.h, C.byref(rq)))
+        if grammars is None and ex:
+            out["kernel"] = sampler_kernel_name(rq.kernel_id)
             return toks, tr, filt, out
-        if rules is not None:
-            self._check(lib().skw_debug_sample_rows_rules(self.h, p if per_row else (FullParams * R)(*([p] * R)), R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
-                                                          filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data, rules_ptr))
-            return toks, tr, filt
-        fn = lib().skw_debug_sample_rows_mixed if per_row else lib().skw_debug_sample_rows
-        self._check(fn(self.h, p if per_row else C.byref(p), R, hb.ctypes.data, stride, nh.ctypes.data, lg.ctypes.data, int(form),
-                       filt.ctypes.data if want_filtered else None, toks.ctypes.data, tr.ctypes.data))
         return toks, tr, filt
 
     ATTN16_FORMS = {"encoder": 0, "prefill": 1, "cross16": 2, "cross2p": 3, "self": 4}
